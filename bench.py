@@ -27,10 +27,19 @@ N = 1: the whole frame on one GPU.  N > 1 (one rank per GPU; `--gpus N` spawns i
       finish; the MD batch takes an SB range per rank.  Strong scaling: a step is the same F frames at every N.
   frames (opt-in, secondary): every rank filters whole pictures of its own, no exchange (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task description): value = luma Mpixels/s of the whole job, plus
-`roofline` for the largest device-time kernel of the step (timed live on the stream it runs on; traffic and VALU
-issue from the committed PMC profile) and `cpu_baseline` (the reference's own CPU path on this host, rank 0, N = 1,
-bounded sample).
+Prints ONE JSON line on rank 0: value = luma Mpixels/s of the whole job, ms_per_step = the wall milliseconds of one
+timed step (`--steps` of them are timed), plus `roofline` for the largest device-time kernel of the step (timed live
+on the stream it runs on; traffic and VALU issue from the committed PMC profile).
+
+A plain run sets up, warms up, times the steps, writes its outputs (`--dump-outputs DIR`) and prints the line.
+`--full` adds every measurement that takes runs of its own: the reporting matrix and the tile projection (child bench
+processes), the roofline's isolated one-frame phase, the input upload rate, the frame-buffer / ME rows (`next_rows`)
+and `cpu_baseline` (the reference's own CPU path on this host, rank 0, N = 1, bounded sample).
+
+`--dump-outputs DIR` (N = 1): after the timed steps, what the last timed step left for its caller -- the
+loop-restored picture of slot 0 in full, fixed seeded samples of the other pictures and of the MD table, and every
+slot's frame-level decisions -- as DIR/<name>.npy (float32 / float64).  The inputs depend only on the arguments, so
+two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import datetime
@@ -39,6 +48,7 @@ import os
 import sys
 import threading
 import time
+import zlib
 
 import numpy as np
 
@@ -123,6 +133,45 @@ UNPINNED = dict(case=None, q=160, lf=(16, 16, 8, 8), lam=206765, rdmult=7000, sw
                 sc=(250, 900), us=(256, 128))
 
 
+DUMP_BUDGET = 64 * 10 ** 6  # bytes of array data one --dump-outputs run may write
+DUMP_WHOLE = 52 * 10 ** 6   # the final picture is written whole when its float32 planes fit in this
+DUMP_SAMPLE = 1 << 15       # elements kept of an array that is not written whole, at most
+DUMP_SLOT_FIXED = 1 << 20   # bound on a slot's arrays that are never sampled (MD values of 4 SBs, LR units, FB tables)
+DUMP_SLOT_SAMPLED = 12      # arrays of a slot that are sampled (9 picture planes, 3 CDEF tables), 8 bytes per element
+
+
+def dump_plan(frames, picture_bytes):
+    """(whole, sample) for `frames` slots: whether slot 0's final picture (picture_bytes as float32) is written whole,
+    and the elements kept of every sampled array, so that the run stays within DUMP_BUDGET whatever the frames in
+    flight.  The picture is sampled too when it would leave fewer than 4096 elements per sampled array."""
+    for whole in (picture_bytes <= DUMP_WHOLE, False):
+        left = DUMP_BUDGET - (picture_bytes if whole else 0) - frames * DUMP_SLOT_FIXED
+        sample = min(DUMP_SAMPLE, left // (frames * DUMP_SLOT_SAMPLED * 8))
+        if sample >= 4096 or not whole:
+            return whole, int(max(sample, 256))
+
+
+class OutputDump:
+    """--dump-outputs: arrays as DIR/<name>.npy, float32 (float64 where the integers need more than 24 bits).  An array
+    of more than DUMP_SAMPLE elements that is not written whole keeps the elements at DUMP_SAMPLE indices drawn from a
+    generator seeded by its name: the same elements in every run."""
+
+    def __init__(self, path, sample=DUMP_SAMPLE):
+        self.path, self.bytes, self.sample = path, 0, sample
+        os.makedirs(path, exist_ok=True)
+
+    def put(self, name, a, whole=False):
+        a = np.asarray(a)
+        if not whole and a.size > self.sample:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).integers(0, a.size, self.sample)
+            a = a.reshape(-1)[np.sort(idx)]
+        a = np.ascontiguousarray(a, np.float64 if a.dtype.itemsize >= 4 else np.float32)
+        self.bytes += a.nbytes
+        if self.bytes > DUMP_BUDGET:
+            raise SystemExit("bench.py: --dump-outputs would write more than %d bytes at %s" % (DUMP_BUDGET, name))
+        np.save(os.path.join(self.path, name + ".npy"), a)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -132,6 +181,13 @@ def parse():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--bit-depth", type=int, default=10)
     ap.add_argument("--cdef-level", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure: the matrix and tile-projection child "
+                         "runs, the roofline's isolated phase, the upload rate, next_rows and the CPU baseline (each "
+                         "still switched off by its --no-... option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: large arrays as fixed seeded samples)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="no device-clock timing inside the LR search")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "r06", "pmc", "kernels.json"),
@@ -199,6 +255,10 @@ def parse():
     ap.add_argument("--no-matrix", action="store_true",
                     help="skip the extra configurations (north_star matrix + config 1) run as child processes")
     a = ap.parse_args()
+    if not a.full:  # a plain run: only what the headline figure needs
+        a.no_cpu_baseline, a.no_matrix, a.tile_projection = True, True, False
+    if a.dump_outputs and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.emulate_rank > 1):
+        raise SystemExit("bench.py: --dump-outputs writes whole-frame outputs: --gpus 1 without --emulate-rank only")
     a.explicit_frames = a.frames_in_flight is not None
     if a.frames_in_flight is None:
         a.frames_in_flight = _frames_in_flight(sys.argv[1:])
@@ -235,7 +295,7 @@ def run_matrix():
     res = {}
     for label, argv in MATRIX:
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-matrix"] + argv, capture_output=True,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-matrix"] + argv, capture_output=True,
                                text=True, timeout=300)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not line:
@@ -264,7 +324,7 @@ def run_projection(a):
     import subprocess
     res = {}
     for nn in (2, 4, 8):
-        argv = ["--no-matrix", "--no-tile-projection", "--no-cpu-baseline", "--emulate-rank", str(nn),
+        argv = ["--full", "--no-matrix", "--no-tile-projection", "--no-cpu-baseline", "--emulate-rank", str(nn),
                 "--width", str(a.width), "--height", str(a.height), "--bit-depth", str(a.bit_depth),
                 "--cdef-level", str(a.cdef_level), "--steps", str(max(10, min(a.steps, 40))), "--warmup", "5"]
         if a.explicit_frames:
@@ -613,6 +673,10 @@ def bench_md(a, torch, dist, n, rank, local):
     e3.record(stream)
     torch.cuda.synchronize()
     expand_ms = e2.elapsed_time(e3) / 5
+    if a.dump_outputs:  # every shape's values of a few superblocks of this rank's range
+        sbs = np.unique(np.linspace(sb0, sb1 - 1, 16).astype(int))
+        OutputDump(a.dump_outputs).put("md_sad_sse_var", np.stack([md.read(int(sb), int(sb) + 1, sp)[0] for sb in sbs]),
+                                       whole=True)
     if n > 1:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -701,19 +765,28 @@ def main():
         plan = eplans[emu_rank]
     NREF = 7
     md_refs, md_ref_y = [], []  # reference frames of the MD batch, shared by the frames in flight
-    for r in range(NREF):
-        rs, _ = synth.frame_pair(W, H, bd, seed=0x5EED0005 + 17 * (r + 1))
-        f = svtgpu.Frame(ctx, W, H, bd)
-        f.upload(rs)
-        md_refs.append(f)
-        md_ref_y.append(rs[0])
-    torch.cuda.synchronize()
+    # the input pictures are generated on the host's cores at once (numpy releases the GIL): the same arrays as one
+    # after the other, in a fraction of the set-up time
+    from concurrent.futures import ThreadPoolExecutor
+    pool = ThreadPoolExecutor(cpu_threads())
+    ref_jobs = [pool.submit(synth.frame_pair, W, H, bd, seed=0x5EED0005 + 17 * (r + 1)) for r in range(NREF)]
 
     def frame_inputs(k):
         if pin:  # the pinned case's frames (every slot the same pictures; nothing is cached between frames)
             return synth.frame_pair_int(W, H, bd, pin["seed"])
         return synth.frame_pair_int(W, H, bd, 0x5EED0010 + 0x100 * k + 0x10000 * (0 if tiled else rank)) \
             if a.inputs == "pinned" else synth.frame_pair(W, H, bd, seed=0x5EED0003 + 0x100 * k + 0x10000 * rank)
+
+    # every slot of a pinned case reads the same host arrays (generated once)
+    input_jobs = [pool.submit(frame_inputs, k) for k in range(1 if pin else a.frames_in_flight)]
+    for r in range(NREF):
+        rs, _ = ref_jobs[r].result()
+        f = svtgpu.Frame(ctx, W, H, bd)
+        f.upload(rs)
+        md_refs.append(f)
+        md_ref_y.append(rs[0])
+    torch.cuda.synchronize()
+    pool.shutdown()
 
     def make_comm(k):
         """One communicator per frame slot (created in slot order on every rank: RCCL's init is collective)."""
@@ -761,7 +834,7 @@ def main():
             # main stream: one hardware queue less per frame in flight
             self.md_stream = self.stream if a.md_main else frame_stream()
             sp = self.stream.cuda_stream
-            self.src, self.rec = frame_inputs(k)
+            self.src, self.rec = input_jobs[0 if pin else k].result()
             self.R, self.S, self.D, self.O, self.L = (svtgpu.Frame(ctx, W, H, bd) for _ in range(5))
             # a rank of a tiled picture receives only the part of the inputs its calls read (the plan's in_rect)
             inr = tplan["in_rect"] if tplan else None
@@ -805,7 +878,7 @@ def main():
                 if timed:
                     es[2].record(stream)
                 if a.cdef_sync:
-                    prm, _ = st.pick(ctrls, q, lam, sp)
+                    prm, fbs = self.cdef_last = st.pick(ctrls, q, lam, sp)
                 else:
                     st.pick_async(ctrls, q, lam, sp)
                     prm = None
@@ -840,7 +913,7 @@ def main():
             if timed:
                 es[2].record(stream)
             if a.cdef_sync:
-                prm, _ = st.pick(ctrls, q, lam, sp)
+                prm, fbs = self.cdef_last = st.pick(ctrls, q, lam, sp)
             else:  # the strength search and RD choice in stream order, the apply reading their result on the device
                 st.pick_async(ctrls, q, lam, sp)
                 prm = None
@@ -864,7 +937,7 @@ def main():
             # finish) with the boundary lines from the DLF output
             self.at_lr.set()
             if a.lr_sync:
-                lr_ft = lr.search(O, S, lr_ctrls, sp)
+                lr_ft = self.lr_ft = lr.search(O, S, lr_ctrls, sp)
                 hc("lr_search")
                 lr.apply(D, O, L, lr_ft, sp)
             else:  # search, device RD finish and apply in stream order: no host wait in the LR stage
@@ -898,14 +971,16 @@ def main():
     # host -> device bytes of a frame's inputs (recon + source + mode-info grid; resident before timing) and their
     # PCIe-inclusive upload rate from pageable host memory, measured once here
     s0 = slots[0]
-    t_up = time.perf_counter()
-    for _ in range(3):
-        s0.R.upload(s0.rec, s0.stream.cuda_stream)
-        s0.S.upload(s0.src, s0.stream.cuda_stream)
-        if a.stages == "all":
-            s0.dl.set_mode_info(mi, s0.stream.cuda_stream)
-    torch.cuda.synchronize()
-    up_s = (time.perf_counter() - t_up) / 3
+    up_s = None
+    if a.full:
+        t_up = time.perf_counter()
+        for _ in range(3):
+            s0.R.upload(s0.rec, s0.stream.cuda_stream)
+            s0.S.upload(s0.src, s0.stream.cuda_stream)
+            if a.stages == "all":
+                s0.dl.set_mode_info(mi, s0.stream.cuda_stream)
+        torch.cuda.synchronize()
+        up_s = (time.perf_counter() - t_up) / 3
     in_bytes = sum(p.nbytes for p in s0.rec) + sum(p.nbytes for p in s0.src) + (mi_bytes if a.stages == "all" else 0)
 
     errors = []
@@ -959,17 +1034,45 @@ def main():
     dt = time.perf_counter() - t0
     if a.stages == "all" and not a.lr_sync:  # the asynchronous searches' results: a device-side failure raises here
         for sl in slots:
-            sl.lr.read_result(sl.stream.cuda_stream)
+            sl.lr_ft = sl.lr.read_result(sl.stream.cuda_stream)
     dlf_rounds = None
     if a.stages in ("all", "cdef") and not a.cdef_sync:  # every slot's last asynchronous pick (errors raise)
         for sl in slots:
-            sl.cdef_last = sl.st.read_params(sl.stream.cuda_stream)[0]
+            sl.cdef_last = sl.st.read_params(sl.stream.cuda_stream)
     if a.stages == "all" and not a.dlf_sync:  # the last asynchronous level search of every slot
         for sl in slots:
             sl.lf_levels.append(sl.dl.read_levels(sl.stream.cuda_stream).levels())
         dlf_rounds = slots[0].dl.async_rounds()
     lr_tot = lr.profile(False) if not a.no_kernel_timing else None
     h2d, d2h = svtgpu.transfer_bytes(reset=True)
+    if a.dump_outputs:  # what the last timed step left for its caller, every slot
+        whole, sample = dump_plan(F, int(1.5 * W * H * 4))
+        dump = OutputDump(a.dump_outputs, sample)
+        for sl in slots:
+            sp_, pre = sl.stream.cuda_stream, "slot%d_" % sl.k
+            pictures = [("cdef_out", sl.O)]
+            if a.stages == "all":
+                pictures += [("dlf_out", sl.D), ("lr_out", sl.L)]
+            for tag, fr in pictures:
+                for p, plane in enumerate(fr.download(sp_)):
+                    dump.put(pre + tag + "_" + "yuv"[p], plane, whole=whole and tag == "lr_out" and sl.k == 0)
+            prm, fbs = sl.cdef_last
+            dump.put(pre + "cdef_params", [prm.cdef_damping, prm.cdef_bits] + list(prm.cdef_y_strength) +
+                     list(prm.cdef_uv_strength))
+            dump.put(pre + "cdef_fb_strength", fbs)
+            for tag, t_ in zip(("cdef_mse", "cdef_skip", "cdef_dir", "cdef_var"), sl.st.read(sp_)):
+                dump.put(pre + tag, t_)
+            if a.stages == "all":
+                dump.put(pre + "dlf_levels", sl.lf_levels[-1])
+                dump.put(pre + "lr_frame_types", sl.lr_ft)
+                for p in range(3):
+                    u = sl.lr.read_units(p, sp_)
+                    dump.put(pre + "lr_units_" + "yuv"[p],
+                             np.concatenate([u[f].reshape(len(u), -1) for f in u.dtype.names], axis=1))
+                sbs = np.unique(np.linspace(sl.md_range[0], sl.md_range[1] - 1, 4).astype(int))
+                dump.put(pre + "md_sad_sse_var", np.stack([sl.md.read(int(sb), int(sb) + 1, sl.md_stream.cuda_stream)[0]
+                                                           for sb in sbs]), whole=True)
+        torch.cuda.synchronize()
     if n > 1:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1031,9 +1134,10 @@ def main():
     kernels_f = kernel_table(search_ms, md_ms, lr_cls, bool(lr_tot))
     # The roofline's durations come from the condition its PMC counters were collected in: one frame in flight
     # (scripts/r5/pmc_r05.sh runs the bench at F = 1 with the LR chains serial).  With F > 1 slot 0 runs alone for a short timed phase after the
-    # main one; the contended figures of the F-frame run are reported beside it.
+    # main one; the contended figures of the F-frame run are reported beside it.  That phase is a run of its own
+    # (--full); a plain run reports the main run's figures alone.
     iso = None
-    if F > 1:
+    if F > 1 and a.full:
         s0 = slots[0]
         s0.ev = []
         # the roofline's launch spans: HIP events around each launch (rocprofv3's span), the two LR chains one after
@@ -1053,7 +1157,9 @@ def main():
     roof = roofline_of(iso["kernels"] if iso else kernels_f, bd, a.pmc_json)
     roof["condition"] = ("one frame in flight (slot 0 alone, %d timed steps after the main run, the LR search's two "
                          "chains one after the other; the PMC counters' condition)" % iso["steps"]) if iso else \
-        "one frame in flight (the main run%s)" % (", LR chains serial" if a.lr_serial else "")
+        "one frame in flight (the main run%s)" % (", LR chains serial" if a.lr_serial else "") if F == 1 else \
+        ("the main run's %d frames in flight: kernels share the CUs with the other frames' kernels, so launch "
+         "durations include queueing (--full times slot 0 alone after the main run)" % F)
     if iso:
         cont = roofline_of(kernels_f, bd, a.pmc_json)
         roof["contended"] = {"frames_in_flight": F, "kernel": cont["kernel"], "avg_launch_ms": cont["avg_launch_ms"],
@@ -1081,9 +1187,9 @@ def main():
     nfr_timed = a.steps * F
     xfer = {"h2d_bytes_per_frame": round(h2d / nfr_timed), "d2h_bytes_per_frame": round(d2h / nfr_timed),
             "input_bytes_per_frame": in_bytes,
-            "input_upload_ms": round(up_s * 1e3, 3),
-            "input_upload_GBs": round(in_bytes / up_s / 1e9, 2),
-            "pcie_inclusive_Mpx_s": round(W * H / (frame_wall_ms * 1e-3 + up_s) / 1e6, 2) if n == 1 else None,
+            "input_upload_ms": round(up_s * 1e3, 3) if up_s else None,
+            "input_upload_GBs": round(in_bytes / up_s / 1e9, 2) if up_s else None,
+            "pcie_inclusive_Mpx_s": round(W * H / (frame_wall_ms * 1e-3 + up_s) / 1e6, 2) if n == 1 and up_s else None,
             "note": "h2d/d2h: host<->device bytes of the frame-level entry points during the timed steps on this rank "
                     "(DLF trial SSEs, CDEF pick, LR records and units); the frame inputs (recon + source + the "
                     "mode-info grid, input_bytes_per_frame) are resident before timing -- an encoder uploads them "

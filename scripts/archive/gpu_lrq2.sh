@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${1:-lrq}
 mkdir -p $OUT
-B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -k "lr or pipeline or rtcd" > $OUT/pytest.log 2>&1 &&
 SVTGPU_WN_QGRID=256 timeout -k 10 200 $B --frames-in-flight 1 > $OUT/f1_q256.log 2>&1 &&
 SVTGPU_WN_QGRID=512 timeout -k 10 200 $B --frames-in-flight 1 > $OUT/f1_q512.log 2>&1 &&

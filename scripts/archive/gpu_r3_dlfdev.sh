@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_dlf_device_gpu.py -m gpu -x -v 
 grep -E "passed|failed" $O/pytest.log | tail -1
 for f in 1 4; do
   for m in 0 1; do
-    SVTGPU_DLF_DEVICE=$m timeout -k 10 300 python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-matrix --frames-in-flight $f > $O/bench_f${f}_d$m.log 2>&1 || { echo "bench failed"; tail -20 $O/bench_f${f}_d$m.log; exit 1; }
+    SVTGPU_DLF_DEVICE=$m timeout -k 10 300 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-matrix --frames-in-flight $f > $O/bench_f${f}_d$m.log 2>&1 || { echo "bench failed"; tail -20 $O/bench_f${f}_d$m.log; exit 1; }
     echo "F=$f dev=$m $(grep '^{' $O/bench_f${f}_d$m.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["config"]["frame_latency_ms"], d["config"]["stage_ms"])')"
   done
 done

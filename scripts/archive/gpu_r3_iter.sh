@@ -13,7 +13,7 @@ grep -E "passed|failed" gpurun_out/it/pytest.log | tail -1
 i=0
 for cfg in "$@"; do
   for f in 1 3; do
-    env $cfg timeout -k 10 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-matrix \
+    env $cfg timeout -k 10 300 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-matrix \
         --frames-in-flight $f > gpurun_out/it/b${i}_f$f.log 2>&1 || { echo "bench failed"; tail -20 gpurun_out/it/b${i}_f$f.log; exit 1; }
     echo "[$cfg] F=$f $(grep '^{' gpurun_out/it/b${i}_f$f.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print(d["value"], c["frame_latency_ms"], c["stage_ms"]["lr_search_apply"], c["lr_search_kernel_ms"])')"
   done

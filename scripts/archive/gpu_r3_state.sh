@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 grep -E "passed|failed" $O/pytest.log | tail -1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python bench.py > $O/bench_default.log 2>&1 || { echo "bench failed"; tail -20 $O/bench_default.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.log 2>&1 || { echo "bench failed"; tail -20 $O/bench_default.log; exit 1; }
 grep '^{' $O/bench_default.log | cut -c1-600
-timeout -k 10 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-matrix --frames-in-flight 1 > $O/bench_f1.log 2>&1 || { echo "bench f1 failed"; tail -20 $O/bench_f1.log; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-matrix --frames-in-flight 1 > $O/bench_f1.log 2>&1 || { echo "bench f1 failed"; tail -20 $O/bench_f1.log; exit 1; }
 grep '^{' $O/bench_f1.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print("F=1", d["value"], c["frame_latency_ms"], c["stage_ms"])'

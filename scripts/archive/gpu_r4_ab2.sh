@@ -13,7 +13,7 @@ for run in "1 0" "4 0" "4 8"; do
   for v in A B; do
     E=""; [ $v = B ] && E="$AB"
     X=""; [ $2 -gt 0 ] && X="--emulate-rank $2"
-    env $E timeout -k 10 300 python bench.py --steps 40 --warmup 4 --no-cpu-baseline --no-matrix --no-tile-projection --frames-in-flight $1 $X --host-timing > $O/b_${v}_f$1_e$2.log 2>&1 || { echo "bench $v $run failed"; tail -20 $O/b_${v}_f$1_e$2.log; exit 1; }
+    env $E timeout -k 10 300 python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --no-matrix --no-tile-projection --frames-in-flight $1 $X --host-timing > $O/b_${v}_f$1_e$2.log 2>&1 || { echo "bench $v $run failed"; tail -20 $O/b_${v}_f$1_e$2.log; exit 1; }
     echo "$v F=$1 emu=$2 $(grep '^{' $O/b_${v}_f$1_e$2.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; h=c.get("host_ms",{}); print(d["value"], c["frame_latency_ms"], c["stage_ms"]["dlf_pick_filter"], c["stage_ms"]["cdef_pick_apply"], c["stage_ms"]["lr_search_apply"], {k: h[k][0] for k in ("dlf_pick","cdef_pick","lr_search") if k in h})')"
   done
 done

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-r4abenv}
 mkdir -p $O
 export TMPDIR=/tmp
-B0="python3 bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps 60 --warmup 5"
+B0="python3 bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps 60 --warmup 5"
 run() { # tag value args
   env $VAR=$2 timeout -k 10 300 $B0 ${@:3} > $O/$1.log 2>&1 || { echo "bench $1 failed"; tail -20 $O/$1.log; exit 1; }
   echo "$1 $(grep '^{' $O/$1.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; s=c["stage_ms"]; print(d["value"], c["frame_latency_ms"], s["cdef_pick_apply"], s["lr_search_apply"])')"

@@ -17,7 +17,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 $O/smoke.log
 fi
 if [ -z "$NO_BENCH" ]; then
-timeout -k 10 900 python bench.py $BENCH_ARGS > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 900 python bench.py --full $BENCH_ARGS > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["value"], d["ms_per_step"], r["kernel"], r["avg_launch_ms"], r["frac"], r.get("contended", {}).get("kernel"), d["cpu_baseline"]["value"] if d.get("cpu_baseline") else None)'
 fi
 echo done

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-r4sweep}
 mkdir -p $O
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu-baseline --no-matrix --no-tile-projection"
+B="python3 bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection"
 timeout -k 10 300 rocprofv3 --kernel-trace -d $O/trace_f4 -o run --output-format csv -- $B --steps 40 --warmup 5 --frames-in-flight 4 > $O/trace_f4.log 2>&1 || { echo "trace failed"; tail -20 $O/trace_f4.log; exit 1; }
 for f in ${FS:-3 4 5 6}; do
   timeout -k 10 300 $B --steps 60 --warmup 5 --frames-in-flight $f > $O/b_f$f.log 2>&1 || { echo "bench failed"; tail -20 $O/b_f$f.log; exit 1; }

@@ -6,7 +6,7 @@ O=gpurun_out/${1:-lds}
 mkdir -p $O
 export TMPDIR=/tmp
 K="wiener_res|sgr_res|sgr_flt|wiener_stats|wiener_solve|cdef_search|cdef_apply|sod_step|dlf_tile|lr_apply|md_dist"
-timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_WAVES --kernel-include-regex "$K" -d $O/sq -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-matrix --frames-in-flight 1 --no-kernel-timing > $O/sq.log 2>&1 || { echo "pmc failed"; tail -5 $O/sq.log; exit 1; }
+timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_WAVES --kernel-include-regex "$K" -d $O/sq -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-matrix --frames-in-flight 1 --no-kernel-timing > $O/sq.log 2>&1 || { echo "pmc failed"; tail -5 $O/sq.log; exit 1; }
 python3 - "$O" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/sq/**/*counter_collection.csv", recursive=True)[0]

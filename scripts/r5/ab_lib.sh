@@ -9,7 +9,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 LIBS=${LIBS:-svt-av1_pro-anchor-v2.1.0-_amd/lib/libsvtgpu.so}
 STEPS=${STEPS:-40}
-B="python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps $STEPS --warmup 5 $BENCH_ARGS"
+B="python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps $STEPS --warmup 5 $BENCH_ARGS"
 summ() { grep '^{' $1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print(d["value"], d["ms_per_step"], c.get("stage_ms"), d["roofline"]["kernel"], d["roofline"]["avg_launch_ms"])'; }
 for L in $LIBS; do
   t=$(basename $L .so)

@@ -5,7 +5,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-r5mdm}
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps 30 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps 30 --warmup 5"
 s() { grep '^{' $1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print(d["value"], d["ms_per_step"], c.get("frame_latency_ms"), {k: round(v, 2) for k, v in c["stage_ms"].items() if k != "note"})'; }
 run() { n=$1; shift; timeout -k 10 300 $B "$@" > $O/$n.log 2>&1 || { echo "$n failed"; tail $O/$n.log; exit 1; }; echo "$n: $(s $O/$n.log)"; }
 run e8_f6 --emulate-rank 8

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 for L in ${LVLS:-1,1 0,1 1,0 0,0}; do
   for F in ${FS:-4 1}; do
     t=lr${L/,/_}_f$F
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps ${STEPS:-30} --warmup 5 --frames-in-flight $F --lr-levels $L $BENCH_ARGS > $O/$t.log 2>&1 || { echo "$t failed"; tail -20 $O/$t.log; exit 1; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps ${STEPS:-30} --warmup 5 --frames-in-flight $F --lr-levels $L $BENCH_ARGS > $O/$t.log 2>&1 || { echo "$t failed"; tail -20 $O/$t.log; exit 1; }
     echo "$t: $(grep '^{' $O/$t.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["config"].get("stage_ms"))')"
   done
 done

@@ -12,7 +12,7 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 250 --timeout-method threa
 tail -1 $O/tests.log
 fi
 VARS=${VARS:-"new: old:$ENVAB"}
-B="python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps ${STEPS:-30} --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps ${STEPS:-30} --warmup 5"
 for rep in $(seq 1 ${REPS:-2}); do
 for VE in $VARS; do
   V=${VE%%:*}; E=${VE#*:}; E=${E//,/ }

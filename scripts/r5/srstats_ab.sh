@@ -7,7 +7,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 for L in $LIBS; do
   t=$(basename $L .so)
-  SVTGPU_LIB=$L SVTGPU_SR_STATS=1 timeout -k 10 300 python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps 10 --warmup 2 --frames-in-flight 1 > $O/$t.log 2>&1 || { echo "$t failed"; tail -20 $O/$t.log; exit 1; }
+  SVTGPU_LIB=$L SVTGPU_SR_STATS=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps 10 --warmup 2 --frames-in-flight 1 > $O/$t.log 2>&1 || { echo "$t failed"; tail -20 $O/$t.log; exit 1; }
   echo "$t: $(grep '^{' $O/$t.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["config"]["stage_ms"]["lr_search_apply"])')"
   grep "sgr_res:" $O/$t.log | tail -2
 done

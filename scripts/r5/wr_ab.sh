@@ -7,7 +7,7 @@ O=gpurun_out/${1:-r5wrab}
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_lr_gpu.py tests/test_pipeline_golden.py -m gpu > $O/tests.log 2>&1 || { echo "tests failed"; tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-B="python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --steps 30 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --steps 30 --warmup 5"
 for rep in 1 2; do
   for L in svt-av1_pro-anchor-v2.1.0-_amd/lib/libsvtgpu.so $LIB; do
     t=$(basename $L .so)

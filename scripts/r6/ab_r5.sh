@@ -29,7 +29,7 @@ for R in ${REPS:-1 2}; do
         curhostfin) D=.; E="$E SVTGPU_LR_FINISH=host"; X="--dlf-sync --lr-sync" ;;
       esac
       L=$O/${C}_$(echo $V | tr ":=," "___")_${R}.log
-      ( cd $D && env $E timeout -k 10 300 python bench.py $COMMON ${CFG[$C]} $X $BENCH_ARGS ) > $L 2>&1 ||
+      ( cd $D && env $E timeout -k 10 300 python bench.py --full $COMMON ${CFG[$C]} $X $BENCH_ARGS ) > $L 2>&1 ||
         { echo "bench $C $V failed"; tail -20 $L; exit 1; }
       echo "$C $V #$R: $(summ $L)"
     done

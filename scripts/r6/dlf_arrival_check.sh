@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests/test_dlf_gpu.py tests/test_dlf_devic
 tail -1 $O/tests.log
 B="--steps 20 --warmup 3 --no-cpu-baseline --no-matrix --no-tile-projection"
 run() {
-  timeout -k 10 240 python3 bench.py $B $2 > $O/$1.log 2>&1 || { echo "$1 failed"; tail -5 $O/$1.log; exit 1; }
+  timeout -k 10 240 python3 bench.py --full $B $2 > $O/$1.log 2>&1 || { echo "$1 failed"; tail -5 $O/$1.log; exit 1; }
   echo "$1: $(grep '^{' $O/$1.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print(d["value"], d["ms_per_step"], c["concurrency"]["value"], c["concurrency"]["slot_latency_ms"], c["stage_ms"]["dlf_pick_filter"])')"
 }
 for r in 1 2 3 4; do run f4_r$r "--run-ahead 3"; done

@@ -10,7 +10,7 @@ for rep in 1 2; do
   for n in 8 4 2; do
     for f in 6 7; do
       L=$O/e${n}_f${f}_r$rep.log
-      timeout -k 10 240 python3 bench.py $B --emulate-rank $n --frames-in-flight $f > $L 2>&1 || { echo "e$n f$f failed"; tail -5 $L; exit 1; }
+      timeout -k 10 240 python3 bench.py --full $B --emulate-rank $n --frames-in-flight $f > $L 2>&1 || { echo "e$n f$f failed"; tail -5 $L; exit 1; }
       echo "e$n f$f r$rep: $(grep '^{' $L | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print(d["value"], d["ms_per_step"], c["concurrency"]["value"], c["concurrency"]["streams_per_frame"])')"
     done
   done

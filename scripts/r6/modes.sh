@@ -8,7 +8,7 @@ O=gpurun_out/${1:-r6modes}
 mkdir -p $O
 export TMPDIR=/tmp
 STEPS=${STEPS:-30}
-B="python bench.py --no-cpu-baseline --no-matrix --no-tile-projection --host-timing --steps $STEPS --warmup 5 $BENCH_ARGS"
+B="python bench.py --full --no-cpu-baseline --no-matrix --no-tile-projection --host-timing --steps $STEPS --warmup 5 $BENCH_ARGS"
 summ() { grep '^{' $1 | python -c '
 import json,sys
 d=json.loads(sys.stdin.read()); c=d["config"]

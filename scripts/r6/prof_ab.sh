@@ -12,7 +12,7 @@ B="--no-cpu-baseline --no-matrix --no-tile-projection --no-kernel-timing --steps
 for V in r5 cur; do
   D=.; X="--dlf-sync --lr-sync"
   [ $V = r5 ] && D=_ab/r5 && X=""
-  ( cd $D && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/$V -o run --output-format csv -- python3 bench.py $B $X ) \
+  ( cd $D && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/$V -o run --output-format csv -- python3 bench.py --full $B $X ) \
       > $O/$V/bench.log 2>&1 || { echo "profile $V failed"; tail -20 $O/$V/bench.log; exit 1; }
   echo "$V: $(grep '^{' $O/$V/bench.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["config"]["frame_latency_ms"])')"
 done

@@ -10,7 +10,7 @@ IFS=';' read -ra ML <<< "${MODES:-;--dlf-sync}"
 i=0
 for M in "${ML[@]}"; do
   mkdir -p $O/m$i
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/m$i -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-matrix \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/m$i -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-matrix \
       --no-tile-projection --no-kernel-timing --steps ${STEPS:-10} --warmup 3 --frames-in-flight ${F:-1} $M \
       > $O/m$i/bench.log 2>&1 || { echo "profile [$M] failed"; tail -20 $O/m$i/bench.log; exit 1; }
   f=$(find $O/m$i -name '*kernel_stats.csv' | head -1)

@@ -104,10 +104,10 @@ const char *svtgpu_version(void);
 /* ABI revision of this header: bumped whenever a struct passed across the boundary changes layout or an entry
  * point changes meaning (6: SvtGpuLrProfile::ms_events, svtgpu_comm_create_bounded, the asynchronous LR search
  * svtgpu_lr_search_frame_async; 7: svtgpu_cdef_apply_frame accepts params == NULL, svtgpu_stream_create; 8: the CCSO entry points,
- * SvtGpuCcsoParams).
+ * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 8
+#define SVTGPU_ABI_VERSION 9
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -809,6 +809,141 @@ int  svtgpu_me_search(SvtGpuMeBatch *b, const SvtGpuFrame *source, const SvtGpuF
                       int32_t sa_h, int32_t sub_sad, int32_t sb_begin, int32_t sb_end, void *stream);
 int  svtgpu_me_read(SvtGpuMeBatch *b, uint32_t *best_sad, uint32_t *best_mv, int32_t sb_begin, int32_t sb_end,
                     void *stream); /* host [sb_end - sb_begin][nref][85] each (nullable) */
+
+/* =========================================================================================
+ * Overlapped-block motion compensation (OBMC) distortion; 8-bit only, as in the reference
+ * ========================================================================================= */
+/* RTCD-compatible shims (synchronous, host pointers) for the 22 block sizes, installed by svtgpu_install_obmc_rtcd
+ * (svtgpu_rtcd.h).  wsrc and mask are compact (stride W); diff = wsrc - pre * mask.
+ * ≙ svt_aom_obmc_sad{W}x{H} (aom_dsp_rtcd.h:354-396; C sad_av1.c:18-62): sum of (|diff| + 2048) >> 12 */
+unsigned int svtgpu_aom_obmc_sad4x4(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad4x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad8x4(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad8x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad8x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad16x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad16x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad16x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad32x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad32x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad32x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad64x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad64x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad64x128(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad128x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad128x128(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad4x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad16x4(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad8x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad32x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad16x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+unsigned int svtgpu_aom_obmc_sad64x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);
+/* ≙ svt_aom_obmc_variance{W}x{H} (aom_dsp_rtcd.h:398-440; C OBMC_VAR variance.c:347-373): d = diff rounded >> 12 away
+ * from zero on ties (ROUND_POWER_OF_TWO_SIGNED); *sse = sum d^2; returns *sse - (sum d)^2 / (W * H) */
+unsigned int svtgpu_aom_obmc_variance4x4(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance4x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance8x4(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance8x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance8x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance16x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance16x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance16x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance32x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance32x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance32x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance64x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance64x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance64x128(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance128x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance128x128(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance4x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance16x4(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance8x32(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance32x8(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance16x64(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_variance64x16(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+/* ≙ svt_aom_obmc_sub_pixel_variance{W}x{H} (aom_dsp_rtcd.h:442-484; C OBMC_SUBPIX_VAR variance.c:375-390): the 2-tap
+ * bilinear interpolation (1/8 pel offsets in 0..7) of a (H + 1) x (W + 1) window of pre, then the OBMC variance */
+unsigned int svtgpu_aom_obmc_sub_pixel_variance4x4(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance4x8(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance8x4(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance8x8(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance8x16(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance16x8(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance16x16(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance16x32(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance32x16(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance32x32(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance32x64(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance64x32(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance64x64(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance64x128(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance128x64(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance128x128(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance4x16(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance16x4(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance8x32(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance32x8(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance16x64(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+unsigned int svtgpu_aom_obmc_sub_pixel_variance64x16(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+
+/* Frame level: the full-pel OBMC refinement of many blocks at once (≙ svt_av1_obmc_full_pixel_search, av1me.c:760-776:
+ * obmc_refining_search_sad, :721-758, then the OBMC variance at the MV it ends on).  One item = one call of the
+ * reference's function: the start MV is clamped to the limits, best = obmc_sad(start) + cost, and each of up to
+ * search_range steps visits the neighbours {-1,0},{0,-1},{0,1},{1,0},{-1,1},{1,1},{1,-1},{-1,-1} ({row, col}; the
+ * first four only when search_diag == 0) inside the limits in that order; a neighbour takes over when its SAD is
+ * below the running best both before and after its cost is added; the walk stops at a step nobody takes.
+ * Reference samples outside the frame read the nearest edge sample (the padded reference pictures, as svtgpu_me_search).
+ *
+ * Pools (host arrays given to svtgpu_obmc_set_items, copied to the device):
+ *   wm_pool    int32: an item's wsrc is wm_pool[wm_offset .. + w*h), its mask wm_pool[wm_offset + w*h .. + 2*w*h),
+ *              both compact (stride w); wm_offset is a multiple of 4.
+ *   cost_pool  int32, read by cost_mode 1 items only, at cost_offset, with T = 2 * search_range + 1:
+ *                [0, 4)          the joint costs x->nmv_vec_cost[MV_JOINT_ZERO, HNZVZ, HZVNZ, HNZVNZ]
+ *                [4, 4 + T)      row costs:    entry k = x->mv_cost_stack[0][clip((r0 + k - (ref_mv_row >> 3)) * 8)]
+ *                [4 + T, 4 + 2T) column costs: entry k = x->mv_cost_stack[1][clip((c0 + k - (ref_mv_col >> 3)) * 8)]
+ *              where r0 / c0 = the start row / column after the clamp to the limits, minus search_range, and clip is
+ *              CLIP3(MV_LOW, MV_UPP, .) as in svt_mv_cost (mcomp.h:135).
+ * cost_mode 0 = mvsad_err_cost_light (av1me.c:237; approx_inter_rate): 1296 + 50 * 8 * (|dcol| + |drow|) against the
+ * centre >> 3, no tables.  cost_mode 1 = mvsad_err_cost (av1me.c:254): ROUND_POWER_OF_TWO((unsigned)(joint + row +
+ * column) * sad_per_bit, AV1_PROB_COST_SHIFT).
+ *
+ * The result's variance is the ovf value alone: the caller adds svt_aom_mv_err_cost (or _light) of the final MV, which
+ * needs its RD tables (get_obmc_mvpred_var, av1me.c:709-720). */
+#define SVTGPU_OBMC_MAX_RANGE 16
+typedef struct SvtGpuObmcItem {
+    int32_t ref;                                /* index into refs[] of svtgpu_obmc_search */
+    int32_t x, y;                               /* block origin in the frame (luma samples) */
+    int32_t w, h;                               /* one of the 22 AV1 block sizes */
+    int32_t mvp_col, mvp_row;                   /* mvp_full: the full-pel start MV */
+    int32_t ref_mv_col, ref_mv_row;             /* ref_mv: the centre MV in 1/8 pel */
+    int32_t col_min, col_max, row_min, row_max; /* x->mv_limits (full pel, within [-16384, 16384]) */
+    int32_t sad_per_bit;                        /* sadpb */
+    int32_t search_range;                       /* obmc_ctrls.fpel_search_range, <= SVTGPU_OBMC_MAX_RANGE */
+    int32_t search_diag;                        /* obmc_ctrls.fpel_search_diag */
+    int32_t cost_mode;                          /* 0: approx_inter_rate, 1: the cost tables */
+    int32_t wm_offset, cost_offset;             /* into the pools, in int32 entries */
+} SvtGpuObmcItem;
+typedef struct SvtGpuObmcResult {
+    int32_t  mv_col, mv_row; /* dst_mv (full pel) */
+    uint32_t best_sad;       /* obmc_refining_search_sad's return: SAD + cost at dst_mv */
+    uint32_t variance, sse;  /* ovf at dst_mv and its *sse */
+    int32_t  steps;          /* moves the walk made */
+} SvtGpuObmcResult;
+typedef struct SvtGpuObmcBatch SvtGpuObmcBatch;
+int  svtgpu_obmc_batch_create(SvtGpuContext *ctx, int32_t width, int32_t height, int32_t nref, int32_t max_items,
+                              SvtGpuObmcBatch **out);
+void svtgpu_obmc_batch_destroy(SvtGpuObmcBatch *b);
+/* checks every item (SVTGPU_ERR_INVALID_ARG on an unknown size, search_range > 16, ref >= nref, an origin outside
+ * the frame, empty or oversized limits, an offset outside its pool: nothing is uploaded and the batch holds no items)
+ * and uploads the list and the pools; synchronous */
+int  svtgpu_obmc_set_items(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems, const int32_t *wm_pool,
+                           int32_t wm_count, const int32_t *cost_pool, int32_t cost_count, void *stream);
+/* items [item_begin, item_end) of the current list against refs[nref] (8-bit frames of the batch's size) */
+int  svtgpu_obmc_search(SvtGpuObmcBatch *b, const SvtGpuFrame *const *refs, int32_t item_begin, int32_t item_end,
+                        void *stream);
+int  svtgpu_obmc_read(SvtGpuObmcBatch *b, SvtGpuObmcResult *out, int32_t item_begin, int32_t item_end,
+                      void *stream); /* host [item_end - item_begin]; synchronous */
 
 /* =========================================================================================
  * Frame-buffer work around the path

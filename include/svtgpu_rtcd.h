@@ -11,6 +11,7 @@
  *         svtgpu_install_filter_rtcd();                   // the in-loop filter path (DLF / CDEF / LR)
  *         svtgpu_install_me_md_rtcd();                    // ME / MD distortion + frame buffers
  *         svtgpu_install_ccso_rtcd();                     // CCSO's block kernels (an encoder that re-enables it)
+ *         svtgpu_install_obmc_rtcd();                     // OBMC sad / variance / sub-pixel variance (osdf / ovf / osvf)
  *     }
  *     ...
  *     init_fn_ptr();                                      // EbEncHandle.c:1546: av1me.c:31 COPIES the sad / variance /
@@ -222,4 +223,38 @@ static inline void svtgpu_install_me_md_rtcd(void) {
     sad_16b_kernel                            = svtgpu_sad_16b_kernel;
     svt_sad_loop_kernel                       = svtgpu_sad_loop_kernel;
 }
+
+/* the OBMC distortion family (aom_dsp_rtcd.h:354-484): obmc sad / variance / sub-pixel variance of the 22 block sizes.
+ * init_fn_ptr copies them into svt_aom_mefn_ptr[].osdf / ovf / osvf (av1me.c:171-196), so the install point is the
+ * same as for svtgpu_install_me_md_rtcd: before init_fn_ptr (tests/test_obmc.py checks both orders).  Kept apart from
+ * that function: an encoder opts into the OBMC shims on their own. */
+#define SVTGPU_OBMC_INSTALL(W, H)                                                          \
+    svt_aom_obmc_sad##W##x##H                = svtgpu_aom_obmc_sad##W##x##H;                \
+    svt_aom_obmc_variance##W##x##H           = svtgpu_aom_obmc_variance##W##x##H;           \
+    svt_aom_obmc_sub_pixel_variance##W##x##H = svtgpu_aom_obmc_sub_pixel_variance##W##x##H;
+static inline void svtgpu_install_obmc_rtcd(void) {
+    SVTGPU_OBMC_INSTALL(4, 4)
+    SVTGPU_OBMC_INSTALL(4, 8)
+    SVTGPU_OBMC_INSTALL(8, 4)
+    SVTGPU_OBMC_INSTALL(8, 8)
+    SVTGPU_OBMC_INSTALL(8, 16)
+    SVTGPU_OBMC_INSTALL(16, 8)
+    SVTGPU_OBMC_INSTALL(16, 16)
+    SVTGPU_OBMC_INSTALL(16, 32)
+    SVTGPU_OBMC_INSTALL(32, 16)
+    SVTGPU_OBMC_INSTALL(32, 32)
+    SVTGPU_OBMC_INSTALL(32, 64)
+    SVTGPU_OBMC_INSTALL(64, 32)
+    SVTGPU_OBMC_INSTALL(64, 64)
+    SVTGPU_OBMC_INSTALL(64, 128)
+    SVTGPU_OBMC_INSTALL(128, 64)
+    SVTGPU_OBMC_INSTALL(128, 128)
+    SVTGPU_OBMC_INSTALL(4, 16)
+    SVTGPU_OBMC_INSTALL(16, 4)
+    SVTGPU_OBMC_INSTALL(8, 32)
+    SVTGPU_OBMC_INSTALL(32, 8)
+    SVTGPU_OBMC_INSTALL(16, 64)
+    SVTGPU_OBMC_INSTALL(64, 16)
+}
+#undef SVTGPU_OBMC_INSTALL
 #endif /* SVTGPU_RTCD_H */

@@ -343,6 +343,17 @@ _SIGS = {
     "svtgpu_me_set_origins": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_me_search": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "svtgpu_me_read": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P]),
+    **{"svtgpu_aom_obmc_sad%dx%d" % s: (ctypes.c_uint, [_P, ctypes.c_int, _P, _P]) for s in MD_SIZES},
+    **{"svtgpu_aom_obmc_variance%dx%d" % s: (ctypes.c_uint, [_P, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_uint)])
+       for s in MD_SIZES},
+    **{"svtgpu_aom_obmc_sub_pixel_variance%dx%d" % s: (ctypes.c_uint, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P,
+                                                                         _P, ctypes.POINTER(ctypes.c_uint)])
+       for s in MD_SIZES},
+    "svtgpu_obmc_batch_create": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, ctypes.POINTER(_P)]),
+    "svtgpu_obmc_batch_destroy": (None, [_P]),
+    "svtgpu_obmc_set_items": (ctypes.c_int, [_P, _P, _I32, _P, _I32, _P, _I32, _P]),
+    "svtgpu_obmc_search": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
+    "svtgpu_obmc_read": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
     "svtgpu_ext_all_sad_calculation_8x8_16x16": (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, ctypes.c_uint32, _P,
                                                         _P, _P, _P, _P, _P, ctypes.c_uint8]),
     "svtgpu_ext_eight_sad_calculation_32x32_64x64": (None, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P]),
@@ -920,6 +931,65 @@ class MeBatch:
     def close(self):
         if self.h:
             lib().svtgpu_me_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObmcItem(ctypes.Structure):
+    """SvtGpuObmcItem: one call of svt_av1_obmc_full_pixel_search."""
+    FIELDS = ["ref", "x", "y", "w", "h", "mvp_col", "mvp_row", "ref_mv_col", "ref_mv_row", "col_min", "col_max",
+              "row_min", "row_max", "sad_per_bit", "search_range", "search_diag", "cost_mode", "wm_offset",
+              "cost_offset"]
+    _fields_ = [(n, ctypes.c_int32) for n in FIELDS]
+
+
+OBMC_RESULT_DTYPE = np.dtype([("mv_col", np.int32), ("mv_row", np.int32), ("best_sad", np.uint32),
+                              ("variance", np.uint32), ("sse", np.uint32), ("steps", np.int32)])
+
+
+class ObmcBatch:
+    """Batched full-pel OBMC refinement (svtgpu_obmc_search): one item = one block's walk from its start MV; per item
+    the final MV, the best SAD + cost, the OBMC variance / sse there and the moves made."""
+
+    def __init__(self, ctx, width, height, nref, max_items):
+        self.ctx, self.width, self.height, self.nref, self.max_items = ctx, width, height, nref, max_items
+        h = _P()
+        check(lib().svtgpu_obmc_batch_create(ctx.h, width, height, nref, max_items, ctypes.byref(h)))
+        self.h = h
+        self.nitems = 0
+
+    def set_items(self, items, wm_pool, cost_pool=None, stream=None):
+        """items: dicts (or ObmcItem) with the SvtGpuObmcItem fields; wm_pool / cost_pool: int32 arrays."""
+        arr = (ObmcItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            arr[i] = it if isinstance(it, ObmcItem) else ObmcItem(**{k: int(it[k]) for k in ObmcItem.FIELDS})
+        wm = np.ascontiguousarray(wm_pool, dtype=np.int32)
+        cp = np.ascontiguousarray(cost_pool if cost_pool is not None else np.zeros(0), dtype=np.int32)
+        self.nitems = 0
+        check(lib().svtgpu_obmc_set_items(self.h, arr, len(items), ptr(wm), wm.size, ptr(cp) if cp.size else None,
+                                          cp.size, stream))
+        self.nitems = len(items)
+
+    def search(self, refs, item_begin=0, item_end=None, stream=None):
+        assert len(refs) == self.nref
+        arr = (_P * self.nref)(*[r.h for r in refs])
+        end = self.nitems if item_end is None else item_end
+        check(lib().svtgpu_obmc_search(self.h, arr, item_begin, end, stream))
+
+    def read(self, item_begin=0, item_end=None, stream=None):
+        end = self.nitems if item_end is None else item_end
+        out = np.zeros(max(end - item_begin, 0), OBMC_RESULT_DTYPE)
+        check(lib().svtgpu_obmc_read(self.h, ptr(out), item_begin, end, stream))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().svtgpu_obmc_batch_destroy(self.h)
             self.h = None
 
     def __del__(self):

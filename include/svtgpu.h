@@ -104,10 +104,10 @@ const char *svtgpu_version(void);
 /* ABI revision of this header: bumped whenever a struct passed across the boundary changes layout or an entry
  * point changes meaning (6: SvtGpuLrProfile::ms_events, svtgpu_comm_create_bounded, the asynchronous LR search
  * svtgpu_lr_search_frame_async; 7: svtgpu_cdef_apply_frame accepts params == NULL, svtgpu_stream_create; 8: the CCSO entry points,
- * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*).
+ * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*; 10: the super-resolution upscale svtgpu_superres_*).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 9
+#define SVTGPU_ABI_VERSION 10
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -974,6 +974,35 @@ int svtgpu_extend_plane(void *data, int32_t bits, int32_t stride, int32_t width,
 /* svt_convert_pic_8bit_to_16bit (EbRestProcess.c:235-272) and the 16 -> 8 copy-back of non-reference pictures
  * (EbRestProcess.c:670-697) on device frames: all three planes, direction from the frames' bit depths */
 int svtgpu_frame_convert(const SvtGpuFrame *src, SvtGpuFrame *dst, void *stream);
+
+/* =========================================================================================
+ * Super-resolution: the normative horizontal upscale between CDEF and loop restoration
+ * (svt_av1_superres_upscale_frame, EbRestProcess.c:405-458; svt_av1_upscale_normative_rows, EbSuperRes.c:214-284)
+ * ========================================================================================= */
+/* calculate_scaled_size_helper (EbSuperRes.c:22-41): the downscaled size of `dim` for a scale denominator.  8 leaves
+ * it unchanged, 9..16 give dim * 8 / denom rounded to nearest and at least min(16, dim), 17 is the 3/4 code of the
+ * reference's resize mode; any other value returns dim.  Host only. */
+int32_t svtgpu_superres_scaled_size(int32_t dim, int32_t denom);
+/* The step and the start phase (14 fractional bits) of an upscale of in_w to out_w samples (plane widths):
+ * av1_get_upscale_convolve_step / get_upscale_convolve_x0 (EbSuperRes.c:43-52).  Host only. */
+int svtgpu_superres_geometry(int32_t in_w, int32_t out_w, int32_t *x_step_qn, int32_t *x0_qn);
+/* One plane, device pointers, asynchronous on `stream` (nullable = the library's default stream) like
+ * svtgpu_convert_plane; bits = 8 or 16, strides and widths in samples.  Output column X < out_w samples source
+ * position x0_qn + X * x_step_qn whatever the picture's tile columns are (the reference carries the phase across
+ * them).  Source indices are clamped to [0, src_plane_width - 1]: src_plane_width is the downscaled picture's coded
+ * plane width (mi_cols * 4 >> sub_x), where the reference starts replicating, and the columns between in_w and it are
+ * read as they lie.  Every column of [0, dst_plane_width) is written: those at and past out_w repeat the row's last
+ * upscaled sample.  in_w <= out_w <= 2 * in_w; 16-bit samples are below 1 << 15 (bit_depth 8..12). */
+int svtgpu_superres_upscale_plane(const void *src, int32_t bits, int32_t src_stride, int32_t src_plane_width,
+                                  int32_t in_w, void *dst, int32_t dst_stride, int32_t dst_plane_width, int32_t out_w,
+                                  int32_t rows, int32_t bit_depth, void *stream);
+/* svt_av1_superres_upscale_frame: the three planes of `src` (crop width frame_width; the coded width is frame_width
+ * rounded up to 8) into `dst` (crop width upscaled_width), chroma widths rounded up, all rows of the frames.
+ * SVTGPU_ERR_INVALID_ARG: src == dst, unequal heights or bit depths, frame_width > src's width, upscaled_width >
+ * dst's width, upscaled_width < frame_width, or 2 * frame_width < upscaled_width (the denominator cannot exceed 16).
+ * Equal widths copy the planes. */
+int svtgpu_superres_upscale_frame(const SvtGpuFrame *src, SvtGpuFrame *dst, int32_t frame_width, int32_t upscaled_width,
+                                  void *stream);
 
 /* =========================================================================================
  * Loop restoration

@@ -339,6 +339,10 @@ _SIGS = {
     "svtgpu_pad_plane": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "svtgpu_extend_plane": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "svtgpu_frame_convert": (ctypes.c_int, [_P, _P, _P]),
+    "svtgpu_superres_scaled_size": (_I32, [_I32, _I32]),
+    "svtgpu_superres_geometry": (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+    "svtgpu_superres_upscale_plane": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "svtgpu_superres_upscale_frame": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
     "svtgpu_me_batch_destroy": (None, [_P]),
     "svtgpu_me_set_origins": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_me_search": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -1306,6 +1310,24 @@ def plane_sse(a, b, plane, stream=None):
     v = _U64()
     check(lib().svtgpu_plane_sse(a.h, b.h, plane, ctypes.byref(v), stream))
     return v.value
+
+
+def superres_scaled_size(dim, denom):
+    """svtgpu_superres_scaled_size: the downscaled size of `dim` for a superres / resize denominator (host only)."""
+    return int(lib().svtgpu_superres_scaled_size(int(dim), int(denom)))
+
+
+def superres_geometry(in_w, out_w):
+    """svtgpu_superres_geometry: (x_step_qn, x0_qn) of an upscale of in_w to out_w samples (host only)."""
+    step, x0 = _I32(0), _I32(0)
+    check(lib().svtgpu_superres_geometry(int(in_w), int(out_w), ctypes.byref(step), ctypes.byref(x0)))
+    return int(step.value), int(x0.value)
+
+
+def superres_upscale(src, dst, frame_width, upscaled_width, stream=None):
+    """svtgpu_superres_upscale_frame: the normative upscale of the three planes of Frame `src` (crop width frame_width)
+    into Frame `dst` (crop width upscaled_width), asynchronous on `stream`."""
+    check(lib().svtgpu_superres_upscale_frame(src.h, dst.h, int(frame_width), int(upscaled_width), stream))
 
 
 def declared_symbols(header=HEADER_PATH):

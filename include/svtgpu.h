@@ -94,6 +94,11 @@ typedef struct SvtGpuConvolveParams {
 #ifndef SVTGPU_BIT_DEPTH_T
 #define SVTGPU_BIT_DEPTH_T int32_t
 #endif
+/* the return type of the resize shims: EbErrorType in a unit compiled against the reference (svtgpu_rtcd.h); the same
+ * 32 bits, 0 = EB_ErrorNone */
+#ifndef SVTGPU_ERROR_T
+#define SVTGPU_ERROR_T uint32_t
+#endif
 
 /* ---------------------------------------------------------------------------------------------
  * Library / device
@@ -104,10 +109,11 @@ const char *svtgpu_version(void);
 /* ABI revision of this header: bumped whenever a struct passed across the boundary changes layout or an entry
  * point changes meaning (6: SvtGpuLrProfile::ms_events, svtgpu_comm_create_bounded, the asynchronous LR search
  * svtgpu_lr_search_frame_async; 7: svtgpu_cdef_apply_frame accepts params == NULL, svtgpu_stream_create; 8: the CCSO entry points,
- * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*; 10: the super-resolution upscale svtgpu_superres_*).
+ * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*; 10: the super-resolution upscale svtgpu_superres_*;
+ * 11: the non-normative frame resizer svtgpu_resize_* and its two RTCD shims).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 10
+#define SVTGPU_ABI_VERSION 11
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1003,6 +1009,57 @@ int svtgpu_superres_upscale_plane(const void *src, int32_t bits, int32_t src_str
  * Equal widths copy the planes. */
 int svtgpu_superres_upscale_frame(const SvtGpuFrame *src, SvtGpuFrame *dst, int32_t frame_width, int32_t upscaled_width,
                                   void *stream);
+
+/* =========================================================================================
+ * The non-normative frame resizer (svt_av1_resize_plane / svt_aom_resize_frame, EbResize.c:148-973): the down-scaler of
+ * the source picture of a superres or resized frame, of scaled_input_pic before the LR search and of reference pictures
+ * at another size, and its up-scaler (the normative table), bit-exact with svt_av1_resize_plane_c /
+ * svt_av1_highbd_resize_plane_c and their _horizontal variants
+ * ========================================================================================= */
+/* The plan of one 1-D resize of in_length to out_length samples (resize_multistep, EbResize.c:353-387): `steps`
+ * factor-of-2 halvings (get_down2_steps; each takes a length n to (n + 1) >> 1, by svt_av1_down2_symeven when n is even
+ * and down2_symodd when it is odd), then, unless the halved length -- in_length halved `steps` times -- already equals
+ * out_length, one svt_av1_interpolate_core of that length: filter_index 0..4 names the table (the 0.5 / 0.625 / 0.75 /
+ * 0.875-band down-scaling tables and the normative up-scaling table, choose_interp_filter), delta and offset are its
+ * position step and start (14 fractional bits): output x reads taps (y >> 14) - 3 + k, k = 0..7, of phase (y >> 8) & 63
+ * at y = offset + 128 + x * delta.  filter_index = -1, delta = offset = 0: no interpolation (equal lengths: a copy).
+ * 1 <= lengths <= 65536 and out_length <= 2 * in_length, else SVTGPU_ERR_INVALID_ARG.  Host only. */
+int svtgpu_resize_plan(int32_t in_length, int32_t out_length, int32_t *steps, int32_t *filter_index, int32_t *delta,
+                       int32_t *offset);
+/* The library's tables, for a test to hold them to the reference's: table filter_index (0..4 as above) as [64 phases]
+ * [8 taps], and the two half filters of the halvings (svt_aom_av1_down2_symeven_half_filter,
+ * av1_down2_symodd_half_filter).  Host only. */
+int svtgpu_resize_filter(int32_t filter_index, int16_t out[64][8]);
+int svtgpu_resize_half_filters(int16_t symeven[4], int16_t symodd[4]);
+/* One plane, device pointers, asynchronous on `stream` (nullable = the library's default stream) like
+ * svtgpu_superres_upscale_plane; bits = 8 or 16, strides in samples.  Every row goes from in_w to out_w, rounded and
+ * clipped, then every column from in_h to out_h; a direction of equal lengths is copied.  Exactly out_w x out_h
+ * samples of dst are written.  SVTGPU_ERR_INVALID_ARG without a launch: a null pointer, overlapping buffers, bits not 8
+ * or 16, a width beyond its stride, a non-positive size, a size above 65536, an up-scale beyond 2x in a direction
+ * (down-scales of any ratio are accepted), bit_depth outside 8..12 or not 8 for 8-bit samples.
+ * Workspace: the intermediate plane and the buffers of multi-step halvings come from one device allocation per stream
+ * that the library keeps and grows (a stream synchronise, a free and an allocation, only when a call needs more than
+ * every call before it on that stream; nothing is allocated otherwise).  Calls on one stream reuse it in stream order,
+ * so any number may be queued back to back; calls on different streams use different workspaces and may overlap; host
+ * threads that enqueue on the same stream take turns inside the call.  The workspace of a stream is kept until the
+ * process ends: destroy a stream only after its last resize has completed. */
+int svtgpu_resize_plane(const void *src, int32_t bits, int32_t src_stride, int32_t in_w, int32_t in_h, void *dst,
+                        int32_t dst_stride, int32_t out_w, int32_t out_h, int32_t bit_depth, void *stream);
+/* svt_aom_resize_frame (EbResize.c:887-973): the three 4:2:0 planes of `src` (crop size src_w x src_h, at most the
+ * frame's size) into `dst` (crop size dst_w x dst_h); chroma sizes are (dim + 1) >> 1 on both sides.  Equal sizes copy
+ * the crop.  The samples of dst outside the crop are left as they are: SvtGpuFrame has no border, so the padding the
+ * reference ends with (svt_aom_generate_padding) stays with the caller, by svtgpu_pad_plane on its own padded buffers.
+ * SVTGPU_ERR_INVALID_ARG before any launch: src == dst, unequal bit depths, a crop size beyond its frame, or a plane
+ * that svtgpu_resize_plane would refuse. */
+int svtgpu_resize_frame(const SvtGpuFrame *src, SvtGpuFrame *dst, int32_t src_w, int32_t src_h, int32_t dst_w,
+                        int32_t dst_h, void *stream);
+/* RTCD-compatible shims of svt_av1_resize_plane / svt_av1_highbd_resize_plane (aom_dsp_rtcd.h:898-901): host pointers,
+ * synchronous, staged through a device buffer of the calling thread.  0 (EB_ErrorNone), or 0x80001005
+ * (EB_ErrorBadParameter) for sizes svtgpu_resize_plane refuses. */
+SVTGPU_ERROR_T svtgpu_av1_resize_plane(const uint8_t *const input, int height, int width, int in_stride, uint8_t *output,
+                                       int height2, int width2, int out_stride);
+SVTGPU_ERROR_T svtgpu_av1_highbd_resize_plane(const uint16_t *const input, int height, int width, int in_stride,
+                                              uint16_t *output, int height2, int width2, int out_stride, int bd);
 
 /* =========================================================================================
  * Loop restoration

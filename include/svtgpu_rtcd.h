@@ -12,6 +12,7 @@
  *         svtgpu_install_me_md_rtcd();                    // ME / MD distortion + frame buffers
  *         svtgpu_install_ccso_rtcd();                     // CCSO's block kernels (an encoder that re-enables it)
  *         svtgpu_install_obmc_rtcd();                     // OBMC sad / variance / sub-pixel variance (osdf / ovf / osvf)
+ *         svtgpu_install_resize_rtcd();                   // svt_av1_resize_plane / svt_av1_highbd_resize_plane
  *     }
  *     ...
  *     init_fn_ptr();                                      // EbEncHandle.c:1546: av1me.c:31 COPIES the sad / variance /
@@ -42,6 +43,9 @@
 #endif
 #ifndef SVTGPU_BIT_DEPTH_T
 #define SVTGPU_BIT_DEPTH_T EbBitDepth
+#endif
+#ifndef SVTGPU_ERROR_T
+#define SVTGPU_ERROR_T EbErrorType
 #endif
 #include "svtgpu.h"
 
@@ -257,4 +261,12 @@ static inline void svtgpu_install_obmc_rtcd(void) {
     SVTGPU_OBMC_INSTALL(64, 16)
 }
 #undef SVTGPU_OBMC_INSTALL
+
+/* the non-normative frame resizer's two plane functions (aom_dsp_rtcd.h:898-901), which svt_aom_resize_frame calls per
+ * plane (EbResize.c:889-935); nothing copies these pointers, so any point after the RTCD setup will do.  An encoder that
+ * keeps its pictures on the device calls svtgpu_resize_frame instead. */
+static inline void svtgpu_install_resize_rtcd(void) {
+    svt_av1_resize_plane        = svtgpu_av1_resize_plane;
+    svt_av1_highbd_resize_plane = svtgpu_av1_highbd_resize_plane;
+}
 #endif /* SVTGPU_RTCD_H */

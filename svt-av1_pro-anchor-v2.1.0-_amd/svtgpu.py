@@ -343,6 +343,15 @@ _SIGS = {
     "svtgpu_superres_geometry": (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "svtgpu_superres_upscale_plane": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "svtgpu_superres_upscale_frame": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
+    "svtgpu_resize_plan": (ctypes.c_int, [_I32, _I32] + [ctypes.POINTER(_I32)] * 4),
+    "svtgpu_resize_filter": (ctypes.c_int, [_I32, _P]),
+    "svtgpu_resize_half_filters": (ctypes.c_int, [_P, _P]),
+    "svtgpu_resize_plane": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _P]),
+    "svtgpu_resize_frame": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
+    "svtgpu_av1_resize_plane": (ctypes.c_uint32, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int]),
+    "svtgpu_av1_highbd_resize_plane": (ctypes.c_uint32, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int,
+                                                         ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "svtgpu_me_batch_destroy": (None, [_P]),
     "svtgpu_me_set_origins": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_me_search": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -1328,6 +1337,37 @@ def superres_upscale(src, dst, frame_width, upscaled_width, stream=None):
     """svtgpu_superres_upscale_frame: the normative upscale of the three planes of Frame `src` (crop width frame_width)
     into Frame `dst` (crop width upscaled_width), asynchronous on `stream`."""
     check(lib().svtgpu_superres_upscale_frame(src.h, dst.h, int(frame_width), int(upscaled_width), stream))
+
+
+def resize_plan(in_length, out_length):
+    """svtgpu_resize_plan: (halving steps, the length that reaches the interpolation, table index or -1, delta, offset)
+    of one 1-D resize of in_length to out_length samples (host only)."""
+    v = [_I32(0) for _ in range(4)]
+    check(lib().svtgpu_resize_plan(int(in_length), int(out_length), *[ctypes.byref(x) for x in v]))
+    n = int(in_length)
+    for _ in range(v[0].value):
+        n = (n + 1) >> 1
+    return int(v[0].value), n, int(v[1].value), int(v[2].value), int(v[3].value)
+
+
+def resize_filter(filter_index):
+    """svtgpu_resize_filter: table 0..4 (0.5 / 0.625 / 0.75 / 0.875-band, normative) as int16 [64][8] (host only)."""
+    a = np.zeros((64, 8), np.int16)
+    check(lib().svtgpu_resize_filter(int(filter_index), ptr(a)))
+    return a
+
+
+def resize_half_filters():
+    """svtgpu_resize_half_filters: the (symeven, symodd) half filters of the factor-of-2 steps (host only)."""
+    e, o = np.zeros(4, np.int16), np.zeros(4, np.int16)
+    check(lib().svtgpu_resize_half_filters(ptr(e), ptr(o)))
+    return e, o
+
+
+def resize(src, dst, src_w, src_h, dst_w, dst_h, stream=None):
+    """svtgpu_resize_frame: the three planes of Frame `src` (crop size src_w x src_h) resized into Frame `dst` (crop size
+    dst_w x dst_h) as svt_aom_resize_frame does, asynchronous on `stream`."""
+    check(lib().svtgpu_resize_frame(src.h, dst.h, int(src_w), int(src_h), int(dst_w), int(dst_h), stream))
 
 
 def declared_symbols(header=HEADER_PATH):

@@ -16,8 +16,9 @@
 //    8-wide transforms on both sides, 14-tap 16-wide), so the reference's SB-lagged order equals
 //    "all vertical edges, then all horizontal edges" (the AV1 normative order).
 //  * One workgroup per 64x64 tile: the tile plus a 12-sample apron is staged in LDS, the vertical
-//    edges that reach the tile are filtered over the tile's rows and the apron rows, then the
-//    horizontal edges over the tile's columns; the tile is either written out (apply) or compared with
+//    edges that reach the tile are filtered over the tile's rows and the apron rows a horizontal edge of
+//    the tile reads (packed 8-byte LDS accesses along the rows), then the horizontal edges that reach the
+//    tile over its columns; the tile is either written out (apply) or compared with
 //    the source for the SSE of a level trial — recon is never modified by a trial, so the search
 //    needs no backup/restore copies, and a trial reads each sample once.
 #include <algorithm>
@@ -265,24 +266,58 @@ struct DlfTileLds {
     uint32_t s_thr[64];
     uint16_t s_list[(LW / 4) * (TILE / 4 + 3)]; // list_edges (>= the horizontal count, 19 x 16)
     int      s_cnt[8];
+    uint8_t  s_unit[2][TILE / 4]; // per 4-column segment of the tile: first / last 4-row unit the item needs (below)
 };
 
-// The edges of one direction that filter anything (a length and a nonzero level on either side), listed in LDS
-// grouped by filter length (4, 6, 8, 14): a wave then runs lines of one length, where interleaved lengths made every
-// lane pay for every filter variant of its wave.  Order within a group is free (edges of one direction never overlap).
-// Returns the count; list[] holds record indices.  Ends with a barrier.
-__device__ __forceinline__ int list_edges(const uint32_t *rec, int n, const uint8_t *lvl, uint16_t *list, int *s_cnt) {
+// Which lines of the 88 x 88 image an item needs.  The item's result is the tile (LDS rows and columns 12..75) after
+// the vertical-edge pass and then the horizontal-edge pass; nothing else leaves the workgroup.  From the lengths' reach
+// (modified samples per side: 2 for lengths 4 and 6, 3 for 8, 6 for 14; samples read per side: half_taps = 2, 3, 4, 7):
+//  * A horizontal edge at LDS row 8 + 4e (e = 0..18, picture rows y0-4 .. y0+68) modifies tile rows for every length
+//    when 1 <= e <= 17, and at e = 0 (y0-4) or e = 18 (y0+68) only as a 14-tap edge (q side down to y0+1, p side up to
+//    y0+62); the shorter lengths there end at y0-2 / start at y0+66.  Chroma has no 14-tap edge, so both rows are dead
+//    for every U and V item.
+//  * Such an edge reads rows 8+4e-h .. 8+4e+h-1 of its 4 columns, so the vertical pass has to be right, per 4-column
+//    segment c of the tile, on the tile's row units 3..18 and on
+//        unit 2 (rows 8..11)   when the edge at y0 has a length (h <= 4 reads rows 8..15 at most),
+//        unit 1 (rows 4..7)    when the edge at y0 is 14-tap (reads rows 5..18),
+//        unit 0 (rows 0..3)    when the edge at y0-4 is 14-tap (reads rows 1..14),
+//    and mirrored below: unit 19 for an edge at y0+64, 20 for a 14-tap one there (rows 69..82), 21 for a 14-tap edge at
+//    y0+68 (rows 73..86).  s_unit holds that range per segment, from the staged horizontal records' lengths alone (a
+//    superset of what the levels leave active).
+//  * A vertical edge at LDS column 8 + 4e modifies columns 4e+6..4e+9 (lengths 4, 6), 4e+5..4e+10 (8) or 4e+2..4e+13
+//    (14): tile segments e-2..e-1, or e-3..e for a 14-tap edge, clipped to 0..15.  No segment (e = 0 or 18 unless
+//    14-tap): the edge is dead.  Otherwise its 4-row unit is needed when it lies in the union of those segments'
+//    ranges.  Vertical edges never read what another vertical edge modifies, so nothing else depends on a dropped line.
+__device__ __forceinline__ bool need_vert_unit(const uint8_t (*unit)[TILE / 4], int e, int sr, int len) {
+    const int c0 = max(e - (len == 14 ? 3 : 2), 0), c1 = min(len == 14 ? e : e - 1, TILE / 4 - 1);
+    int lo = 255, hi = -1; // an edge with no segment in the tile keeps (255, -1): never needed
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (c0 + k <= c1) lo = min(lo, (int)unit[0][c0 + k]), hi = max(hi, (int)unit[1][c0 + k]);
+    return sr >= lo && sr <= hi;
+}
+
+// The edges of one direction that filter anything (a length and a nonzero level on either side) and that the tile
+// needs (keep(record index, length)), listed in LDS grouped by filter length (4, 6, 8, 14): a wave then runs lines of
+// one length, where interleaved lengths made every lane pay for every filter variant of its wave.  Order within a
+// group is free (edges of one direction never overlap).  Every lane keeps the buckets of its records from the counting
+// pass for the placing pass.  Returns the count; list[] holds record indices.  Ends with a barrier.
+template <int N, typename Keep>
+__device__ __forceinline__ int list_edges(const uint32_t *rec, const uint8_t *lvl, uint16_t *list, int *s_cnt, Keep keep) {
+    constexpr int IT = (N + NTHR - 1) / NTHR;
     const int tid = threadIdx.x, lane = tid & 63;
     auto bucket = [&](int ri) {
         const uint32_t r   = rec[ri];
         const int      len = r & 15;
-        if (!len || (!lvl[(r >> 8) & 127] && !lvl[(r >> 16) & 127])) return -1;
+        if (!len || (!lvl[(r >> 8) & 127] && !lvl[(r >> 16) & 127]) || !keep(ri, len)) return -1;
         return len == 4 ? 0 : len == 6 ? 1 : len == 8 ? 2 : 3;
     };
+    int bk[IT];
     if (tid < 8) s_cnt[tid] = 0; // [0, 4): counts, then cursors; [4, 8): group starts
     __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += NTHR) {
-        const int b = i0 + tid < n ? bucket(i0 + tid) : -1;
+#pragma unroll
+    for (int u = 0; u < IT; u++) {
+        const int b = bk[u] = u * NTHR + tid < N ? bucket(u * NTHR + tid) : -1;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
             const unsigned long long m = __ballot(b == g);
@@ -298,8 +333,9 @@ __device__ __forceinline__ int list_edges(const uint32_t *rec, int n, const uint
         }
     }
     __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += NTHR) {
-        const int b = i0 + tid < n ? bucket(i0 + tid) : -1;
+#pragma unroll
+    for (int u = 0; u < IT; u++) {
+        const int b = bk[u];
 #pragma unroll
         for (int g = 0; g < 4; g++) {
             const unsigned long long m = __ballot(b == g);
@@ -308,7 +344,7 @@ __device__ __forceinline__ int list_edges(const uint32_t *rec, int n, const uint
             int       base   = 0;
             if (lane == leader) base = atomicAdd(&s_cnt[g], (int)__popcll(m));
             base = __shfl(base, leader);
-            if (b == g) list[base + __popcll(m & ((1ull << lane) - 1))] = (uint16_t)(i0 + tid);
+            if (b == g) list[base + __popcll(m & ((1ull << lane) - 1))] = (uint16_t)(u * NTHR + tid);
         }
     }
     __syncthreads();
@@ -399,31 +435,94 @@ __device__ __forceinline__ void dlf_tile_item(KArgs &a, int bi, int nbi, DlfTile
     for (int u = 0; u < IS; u++)
         if (tid + u * NTHR < NS) *(uint2 *)&t[4 * (tid + u * NTHR)] = q[u];
     const int tw = min(TILE, J.ox + J.ow - x0), th = min(TILE, J.oy + J.oh - y0);
+    // trial: the lane's source samples -- 4 columns (tid % 16) of every 16th row, one aligned load each, packed like the
+    // LDS image -- issued here so that they are in flight while the edges are filtered (8 registers)
+    constexpr int ER = TILE * TILE / 4 / NTHR, EC = TILE / 4;
+    uint2         ref4[TRIAL ? ER : 1];
+    if (TRIAL) {
+        const T  *ref = (const T *)J.ref;
+        const int c = 4 * (tid % EC);
+#pragma unroll
+        for (int k = 0; k < ER; k++) {
+            const int r = tid / EC + k * (NTHR / EC);
+            ref4[k] = make_uint2(0u, 0u);
+            if (r >= th || c >= tw) continue;
+            const T *sp = ref + (size_t)(y0 + r) * J.ref_stride + x0 + c;
+            if (c + 4 <= tw) {
+                if constexpr (sizeof(T) == 2) {
+                    ref4[k] = *(const uint2 *)sp;
+                } else {
+                    const uint32_t b = *(const uint32_t *)sp;
+                    ref4[k] = make_uint2((b & 0xFF) | ((b & 0xFF00) << 8), ((b >> 16) & 0xFF) | ((b >> 8) & 0xFF0000));
+                }
+            } else {
+                uint32_t w[2] = {0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (c + j < tw) w[j >> 1] |= (uint32_t)(uint16_t)sp[j] << (16 * (j & 1));
+                ref4[k] = make_uint2(w[0], w[1]);
+            }
+        }
+    }
     {
         __syncthreads();
         wgclk_mark(a.wgclk, 1);
-        // vertical edges x0-4 .. x0+64 over all 88 rows: (listed edge, line) per item
-        const int nve = list_edges(rv, NV, s_lvl[0], s_list, s_cnt);
+        // the row units the vertical pass owes each 4-column segment (derivation at s_unit); list_edges' first barrier
+        // orders these stores before its reads
+        if (tid < TILE / 4) {
+            const int l0 = rh[tid] & 15, l1 = rh[RH_C + tid] & 15;
+            const int l17 = rh[17 * RH_C + tid] & 15, l18 = rh[18 * RH_C + tid] & 15;
+            L.s_unit[0][tid] = (uint8_t)(l0 == 14 ? 0 : l1 == 14 ? 1 : l1 ? 2 : 3);
+            L.s_unit[1][tid] = (uint8_t)(l18 == 14 ? 21 : l17 == 14 ? 20 : l17 ? 19 : 18);
+        }
+        // vertical edges x0-4 .. x0+68 over the rows the tile needs: (listed edge, line) per item
+        const int nve = list_edges<NV>(rv, s_lvl[0], s_list, s_cnt, [&](int ri, int len) {
+            return need_vert_unit(L.s_unit, ri % RV_C, ri / RV_C, len);
+        });
         for (int i = tid; i < ((DLF_EXP & 1) ? 0 : nve * 4); i += NTHR) {
             const int ri = s_list[i >> 2], line = i & 3, e = ri % RV_C, sr = ri / RV_C;
             const uint32_t r = rv[ri];
             const int len = r & 15;
             const int cur = s_lvl[0][(r >> 8) & 127], prv = s_lvl[0][(r >> 16) & 127];
             const uint32_t th = s_thr[cur ? cur : prv];
+            // The line's window x-8 .. x+7 is four 8-byte groups (rows are 176 B and edges sit on multiples of 4
+            // samples, so every group is 8-byte aligned): the two middle ones hold all that lengths 4, 6 and 8 read,
+            // a 14-tap line adds the outer two.  Samples loaded beyond the length's reach are never used by the filter.
             uint16_t *row = &t[(sr * 4 + line) * LW + (APRON - 4 + e * 4)];
-            const int h = half_taps(len);
-            int F[14];
-#pragma unroll
-            for (int k = 0; k < 14; k++) F[k] = (k >= 7 - h && k < 7 + h) ? row[k - 7] : 0;
+            const uint2 m0 = *(const uint2 *)(row - 4), m1 = *(const uint2 *)row;
+            uint2       o0 = make_uint2(0u, 0u), o1 = o0;
+            if (len == 14) o0 = *(const uint2 *)(row - 8), o1 = *(const uint2 *)(row + 4);
+            int F[14] = {(int)(o0.x >> 16), (int)(o0.y & 0xFFFF), (int)(o0.y >> 16), (int)(m0.x & 0xFFFF),
+                         (int)(m0.x >> 16), (int)(m0.y & 0xFFFF), (int)(m0.y >> 16), (int)(m1.x & 0xFFFF),
+                         (int)(m1.x >> 16), (int)(m1.y & 0xFFFF), (int)(m1.y >> 16), (int)(o1.x & 0xFFFF),
+                         (int)(o1.x >> 16), (int)(o1.y & 0xFFFF)};
             filter_line(F, len, th & 0xFF, (th >> 8) & 0xFF, th >> 16, a.bd);
-#pragma unroll
-            for (int k = 0; k < 14; k++)
-                if (k >= 7 - h && k < 7 + h) row[k - 7] = (uint16_t)F[k];
+            // Write-back in whole dwords that no other line of this pass stores or modifies.  Lengths 4 and 6 modify
+            // x-2 .. x+1: two dwords of their own (a neighbouring edge 4 samples away reaches x+2 at the nearest).
+            // Length 14 modifies x-6 .. x+5, six whole dwords; its transforms are >= 16 wide on both sides, so the
+            // nearest edges sit at x-16 / x+16 and stop at x-11 / x+10.  Length 8 modifies x-3 .. x+2 and is stored as
+            // x-4 .. x+3, the partners x-4 and x+3 unchanged: the length is 8 only when the transforms on both sides are
+            // >= 8 wide, so there is no edge at x-4 or x+4, and an edge at x-8 / x+8 borders that 8-wide transform, which
+            // caps its length at 8: it stops at x-6 / x+5.  Nobody else writes x-4, x-5, x+3 or x+4 in this pass.
+            const uint32_t w1 = (uint32_t)F[5] | ((uint32_t)F[6] << 16), w2 = (uint32_t)F[7] | ((uint32_t)F[8] << 16);
+            if (len < 8) {
+                *(uint32_t *)(row - 2) = w1, *(uint32_t *)row = w2;
+            } else {
+                *(uint2 *)(row - 4) = make_uint2((uint32_t)F[3] | ((uint32_t)F[4] << 16), w1);
+                *(uint2 *)row       = make_uint2(w2, (uint32_t)F[9] | ((uint32_t)F[10] << 16));
+                if (len == 14) {
+                    *(uint32_t *)(row - 6) = (uint32_t)F[1] | ((uint32_t)F[2] << 16);
+                    *(uint32_t *)(row + 4) = (uint32_t)F[11] | ((uint32_t)F[12] << 16);
+                }
+            }
         }
         __syncthreads();
         wgclk_mark(a.wgclk, 2);
-        // horizontal edges y0-4 .. y0+64 over the tile's 64 columns: (listed 4-column edge segment, column) per item
-        const int nhe = list_edges(rh, NH, s_lvl[1], s_list, s_cnt);
+        // horizontal edges y0 .. y0+64 over the tile's 64 columns, and the 14-tap ones at y0-4 and y0+68 (shorter ones
+        // there do not reach the tile): (listed 4-column edge segment, column) per item
+        const int nhe = list_edges<NH>(rh, s_lvl[1], s_list, s_cnt, [&](int ri, int len) {
+            return (ri >= RH_C && ri < (RH_R - 1) * RH_C) || len == 14;
+        });
         for (int i = tid; i < ((DLF_EXP & 2) ? 0 : nhe * 4); i += NTHR) {
             const int ri = s_list[i >> 2], e = ri / RH_C, col = 4 * (ri % RH_C) + (i & 3);
             const uint32_t r = rh[ri];
@@ -445,21 +544,17 @@ __device__ __forceinline__ void dlf_tile_item(KArgs &a, int bi, int nbi, DlfTile
         // emit the tile
         if (TRIAL) {
             uint32_t  s = 0; // <= 16 samples per lane
-            const T  *ref = (const T *)J.ref;
-            const int c = tid % TILE;
-            if (c < tw) {
-                int rv16[TILE / (NTHR / TILE)]; // the lane's source samples, all loads in flight together
+            const int c = 4 * (tid % EC);
 #pragma unroll
-                for (int k = 0; k < TILE / (NTHR / TILE); k++) {
-                    const int r = tid / TILE + k * (NTHR / TILE);
-                    rv16[k] = r < th ? (int)ref[(size_t)(y0 + r) * J.ref_stride + x0 + c] : 0;
-                }
+            for (int k = 0; k < ER; k++) {
+                const int r = tid / EC + k * (NTHR / EC);
+                if (r >= th) continue;
+                const uint2 w = *(const uint2 *)&t[(APRON + r) * LW + APRON + c];
+                const int   d[4] = {(int)(w.x & 0xFFFF) - (int)(ref4[k].x & 0xFFFF), (int)(w.x >> 16) - (int)(ref4[k].x >> 16),
+                                    (int)(w.y & 0xFFFF) - (int)(ref4[k].y & 0xFFFF), (int)(w.y >> 16) - (int)(ref4[k].y >> 16)};
 #pragma unroll
-                for (int k = 0; k < TILE / (NTHR / TILE); k++) {
-                    const int r = tid / TILE + k * (NTHR / TILE);
-                    const int d = r < th ? (int)t[(APRON + r) * LW + APRON + c] - rv16[k] : 0;
-                    s += (uint32_t)(d * d);
-                }
+                for (int j = 0; j < 4; j++)
+                    if (c + j < tw) s += (uint32_t)(d[j] * d[j]);
             }
             const unsigned long long sw = wave_sum_u32_wide(s);
             if ((tid & 63) == 63) red[tid >> 6] = sw;

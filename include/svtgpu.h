@@ -110,10 +110,11 @@ const char *svtgpu_version(void);
  * point changes meaning (6: SvtGpuLrProfile::ms_events, svtgpu_comm_create_bounded, the asynchronous LR search
  * svtgpu_lr_search_frame_async; 7: svtgpu_cdef_apply_frame accepts params == NULL, svtgpu_stream_create; 8: the CCSO entry points,
  * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*; 10: the super-resolution upscale svtgpu_superres_*;
- * 11: the non-normative frame resizer svtgpu_resize_* and its two RTCD shims).
+ * 11: the non-normative frame resizer svtgpu_resize_* and its two RTCD shims; 12: the temporal filter's filter half
+ * svtgpu_tf_*, SvtGpuTfBlock / SvtGpuTfParams / SvtGpuTfPlanes, and its nine RTCD shims).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 11
+#define SVTGPU_ABI_VERSION 12
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1060,6 +1061,118 @@ SVTGPU_ERROR_T svtgpu_av1_resize_plane(const uint8_t *const input, int height, i
                                        int height2, int width2, int out_stride);
 SVTGPU_ERROR_T svtgpu_av1_highbd_resize_plane(const uint16_t *const input, int height, int width, int in_stride,
                                               uint16_t *output, int height2, int width2, int out_stride, int bd);
+
+/* =========================================================================================
+ * The temporal filter's filter half (EbTemporalFiltering.c): the noise estimate (svt_estimate_noise_fp16_c /
+ * svt_estimate_noise_highbd_fp16_c, :3672-3740) and the block loop of produce_temporally_filtered_pic (:2939-3301) from
+ * apply_filtering_central to get_final_filtered_pixels, bit-exact with the reference's C.  The motion half -- motion
+ * estimation, the sub-pel searches and the inter prediction -- stays on the host; what it leaves behind is this section's
+ * input: the predictor planes of every reference picture and, per (reference, 64x64 block), one SvtGpuTfBlock.
+ * ========================================================================================= */
+/* What the search left in MeContext for one 64x64 block of one reference (tf_32x32_block_split_flag, tf_32x32_mv_x / _y,
+ * tf_16x16_mv_x / _y, tf_32x32_block_error, tf_16x16_block_error); 256 bytes.  Index 4 * idx_32x32 + q is 16x16 quadrant
+ * q of 32x32 block idx_32x32 (raster order both). */
+typedef struct SvtGpuTfBlock {
+    int32_t  split32[4];
+    int16_t  mv32_x[4], mv32_y[4];
+    int16_t  mv16_x[16], mv16_y[16];
+    uint64_t err32[4];
+    uint64_t err16[16];
+} SvtGpuTfBlock;
+/* tf_decay_factor_fp16[3], tf_mv_dist_th, tf_chroma of MeContext, the encoder bit depth (8 or 10: 8-bit or 16-bit
+ * samples) and tf_ctrls.use_zz_based_filter */
+typedef struct SvtGpuTfParams {
+    uint32_t decay_factor_fp16[3];
+    int32_t  mv_dist_th;
+    int32_t  tf_chroma;
+    int32_t  bit_depth;
+    int32_t  use_zz_based_filter;
+} SvtGpuTfParams;
+/* The three 4:2:0 planes of a picture as device pointers to the sample at (0, 0), strides in samples.  Every plane is
+ * readable (the output: writable) over the 64-aligned area 64 * ceil(w / 64) x 64 * ceil(h / 64), chroma halved: the
+ * reference filters whole 64x64 blocks, and a quadrant's window error at the right or bottom edge covers the picture's
+ * padding, which the caller supplies as the reference's padded pictures do.  Pointers are 16-byte aligned and strides a
+ * multiple of 16 bytes. */
+typedef struct SvtGpuTfPlanes {
+    void   *plane[3];
+    int32_t stride[3];
+} SvtGpuTfPlanes;
+typedef struct SvtGpuTfState SvtGpuTfState;
+/* The state of one picture size (width and height multiples of 8): the device copy of the metadata and the result slot
+ * of the asynchronous noise estimate.  One state serves one picture at a time. */
+int  svtgpu_tf_state_create(SvtGpuContext *ctx, int32_t width, int32_t height, SvtGpuTfState **out);
+void svtgpu_tf_state_destroy(SvtGpuTfState *state);
+/* The noise estimate of a w x h plane (device pointer; bits = 8: uint8_t samples, 10: uint16_t samples of 10 bits; any
+ * w, h >= 1): the Sobel gate ga < 50 and |Laplacian| sum over the interior, (sum * 82137) / (6 * num), or -65536 when
+ * fewer than 16 samples pass.  Synchronous: *out_fp16 is valid on return. */
+int svtgpu_tf_estimate_noise(SvtGpuContext *ctx, const void *plane, int32_t bits, int32_t stride, int32_t w, int32_t h,
+                             void *stream, int32_t *out_fp16);
+/* The same in stream order with no host wait: the division happens on the device and the value lands in the state;
+ * svtgpu_tf_read_noise copies it out (and waits for `stream`). */
+int svtgpu_tf_estimate_noise_async(SvtGpuTfState *state, const void *plane, int32_t bits, int32_t stride, int32_t w,
+                                   int32_t h, void *stream);
+int svtgpu_tf_read_noise(SvtGpuTfState *state, void *stream, int32_t *out_fp16);
+/* One picture: `centre` filtered with n_refs predictor pictures `refs[n_refs]` into `out` (out may be centre: every
+ * workgroup reads its block before it writes it).  blocks[r * nblk + b] is reference r, block b in raster order, nblk =
+ * ceil(w / 64) * ceil(h / 64); host memory, copied before the call returns.  The caller leaves out the references that
+ * the reference's outlier and brightness tests skip (:3008-3032) and the centre itself.  Whole 64x64 blocks are written.
+ * With tf_chroma == 0 the chroma planes of out are the centre's.  Runs in stream order with no host wait (the call waits
+ * only for the previous call's metadata upload on this state).  SVTGPU_ERR_UNSUPPORTED: n_refs > 26 (the reference's
+ * 16-bit count holds 27 contributions of at most 1000).  SVTGPU_ERR_INVALID_ARG before any launch: a null pointer,
+ * n_refs < 0, a bit depth other than 8 or 10, a plane that is misaligned or narrower than the aligned width. */
+int svtgpu_tf_filter_frame(SvtGpuTfState *state, const SvtGpuTfPlanes *centre, const SvtGpuTfPlanes *refs, int32_t n_refs,
+                           const SvtGpuTfBlock *blocks, const SvtGpuTfParams *params, const SvtGpuTfPlanes *out,
+                           void *stream);
+/* Host-only bookkeeping.  svt_aom_noise_log1p_fp16 (:656-675); and tf_decay_factor_fp16 of one plane from its
+ * decay_control, the log1p of its noise level and q (:2913-2937: q_decay_fp8 = q * q >> 5 from q = 128 up, else
+ * max(q << 2, 1); n_decay_fp10 = decay_control * (0.7 + noise_log1p) / 64).  The caller derives q and decay_control. */
+int32_t  svtgpu_tf_noise_log1p_fp16(int32_t noise_level_fp16);
+uint32_t svtgpu_tf_decay_factor_fp16(int32_t decay_control, int32_t noise_log1p_fp16, int32_t q);
+/* The library's log1p_tab_fp16, sqrt_array_fp16 [16] and expf_tab_fp16, for a test to hold them to the reference's. */
+int svtgpu_tf_tables(const int32_t **log1p_fp16, int32_t *n_log1p, const uint32_t **sqrt_fp16, const int32_t **expf_fp16,
+                     int32_t *n_expf);
+/* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  The two noise
+ * functions carry the reference's prototypes (aom_dsp_rtcd.h:874-877).  The other seven pointers take struct MeContext *
+ * (and EbPictureBufferDesc *), whose layouts this library does not know: svtgpu_rtcd.h's adapters, compiled inside the
+ * encoder, read the fields and call these (idx_32x32 = tf_block_col + 2 * tf_block_row; params' bit_depth and
+ * use_zz_based_filter are not read: the entry names both).  accum / count are indexed with the predictor's stride, as
+ * in the reference. */
+int32_t svtgpu_estimate_noise_fp16(const uint8_t *src, uint16_t width, uint16_t height, uint16_t stride_y);
+int32_t svtgpu_estimate_noise_highbd_fp16(const uint16_t *src, int width, int height, int stride, int bd);
+void svtgpu_tf_apply_planewise_medium(const SvtGpuTfBlock *blk, int32_t idx_32x32, const SvtGpuTfParams *prm,
+                                      const uint8_t *y_src, int y_src_stride, const uint8_t *y_pre, int y_pre_stride,
+                                      const uint8_t *u_src, const uint8_t *v_src, int uv_src_stride, const uint8_t *u_pre,
+                                      const uint8_t *v_pre, int uv_pre_stride, unsigned int block_width,
+                                      unsigned int block_height, int ss_x, int ss_y, uint32_t *y_accum, uint16_t *y_count,
+                                      uint32_t *u_accum, uint16_t *u_count, uint32_t *v_accum, uint16_t *v_count);
+void svtgpu_tf_apply_planewise_medium_hbd(const SvtGpuTfBlock *blk, int32_t idx_32x32, const SvtGpuTfParams *prm,
+                                          const uint16_t *y_src, int y_src_stride, const uint16_t *y_pre, int y_pre_stride,
+                                          const uint16_t *u_src, const uint16_t *v_src, int uv_src_stride,
+                                          const uint16_t *u_pre, const uint16_t *v_pre, int uv_pre_stride,
+                                          unsigned int block_width, unsigned int block_height, int ss_x, int ss_y,
+                                          uint32_t *y_accum, uint16_t *y_count, uint32_t *u_accum, uint16_t *u_count,
+                                          uint32_t *v_accum, uint16_t *v_count, uint32_t encoder_bit_depth);
+void svtgpu_tf_apply_zz_planewise_medium(const SvtGpuTfBlock *blk, int32_t idx_32x32, const SvtGpuTfParams *prm,
+                                         const uint8_t *y_pre, int y_pre_stride, const uint8_t *u_pre, const uint8_t *v_pre,
+                                         int uv_pre_stride, unsigned int block_width, unsigned int block_height, int ss_x,
+                                         int ss_y, uint32_t *y_accum, uint16_t *y_count, uint32_t *u_accum,
+                                         uint16_t *u_count, uint32_t *v_accum, uint16_t *v_count);
+void svtgpu_tf_apply_zz_planewise_medium_hbd(const SvtGpuTfBlock *blk, int32_t idx_32x32, const SvtGpuTfParams *prm,
+                                             const uint16_t *y_pre, int y_pre_stride, const uint16_t *u_pre,
+                                             const uint16_t *v_pre, int uv_pre_stride, unsigned int block_width,
+                                             unsigned int block_height, int ss_x, int ss_y, uint32_t *y_accum,
+                                             uint16_t *y_count, uint32_t *u_accum, uint16_t *u_count, uint32_t *v_accum,
+                                             uint16_t *v_count, uint32_t encoder_bit_depth);
+void svtgpu_tf_apply_filtering_central(int32_t tf_chroma, int32_t src_stride_y, uint8_t **src, uint32_t **accum,
+                                       uint16_t **count, uint16_t blk_width, uint16_t blk_height, uint32_t ss_x,
+                                       uint32_t ss_y);
+void svtgpu_tf_apply_filtering_central_highbd(int32_t tf_chroma, int32_t src_stride_y, uint16_t **src_16bit,
+                                              uint32_t **accum, uint16_t **count, uint16_t blk_width, uint16_t blk_height,
+                                              uint32_t ss_x, uint32_t ss_y);
+void svtgpu_tf_get_final_filtered_pixels(int32_t tf_chroma, uint8_t **src_center_ptr_start,
+                                         uint16_t **altref_buffer_highbd_start, uint32_t **accum, uint16_t **count,
+                                         const uint32_t *stride, int blk_y_src_offset, int blk_ch_src_offset,
+                                         uint16_t blk_width_ch, uint16_t blk_height_ch, int is_highbd);
 
 /* =========================================================================================
  * Loop restoration

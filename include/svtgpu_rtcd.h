@@ -13,6 +13,8 @@
  *         svtgpu_install_ccso_rtcd();                     // CCSO's block kernels (an encoder that re-enables it)
  *         svtgpu_install_obmc_rtcd();                     // OBMC sad / variance / sub-pixel variance (osdf / ovf / osvf)
  *         svtgpu_install_resize_rtcd();                   // svt_av1_resize_plane / svt_av1_highbd_resize_plane
+ *         svtgpu_install_tf_rtcd();                       // the temporal filter's nine pointers (define
+ *                                                         //   SVTGPU_RTCD_WITH_TF before including this header)
  *     }
  *     ...
  *     init_fn_ptr();                                      // EbEncHandle.c:1546: av1me.c:31 COPIES the sad / variance /
@@ -269,4 +271,131 @@ static inline void svtgpu_install_resize_rtcd(void) {
     svt_av1_resize_plane        = svtgpu_av1_resize_plane;
     svt_av1_highbd_resize_plane = svtgpu_av1_highbd_resize_plane;
 }
+
+/* The temporal filter's filter half (aom_dsp_rtcd.h:795-835, 874-877): nine pointers.  The two noise estimates are plain C
+ * and the library exports them.  The other seven take struct MeContext * (and EbPictureBufferDesc *), whose layouts the
+ * library does not know, so the adapters below -- compiled here, inside the encoder, where those types are complete --
+ * read the fields (tf_block_row / tf_block_col, the split flags, motion vectors and block errors, tf_decay_factor_fp16,
+ * tf_mv_dist_th, tf_chroma; stride_y of the picture) and call the library's plain-C shims.  Opt-in: define
+ * SVTGPU_RTCD_WITH_TF before including this header, in a unit that has included EbMotionEstimationContext.h and
+ * EbPictureBufferDesc.h.  Nothing copies these pointers, so any point after the RTCD setup will do.  An encoder that keeps
+ * its pictures on the device calls svtgpu_tf_filter_frame instead. */
+#ifdef SVTGPU_RTCD_WITH_TF
+static void svtgpu_tf_read_me_context(const struct MeContext *c, SvtGpuTfBlock *b, SvtGpuTfParams *p) {
+    for (int i = 0; i < 4; i++) {
+        b->split32[i] = c->tf_32x32_block_split_flag[i];
+        b->mv32_x[i] = c->tf_32x32_mv_x[i], b->mv32_y[i] = c->tf_32x32_mv_y[i];
+        b->err32[i] = c->tf_32x32_block_error[i];
+    }
+    for (int i = 0; i < 16; i++) {
+        b->mv16_x[i] = c->tf_16x16_mv_x[i], b->mv16_y[i] = c->tf_16x16_mv_y[i];
+        b->err16[i] = c->tf_16x16_block_error[i];
+    }
+    for (int i = 0; i < 3; i++) p->decay_factor_fp16[i] = c->tf_decay_factor_fp16[i];
+    p->mv_dist_th = c->tf_mv_dist_th, p->tf_chroma = c->tf_chroma;
+    p->bit_depth = 0, p->use_zz_based_filter = 0; /* named by the entry that is called */
+}
+static void svtgpu_adapt_tf_planewise_medium(struct MeContext *me_ctx, const uint8_t *y_src, int y_src_stride,
+                                             const uint8_t *y_pre, int y_pre_stride, const uint8_t *u_src,
+                                             const uint8_t *v_src, int uv_src_stride, const uint8_t *u_pre,
+                                             const uint8_t *v_pre, int uv_pre_stride, unsigned int block_width,
+                                             unsigned int block_height, int ss_x, int ss_y, uint32_t *y_accum,
+                                             uint16_t *y_count, uint32_t *u_accum, uint16_t *u_count, uint32_t *v_accum,
+                                             uint16_t *v_count) {
+    SvtGpuTfBlock  b;
+    SvtGpuTfParams p;
+    svtgpu_tf_read_me_context(me_ctx, &b, &p);
+    svtgpu_tf_apply_planewise_medium(&b, me_ctx->tf_block_col + me_ctx->tf_block_row * 2, &p, y_src, y_src_stride, y_pre,
+                                     y_pre_stride, u_src, v_src, uv_src_stride, u_pre, v_pre, uv_pre_stride, block_width,
+                                     block_height, ss_x, ss_y, y_accum, y_count, u_accum, u_count, v_accum, v_count);
+}
+static void svtgpu_adapt_tf_planewise_medium_hbd(struct MeContext *me_ctx, const uint16_t *y_src, int y_src_stride,
+                                                 const uint16_t *y_pre, int y_pre_stride, const uint16_t *u_src,
+                                                 const uint16_t *v_src, int uv_src_stride, const uint16_t *u_pre,
+                                                 const uint16_t *v_pre, int uv_pre_stride, unsigned int block_width,
+                                                 unsigned int block_height, int ss_x, int ss_y, uint32_t *y_accum,
+                                                 uint16_t *y_count, uint32_t *u_accum, uint16_t *u_count,
+                                                 uint32_t *v_accum, uint16_t *v_count, uint32_t encoder_bit_depth) {
+    SvtGpuTfBlock  b;
+    SvtGpuTfParams p;
+    svtgpu_tf_read_me_context(me_ctx, &b, &p);
+    svtgpu_tf_apply_planewise_medium_hbd(&b, me_ctx->tf_block_col + me_ctx->tf_block_row * 2, &p, y_src, y_src_stride,
+                                         y_pre, y_pre_stride, u_src, v_src, uv_src_stride, u_pre, v_pre, uv_pre_stride,
+                                         block_width, block_height, ss_x, ss_y, y_accum, y_count, u_accum, u_count, v_accum,
+                                         v_count, encoder_bit_depth);
+}
+static void svtgpu_adapt_tf_zz_planewise_medium(struct MeContext *me_ctx, const uint8_t *y_pre, int y_pre_stride,
+                                                const uint8_t *u_pre, const uint8_t *v_pre, int uv_pre_stride,
+                                                unsigned int block_width, unsigned int block_height, int ss_x, int ss_y,
+                                                uint32_t *y_accum, uint16_t *y_count, uint32_t *u_accum, uint16_t *u_count,
+                                                uint32_t *v_accum, uint16_t *v_count) {
+    SvtGpuTfBlock  b;
+    SvtGpuTfParams p;
+    svtgpu_tf_read_me_context(me_ctx, &b, &p);
+    svtgpu_tf_apply_zz_planewise_medium(&b, me_ctx->tf_block_col + me_ctx->tf_block_row * 2, &p, y_pre, y_pre_stride, u_pre,
+                                        v_pre, uv_pre_stride, block_width, block_height, ss_x, ss_y, y_accum, y_count,
+                                        u_accum, u_count, v_accum, v_count);
+}
+static void svtgpu_adapt_tf_zz_planewise_medium_hbd(struct MeContext *me_ctx, const uint16_t *y_pre, int y_pre_stride,
+                                                    const uint16_t *u_pre, const uint16_t *v_pre, int uv_pre_stride,
+                                                    unsigned int block_width, unsigned int block_height, int ss_x,
+                                                    int ss_y, uint32_t *y_accum, uint16_t *y_count, uint32_t *u_accum,
+                                                    uint16_t *u_count, uint32_t *v_accum, uint16_t *v_count,
+                                                    uint32_t encoder_bit_depth) {
+    SvtGpuTfBlock  b;
+    SvtGpuTfParams p;
+    svtgpu_tf_read_me_context(me_ctx, &b, &p);
+    svtgpu_tf_apply_zz_planewise_medium_hbd(&b, me_ctx->tf_block_col + me_ctx->tf_block_row * 2, &p, y_pre, y_pre_stride,
+                                            u_pre, v_pre, uv_pre_stride, block_width, block_height, ss_x, ss_y, y_accum,
+                                            y_count, u_accum, u_count, v_accum, v_count, encoder_bit_depth);
+}
+static void svtgpu_adapt_tf_get_final_filtered_pixels(struct MeContext *me_ctx, EbByte *src_center_ptr_start,
+                                                      uint16_t **altref_buffer_highbd_start, uint32_t **accum,
+                                                      uint16_t **count, const uint32_t *stride, int blk_y_src_offset,
+                                                      int blk_ch_src_offset, uint16_t blk_width_ch, uint16_t blk_height_ch,
+                                                      Bool is_highbd) {
+    svtgpu_tf_get_final_filtered_pixels(me_ctx->tf_chroma, src_center_ptr_start, altref_buffer_highbd_start, accum, count,
+                                        stride, blk_y_src_offset, blk_ch_src_offset, blk_width_ch, blk_height_ch,
+                                        is_highbd ? 1 : 0);
+}
+static void svtgpu_adapt_tf_filtering_central(struct MeContext *me_ctx, EbPictureBufferDesc *input_picture_ptr_central,
+                                              EbByte *src, uint32_t **accum, uint16_t **count, uint16_t blk_width,
+                                              uint16_t blk_height, uint32_t ss_x, uint32_t ss_y) {
+    svtgpu_tf_apply_filtering_central(me_ctx->tf_chroma, input_picture_ptr_central->stride_y, src, accum, count, blk_width,
+                                      blk_height, ss_x, ss_y);
+}
+static void svtgpu_adapt_tf_filtering_central_highbd(struct MeContext *me_ctx,
+                                                     EbPictureBufferDesc *input_picture_ptr_central, uint16_t **src_16bit,
+                                                     uint32_t **accum, uint16_t **count, uint16_t blk_width,
+                                                     uint16_t blk_height, uint32_t ss_x, uint32_t ss_y) {
+    svtgpu_tf_apply_filtering_central_highbd(me_ctx->tf_chroma, input_picture_ptr_central->stride_y, src_16bit, accum,
+                                             count, blk_width, blk_height, ss_x, ss_y);
+}
+static inline void svtgpu_install_tf_rtcd(void) {
+    svt_av1_apply_temporal_filter_planewise_medium              = svtgpu_adapt_tf_planewise_medium;
+    svt_av1_apply_temporal_filter_planewise_medium_hbd          = svtgpu_adapt_tf_planewise_medium_hbd;
+    svt_av1_apply_zz_based_temporal_filter_planewise_medium     = svtgpu_adapt_tf_zz_planewise_medium;
+    svt_av1_apply_zz_based_temporal_filter_planewise_medium_hbd = svtgpu_adapt_tf_zz_planewise_medium_hbd;
+    get_final_filtered_pixels                                   = svtgpu_adapt_tf_get_final_filtered_pixels;
+    apply_filtering_central                                     = svtgpu_adapt_tf_filtering_central;
+    apply_filtering_central_highbd                              = svtgpu_adapt_tf_filtering_central_highbd;
+    svt_estimate_noise_fp16                                     = svtgpu_estimate_noise_fp16;
+    svt_estimate_noise_highbd_fp16                              = svtgpu_estimate_noise_highbd_fp16;
+}
+/* 1 when pointer k (0..8, the order above) is the library's: the adapters are private to the installing unit */
+static inline int svtgpu_tf_rtcd_installed(int k) {
+    switch (k) {
+    case 0: return svt_av1_apply_temporal_filter_planewise_medium == svtgpu_adapt_tf_planewise_medium;
+    case 1: return svt_av1_apply_temporal_filter_planewise_medium_hbd == svtgpu_adapt_tf_planewise_medium_hbd;
+    case 2: return svt_av1_apply_zz_based_temporal_filter_planewise_medium == svtgpu_adapt_tf_zz_planewise_medium;
+    case 3: return svt_av1_apply_zz_based_temporal_filter_planewise_medium_hbd == svtgpu_adapt_tf_zz_planewise_medium_hbd;
+    case 4: return get_final_filtered_pixels == svtgpu_adapt_tf_get_final_filtered_pixels;
+    case 5: return apply_filtering_central == svtgpu_adapt_tf_filtering_central;
+    case 6: return apply_filtering_central_highbd == svtgpu_adapt_tf_filtering_central_highbd;
+    case 7: return svt_estimate_noise_fp16 == svtgpu_estimate_noise_fp16;
+    case 8: return svt_estimate_noise_highbd_fp16 == svtgpu_estimate_noise_highbd_fp16;
+    default: return 0;
+    }
+}
+#endif /* SVTGPU_RTCD_WITH_TF */
 #endif /* SVTGPU_RTCD_H */

@@ -228,6 +228,49 @@ _U64 = ctypes.c_uint64
 _U8P = ctypes.POINTER(ctypes.c_uint8)
 _LPF8 = (None, [_P, _I32, _P, _P, _P])
 _LPF16 = (None, [_P, _I32, _P, _P, _P, _I32])
+class TfBlock(ctypes.Structure):
+    """Mirror of SvtGpuTfBlock: what the temporal filter's search left for one (reference, 64x64 block)."""
+    _fields_ = [("split32", _I32 * 4), ("mv32_x", ctypes.c_int16 * 4), ("mv32_y", ctypes.c_int16 * 4),
+                ("mv16_x", ctypes.c_int16 * 16), ("mv16_y", ctypes.c_int16 * 16), ("err32", ctypes.c_uint64 * 4),
+                ("err16", ctypes.c_uint64 * 16)]
+
+    @classmethod
+    def make(cls, split32, mv32, mv16, err32, err16):
+        """mv32 [4][2], mv16 [16][2] as (x, y)."""
+        b = cls()
+        for i in range(4):
+            b.split32[i], b.mv32_x[i], b.mv32_y[i], b.err32[i] = int(split32[i]), int(mv32[i][0]), int(mv32[i][1]), int(err32[i])
+        for i in range(16):
+            b.mv16_x[i], b.mv16_y[i], b.err16[i] = int(mv16[i][0]), int(mv16[i][1]), int(err16[i])
+        return b
+
+
+class TfParams(ctypes.Structure):
+    """Mirror of SvtGpuTfParams."""
+    _fields_ = [("decay_factor_fp16", ctypes.c_uint32 * 3), ("mv_dist_th", _I32), ("tf_chroma", _I32), ("bit_depth", _I32),
+                ("use_zz_based_filter", _I32)]
+
+    @classmethod
+    def make(cls, decay, mv_dist_th, tf_chroma, bit_depth, zz=0):
+        p = cls()
+        for i in range(3):
+            p.decay_factor_fp16[i] = int(decay[i])
+        p.mv_dist_th, p.tf_chroma, p.bit_depth, p.use_zz_based_filter = int(mv_dist_th), int(tf_chroma), int(bit_depth), int(zz)
+        return p
+
+
+class TfPlanes(ctypes.Structure):
+    """Mirror of SvtGpuTfPlanes: three device pointers and their strides in samples."""
+    _fields_ = [("plane", _P * 3), ("stride", _I32 * 3)]
+
+    @classmethod
+    def make(cls, ptrs, strides):
+        p = cls()
+        for i in range(3):
+            p.plane[i], p.stride[i] = ptrs[i], int(strides[i])
+        return p
+
+
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
     "svtgpu_version": (ctypes.c_char_p, []),
@@ -352,6 +395,36 @@ _SIGS = {
                                                   ctypes.c_int, ctypes.c_int]),
     "svtgpu_av1_highbd_resize_plane": (ctypes.c_uint32, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int,
                                                          ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "svtgpu_tf_state_create": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(_P)]),
+    "svtgpu_tf_state_destroy": (None, [_P]),
+    "svtgpu_tf_estimate_noise": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, ctypes.POINTER(_I32)]),
+    "svtgpu_tf_estimate_noise_async": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
+    "svtgpu_tf_read_noise": (ctypes.c_int, [_P, _P, ctypes.POINTER(_I32)]),
+    "svtgpu_tf_filter_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32,
+                                              ctypes.POINTER(TfBlock), ctypes.POINTER(TfParams), ctypes.POINTER(TfPlanes), _P]),
+    "svtgpu_tf_noise_log1p_fp16": (_I32, [_I32]),
+    "svtgpu_tf_decay_factor_fp16": (ctypes.c_uint32, [_I32, _I32, _I32]),
+    "svtgpu_tf_tables": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I32), ctypes.POINTER(_P), ctypes.POINTER(_P),
+                                        ctypes.POINTER(_I32)]),
+    "svtgpu_estimate_noise_fp16": (_I32, [_P, ctypes.c_uint16, ctypes.c_uint16, ctypes.c_uint16]),
+    "svtgpu_estimate_noise_highbd_fp16": (_I32, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "svtgpu_tf_apply_planewise_medium": (None, [ctypes.POINTER(TfBlock), _I32, ctypes.POINTER(TfParams)] + [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P,
+                                                      ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                      ctypes.c_int] + [_P] * 6),
+    "svtgpu_tf_apply_planewise_medium_hbd": (None, [ctypes.POINTER(TfBlock), _I32, ctypes.POINTER(TfParams)] + [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P,
+                                                          ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                          ctypes.c_int] + [_P] * 6 + [ctypes.c_uint32]),
+    "svtgpu_tf_apply_zz_planewise_medium": (None, [ctypes.POINTER(TfBlock), _I32, ctypes.POINTER(TfParams)] + [_P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_uint,
+                                                         ctypes.c_uint, ctypes.c_int, ctypes.c_int] + [_P] * 6),
+    "svtgpu_tf_apply_zz_planewise_medium_hbd": (None, [ctypes.POINTER(TfBlock), _I32, ctypes.POINTER(TfParams)] + [_P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_uint,
+                                                             ctypes.c_uint, ctypes.c_int, ctypes.c_int] + [_P] * 6 +
+                                                [ctypes.c_uint32]),
+    "svtgpu_tf_apply_filtering_central": (None, [_I32, _I32, _P, _P, _P, ctypes.c_uint16, ctypes.c_uint16, ctypes.c_uint32,
+                                                 ctypes.c_uint32]),
+    "svtgpu_tf_apply_filtering_central_highbd": (None, [_I32, _I32, _P, _P, _P, ctypes.c_uint16, ctypes.c_uint16,
+                                                        ctypes.c_uint32, ctypes.c_uint32]),
+    "svtgpu_tf_get_final_filtered_pixels": (None, [_I32, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_uint16,
+                                                   ctypes.c_uint16, ctypes.c_int]),
     "svtgpu_me_batch_destroy": (None, [_P]),
     "svtgpu_me_set_origins": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_me_search": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -1368,6 +1441,68 @@ def resize(src, dst, src_w, src_h, dst_w, dst_h, stream=None):
     """svtgpu_resize_frame: the three planes of Frame `src` (crop size src_w x src_h) resized into Frame `dst` (crop size
     dst_w x dst_h) as svt_aom_resize_frame does, asynchronous on `stream`."""
     check(lib().svtgpu_resize_frame(src.h, dst.h, int(src_w), int(src_h), int(dst_w), int(dst_h), stream))
+
+
+def tf_tables():
+    """svtgpu_tf_tables: the library's (log1p_tab_fp16, sqrt_array_fp16, expf_tab_fp16) as numpy arrays (host only)."""
+    l, q, e, nl, ne = _P(), _P(), _P(), _I32(0), _I32(0)
+    check(lib().svtgpu_tf_tables(ctypes.byref(l), ctypes.byref(nl), ctypes.byref(q), ctypes.byref(e), ctypes.byref(ne)))
+    return (np.ctypeslib.as_array(ctypes.cast(l, ctypes.POINTER(_I32)), (nl.value,)).copy(),
+            np.ctypeslib.as_array(ctypes.cast(q, ctypes.POINTER(ctypes.c_uint32)), (16,)).copy(),
+            np.ctypeslib.as_array(ctypes.cast(e, ctypes.POINTER(_I32)), (ne.value,)).copy())
+
+
+def tf_noise_log1p_fp16(noise_level_fp16):
+    return int(lib().svtgpu_tf_noise_log1p_fp16(int(noise_level_fp16)))
+
+
+def tf_decay_factor_fp16(decay_control, noise_log1p_fp16, q):
+    return int(lib().svtgpu_tf_decay_factor_fp16(int(decay_control), int(noise_log1p_fp16), int(q)))
+
+
+def tf_estimate_noise(ctx, plane_ptr, bits, stride, w, h, stream=None):
+    """svtgpu_tf_estimate_noise of a device plane (synchronous)."""
+    v = _I32(0)
+    check(lib().svtgpu_tf_estimate_noise(ctx.h, plane_ptr, int(bits), int(stride), int(w), int(h), stream, ctypes.byref(v)))
+    return int(v.value)
+
+
+class TfState:
+    """svtgpu_tf_state_*: the temporal filter's per-picture-size state (metadata on the device, the noise result slot)."""
+
+    def __init__(self, ctx, width, height):
+        h = _P()
+        check(lib().svtgpu_tf_state_create(ctx.h, int(width), int(height), ctypes.byref(h)))
+        self.h, self.ctx, self.width, self.height = h, ctx, int(width), int(height)
+        self.nblk = ((self.width + 63) // 64) * ((self.height + 63) // 64)
+
+    def close(self):
+        if self.h:
+            lib().svtgpu_tf_state_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate_noise_async(self, plane_ptr, bits, stride, w, h, stream=None):
+        check(lib().svtgpu_tf_estimate_noise_async(self.h, plane_ptr, int(bits), int(stride), int(w), int(h), stream))
+
+    def read_noise(self, stream=None):
+        v = _I32(0)
+        check(lib().svtgpu_tf_read_noise(self.h, stream, ctypes.byref(v)))
+        return int(v.value)
+
+    def filter_frame(self, centre, refs, blocks, params, out, stream=None):
+        """centre / out: TfPlanes; refs: a list of TfPlanes; blocks: a list of TfBlock, [reference][block] flattened."""
+        n = len(refs)
+        assert len(blocks) == n * self.nblk, "one TfBlock per (reference, 64x64 block)"
+        ra = (TfPlanes * max(n, 1))(*refs)
+        ba = (TfBlock * max(len(blocks), 1))(*blocks)
+        check(lib().svtgpu_tf_filter_frame(self.h, ctypes.byref(centre), ra if n else None, n, ba if n else None,
+                                           ctypes.byref(params), ctypes.byref(out), stream))
 
 
 def declared_symbols(header=HEADER_PATH):

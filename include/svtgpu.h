@@ -111,10 +111,11 @@ const char *svtgpu_version(void);
  * svtgpu_lr_search_frame_async; 7: svtgpu_cdef_apply_frame accepts params == NULL, svtgpu_stream_create; 8: the CCSO entry points,
  * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*; 10: the super-resolution upscale svtgpu_superres_*;
  * 11: the non-normative frame resizer svtgpu_resize_* and its two RTCD shims; 12: the temporal filter's filter half
- * svtgpu_tf_*, SvtGpuTfBlock / SvtGpuTfParams / SvtGpuTfPlanes, and its nine RTCD shims).
+ * svtgpu_tf_*, SvtGpuTfBlock / SvtGpuTfParams / SvtGpuTfPlanes, and its nine RTCD shims; 13: the eight single-reference
+ * interpolation shims svtgpu_av1_(highbd_)convolve_*_sr, SvtGpuTfMotion and svtgpu_tf_predict_frame).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 12
+#define SVTGPU_ABI_VERSION 13
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1173,6 +1174,80 @@ void svtgpu_tf_get_final_filtered_pixels(int32_t tf_chroma, uint8_t **src_center
                                          uint16_t **altref_buffer_highbd_start, uint32_t **accum, uint16_t **count,
                                          const uint32_t *stride, int blk_y_src_offset, int blk_ch_src_offset,
                                          uint16_t blk_width_ch, uint16_t blk_height_ch, int is_highbd);
+
+/* =========================================================================================
+ * AV1 sub-pel interpolation (single reference) and the temporal filter's motion compensation.  The per-block family
+ * svt_av1_convolve_{2d,x,y,2d_copy}_sr and svt_av1_highbd_convolve_*_sr (EbInterPrediction.c:320-427, :679-786: what the
+ * reference's svt_aom_convolve[][][0] / svt_aom_convolveHbd[][][0] tables hold), and tf_64x64_inter_prediction /
+ * tf_32x32_inter_prediction (EbTemporalFiltering.c:2230-2580) for every (reference, 64x64 block) of a picture in one launch,
+ * bit-exact with the reference's C.  With it the device chain of the temporal filter is: upload the padded reference
+ * pictures, svtgpu_tf_predict_frame, svtgpu_tf_filter_frame; the host supplies the per-block motion records only.  The
+ * search (ME / HME, the tf_*_sub_pel_search walks), the compound (jnt_) and scaled convolves and intrabc stay on the host.
+ * ========================================================================================= */
+/* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
+ * the 8-tap kernel rows already selected for the phase (av1_get_interp_filter_subpel_kernel of the InterpFilterParams);
+ * round_0 / round_1 are the ConvolveParams' (get_conv_params_no_round: 3 / 11, at 12 bits 5 / 9).  The four forms read
+ * what the reference's C reads: 2d both rows, rows -3 .. h + 3 and columns -3 .. w + 4 of src; x filter_x and round_0,
+ * columns -3 .. w + 4; y filter_y, rows -3 .. h + 4; copy neither.  w, h in {2, 4, 8, 16, 32, 64, 128}; bd 8 for the
+ * 8-bit entries, 10 or 12 for the highbd ones.  svtgpu_rtcd.h's adapters carry the reference's prototypes. */
+void svtgpu_av1_convolve_2d_sr(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                               int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                               int32_t round_1);
+void svtgpu_av1_convolve_x_sr(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                              int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                              int32_t round_1);
+void svtgpu_av1_convolve_y_sr(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                              int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                              int32_t round_1);
+void svtgpu_av1_convolve_2d_copy_sr(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                                    int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                                    int32_t round_1);
+void svtgpu_av1_highbd_convolve_2d_sr(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                      int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                      int32_t round_0, int32_t round_1, int32_t bd);
+void svtgpu_av1_highbd_convolve_x_sr(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                     int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                     int32_t round_0, int32_t round_1, int32_t bd);
+void svtgpu_av1_highbd_convolve_y_sr(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                     int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                     int32_t round_0, int32_t round_1, int32_t bd);
+void svtgpu_av1_highbd_convolve_2d_copy_sr(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                           int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                           int32_t round_0, int32_t round_1, int32_t bd);
+/* The library's six filter tables, [6][16][8] int16: sub_pel_filters_8, _8smooth, _8sharp, bilinear_filters,
+ * sub_pel_filters_4, sub_pel_filters_4smooth, for a test to hold them to the reference's. */
+int svtgpu_interp_tables(const int16_t **tables, int32_t *n_tables);
+/* What the temporal filter's search left in MeContext for one (reference, 64x64 block), as far as the compensation reads
+ * it; 368 bytes.  use64: the block took the tf_64x64_inter_prediction path (tf_64x64_mv_x / _y) and nothing else is read.
+ * split32[i]: tf_32x32_block_split_flag; split16[4 * i + j]: tf_16x16_block_split_flag[i][j]; mv32 / mv16 / mv8:
+ * tf_32x32_mv, tf_16x16_mv [4 * i + j], tf_8x8_mv [16 * i + 4 * j + k] (i, j, k raster indices of the 32x32 block in the
+ * 64x64, the 16x16 in the 32x32, the 8x8 in the 16x16).  MVs are in 1/8 luma sample. */
+typedef struct SvtGpuTfMotion {
+    int16_t mv64_x, mv64_y;
+    uint8_t use64, reserved0[3];
+    uint8_t split32[4];
+    uint8_t split16[16];
+    uint8_t reserved1[4];
+    int16_t mv32_x[4], mv32_y[4];
+    int16_t mv16_x[16], mv16_y[16];
+    int16_t mv8_x[64], mv8_y[64];
+} SvtGpuTfMotion;
+/* The motion compensation of one picture: for every reference r and 64x64 block b, the predictor of the block from
+ * refs[r] with motion[r * nblk + b] (host memory, copied before the call returns) into pred[r], in exactly the layout
+ * svtgpu_tf_filter_frame reads: whole 64x64 blocks over the 64-aligned area, pred planes 16-byte aligned with strides a
+ * multiple of 16 bytes.  The 8-tap sharp filter (4-tap for the 4x4 chroma of an 8x8 block), MV clamp and phase as
+ * compute_subpel_params / clamp_mv_to_umv_border_sb with the edges tf_*_inter_prediction builds.  refs[r].plane[p] points
+ * at sample (0, 0) of the padded reference picture; border_x / border_y (luma samples, chroma halved) is the padding that
+ * is readable around the state's width x height on every side, and strides are at least width + 2 * border_x.  Every read
+ * coordinate is clamped into [-border, size + border - 1], so no MV makes the kernel read outside the planes; from a
+ * border of 72 the clamp never acts (a clamped MV reaches 64 + 4 + 3 samples out) and the result is the reference's.
+ * tf_chroma == 0 leaves the chroma predictors untouched: plane[1] / plane[2] of refs and pred are then neither checked nor
+ * read and may be null.  Runs in stream order with no host wait, the state's metadata
+ * buffer reused as by svtgpu_tf_filter_frame.  SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any
+ * launch: a null pointer, n_refs < 0, a bit depth other than 8 or 10, a negative border, a misaligned or too narrow plane. */
+int svtgpu_tf_predict_frame(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                            int32_t border_y, const SvtGpuTfMotion *motion, int32_t bit_depth, int32_t tf_chroma,
+                            const SvtGpuTfPlanes *pred, void *stream);
 
 /* =========================================================================================
  * Loop restoration

@@ -15,6 +15,9 @@
  *         svtgpu_install_resize_rtcd();                   // svt_av1_resize_plane / svt_av1_highbd_resize_plane
  *         svtgpu_install_tf_rtcd();                       // the temporal filter's nine pointers (define
  *                                                         //   SVTGPU_RTCD_WITH_TF before including this header)
+ *         svtgpu_install_interp_rtcd();                   // the eight single-reference convolves (define
+ *                                                         //   SVTGPU_RTCD_WITH_INTERP); must precede
+ *                                                         //   svt_aom_asm_set_convolve_asm_table(), :1533, which copies them
  *     }
  *     ...
  *     init_fn_ptr();                                      // EbEncHandle.c:1546: av1me.c:31 COPIES the sad / variance /
@@ -398,4 +401,67 @@ static inline int svtgpu_tf_rtcd_installed(int k) {
     }
 }
 #endif /* SVTGPU_RTCD_WITH_TF */
+
+/* The single-reference interpolation family (common_dsp_rtcd.h: svt_av1_convolve_{2d,x,y,2d_copy}_sr and the four
+ * svt_av1_highbd_convolve_*_sr): eight pointers.  They take the reference's InterpFilterParams / ConvolveParams, whose
+ * layouts the library does not know, so the adapters below -- compiled here, where those types are complete (convolve.h)
+ * -- pick the kernel row of the phase with av1_get_interp_filter_subpel_kernel, read round_0 / round_1 and call the
+ * library's plain-C shims.  Opt-in: define SVTGPU_RTCD_WITH_INTERP before including this header, in a unit that has
+ * included convolve.h.  Install point: after the RTCD setup (EbEncHandle.c:1531) and BEFORE
+ * svt_aom_asm_set_convolve_asm_table() (:1533) and svt_aom_asm_set_convolve_hbd_asm_table() (:1537): those two functions
+ * COPY the pointers into the svt_aom_convolve[][][] / svt_aom_convolveHbd[][][] tables that svt_inter_predictor and
+ * svt_highbd_inter_predictor call, so an install after them changes nothing the encoder calls. */
+#ifdef SVTGPU_RTCD_WITH_INTERP
+#define SVTGPU_ADAPT_CONVOLVE(name)                                                                                        \
+    static void svtgpu_adapt_convolve_##name(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride,     \
+                                             int32_t w, int32_t h, InterpFilterParams *filter_params_x,                    \
+                                             InterpFilterParams *filter_params_y, const int32_t subpel_x_q4,               \
+                                             const int32_t subpel_y_q4, ConvolveParams *conv_params) {                     \
+        svtgpu_av1_convolve_##name(                                                                                        \
+            src, src_stride, dst, dst_stride, w, h,                                                                        \
+            filter_params_x ? av1_get_interp_filter_subpel_kernel(*filter_params_x, subpel_x_q4 & SUBPEL_MASK) : NULL,     \
+            filter_params_y ? av1_get_interp_filter_subpel_kernel(*filter_params_y, subpel_y_q4 & SUBPEL_MASK) : NULL,     \
+            conv_params->round_0, conv_params->round_1);                                                                   \
+    }                                                                                                                      \
+    static void svtgpu_adapt_highbd_convolve_##name(const uint16_t *src, int32_t src_stride, uint16_t *dst,                \
+                                                    int32_t dst_stride, int32_t w, int32_t h,                              \
+                                                    const InterpFilterParams *filter_params_x,                             \
+                                                    const InterpFilterParams *filter_params_y, const int32_t subpel_x_q4,  \
+                                                    const int32_t subpel_y_q4, ConvolveParams *conv_params, int32_t bd) {  \
+        svtgpu_av1_highbd_convolve_##name(                                                                                 \
+            src, src_stride, dst, dst_stride, w, h,                                                                        \
+            filter_params_x ? av1_get_interp_filter_subpel_kernel(*filter_params_x, subpel_x_q4 & SUBPEL_MASK) : NULL,     \
+            filter_params_y ? av1_get_interp_filter_subpel_kernel(*filter_params_y, subpel_y_q4 & SUBPEL_MASK) : NULL,     \
+            conv_params->round_0, conv_params->round_1, bd);                                                               \
+    }
+SVTGPU_ADAPT_CONVOLVE(2d_sr)
+SVTGPU_ADAPT_CONVOLVE(x_sr)
+SVTGPU_ADAPT_CONVOLVE(y_sr)
+SVTGPU_ADAPT_CONVOLVE(2d_copy_sr)
+#undef SVTGPU_ADAPT_CONVOLVE
+static inline void svtgpu_install_interp_rtcd(void) {
+    svt_av1_convolve_2d_sr             = svtgpu_adapt_convolve_2d_sr;
+    svt_av1_convolve_x_sr              = svtgpu_adapt_convolve_x_sr;
+    svt_av1_convolve_y_sr              = svtgpu_adapt_convolve_y_sr;
+    svt_av1_convolve_2d_copy_sr        = svtgpu_adapt_convolve_2d_copy_sr;
+    svt_av1_highbd_convolve_2d_sr      = svtgpu_adapt_highbd_convolve_2d_sr;
+    svt_av1_highbd_convolve_x_sr       = svtgpu_adapt_highbd_convolve_x_sr;
+    svt_av1_highbd_convolve_y_sr       = svtgpu_adapt_highbd_convolve_y_sr;
+    svt_av1_highbd_convolve_2d_copy_sr = svtgpu_adapt_highbd_convolve_2d_copy_sr;
+}
+/* 1 when pointer k (0..7, the order above) is the library's: the adapters are private to the installing unit */
+static inline int svtgpu_interp_rtcd_installed(int k) {
+    switch (k) {
+    case 0: return svt_av1_convolve_2d_sr == svtgpu_adapt_convolve_2d_sr;
+    case 1: return svt_av1_convolve_x_sr == svtgpu_adapt_convolve_x_sr;
+    case 2: return svt_av1_convolve_y_sr == svtgpu_adapt_convolve_y_sr;
+    case 3: return svt_av1_convolve_2d_copy_sr == svtgpu_adapt_convolve_2d_copy_sr;
+    case 4: return svt_av1_highbd_convolve_2d_sr == svtgpu_adapt_highbd_convolve_2d_sr;
+    case 5: return svt_av1_highbd_convolve_x_sr == svtgpu_adapt_highbd_convolve_x_sr;
+    case 6: return svt_av1_highbd_convolve_y_sr == svtgpu_adapt_highbd_convolve_y_sr;
+    case 7: return svt_av1_highbd_convolve_2d_copy_sr == svtgpu_adapt_highbd_convolve_2d_copy_sr;
+    default: return 0;
+    }
+}
+#endif /* SVTGPU_RTCD_WITH_INTERP */
 #endif /* SVTGPU_RTCD_H */

@@ -197,6 +197,14 @@ static inline hipStream_t pick_stream(SvtGpuContext *ctx, void *stream) {
     return stream ? (hipStream_t)stream : ctx->stream;
 }
 
+// The temporal filter state's geometry and metadata buffer (tf.hip) for svtgpu_tf_predict_frame (interp.hip):
+// _begin grows both copies to `bytes` and waits until the previous upload has left the pinned one; _upload enqueues the
+// copy on `st` and records it.
+void svtgpu_tf_state_geometry(const SvtGpuTfState *s, SvtGpuContext **ctx, int32_t *width, int32_t *height,
+                              int32_t *blk_cols, int32_t *nblk);
+int  svtgpu_tf_meta_begin(SvtGpuTfState *s, size_t bytes, uint8_t **host, uint8_t **dev);
+int  svtgpu_tf_meta_upload(SvtGpuTfState *s, size_t bytes, hipStream_t st);
+
 // Diagnostics (SVTGPU_WGCLK=<file>, never on by default): per workgroup 8 words -- up to 6 time marks on the 100 MHz
 // s_memrealtime clock (slot 0 = start; the kernel's phases after it; unused slots stay 0) and the hardware id words
 // (HW_ID: wave / SIMD / CU / SE; XCC_ID) -- appended to the file by the launching host code (svtgpu_wgclk_*).

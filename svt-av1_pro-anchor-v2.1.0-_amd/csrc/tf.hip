@@ -540,8 +540,8 @@ struct SvtGpuTfState {
     SvtGpuContext *ctx;
     int32_t        width, height, blk_cols, nblk;
     NoiseSlot     *d_noise;
-    uint8_t       *d_meta, *h_meta; // [cap_refs] TfRef, then [cap_refs][nblk] SvtGpuTfBlock; h_meta pinned
-    int32_t        cap_refs;
+    uint8_t       *d_meta, *h_meta; // the filter: [n_refs] TfRef, then [n_refs][nblk] SvtGpuTfBlock; h_meta pinned
+    size_t         cap_meta;        // bytes of each
     hipEvent_t     copied;          // the last upload of h_meta has left it
     hipStream_t    last;            // the stream of the last filter call
 };
@@ -549,20 +549,20 @@ struct SvtGpuTfState {
 namespace {
 size_t meta_bytes(const SvtGpuTfState *s, int refs) { return (size_t)refs * (sizeof(TfRef) + (size_t)s->nblk * sizeof(SvtGpuTfBlock)); }
 
-int meta_reserve(SvtGpuTfState *s, int refs) {
-    if (refs <= s->cap_refs) return SVTGPU_OK;
+int meta_reserve(SvtGpuTfState *s, size_t bytes) {
+    if (bytes <= s->cap_meta) return SVTGPU_OK;
     if (s->d_meta) { // an earlier call may still read it
         HIP_TRY(hipStreamSynchronize(s->last));
         (void)hipFree(s->d_meta), (void)hipHostFree(s->h_meta);
-        s->d_meta = s->h_meta = nullptr, s->cap_refs = 0;
+        s->d_meta = s->h_meta = nullptr, s->cap_meta = 0;
     }
-    if (hipMalloc(&s->d_meta, meta_bytes(s, refs)) != hipSuccess) return SVTGPU_ERR_OOM;
-    if (hipHostMalloc(&s->h_meta, meta_bytes(s, refs)) != hipSuccess) {
+    if (hipMalloc(&s->d_meta, bytes) != hipSuccess) return SVTGPU_ERR_OOM;
+    if (hipHostMalloc(&s->h_meta, bytes) != hipSuccess) {
         (void)hipFree(s->d_meta);
         s->d_meta = nullptr;
         return SVTGPU_ERR_OOM;
     }
-    s->cap_refs = refs;
+    s->cap_meta = bytes;
     return SVTGPU_OK;
 }
 
@@ -575,6 +575,26 @@ bool planes_ok(const SvtGpuTfPlanes *p, int aw, int bs) {
     return true;
 }
 } // namespace
+
+// The state's metadata buffer for svtgpu_tf_predict_frame (interp.hip), under the filter's rule: one pinned host copy,
+// rewritten once the previous upload has left it, and a device copy that the calls of one stream reuse in order.
+void svtgpu_tf_state_geometry(const SvtGpuTfState *s, SvtGpuContext **ctx, int32_t *width, int32_t *height,
+                              int32_t *blk_cols, int32_t *nblk) {
+    *ctx = s->ctx, *width = s->width, *height = s->height, *blk_cols = s->blk_cols, *nblk = s->nblk;
+}
+int svtgpu_tf_meta_begin(SvtGpuTfState *s, size_t bytes, uint8_t **host, uint8_t **dev) {
+    if (int rc = meta_reserve(s, bytes)) return rc;
+    HIP_TRY(hipEventSynchronize(s->copied));
+    *host = s->h_meta, *dev = s->d_meta;
+    return SVTGPU_OK;
+}
+int svtgpu_tf_meta_upload(SvtGpuTfState *s, size_t bytes, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(s->d_meta, s->h_meta, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->copied, st));
+    svtgpu_count_xfer(0, bytes);
+    s->last = st;
+    return SVTGPU_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // host-only entry points
@@ -675,7 +695,7 @@ extern "C" int svtgpu_tf_filter_frame(SvtGpuTfState *s, const SvtGpuTfPlanes *ce
     TfFrameArgs a;
     memset(&a, 0, sizeof a);
     if (n_refs) {
-        if (int rc = meta_reserve(s, n_refs)) return rc;
+        if (int rc = meta_reserve(s, meta_bytes(s, n_refs))) return rc;
         HIP_TRY(hipEventSynchronize(s->copied)); // the previous call's upload has left the pinned buffer
         TfRef *hr = (TfRef *)s->h_meta;
         for (int r = 0; r < n_refs; r++)

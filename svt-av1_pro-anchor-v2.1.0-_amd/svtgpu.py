@@ -271,6 +271,33 @@ class TfPlanes(ctypes.Structure):
         return p
 
 
+class TfMotion(ctypes.Structure):
+    """Mirror of SvtGpuTfMotion: the partition and MVs of one (reference, 64x64 block), 368 bytes."""
+    _fields_ = [("mv64_x", ctypes.c_int16), ("mv64_y", ctypes.c_int16), ("use64", ctypes.c_uint8),
+                ("reserved0", ctypes.c_uint8 * 3), ("split32", ctypes.c_uint8 * 4), ("split16", ctypes.c_uint8 * 16),
+                ("reserved1", ctypes.c_uint8 * 4), ("mv32_x", ctypes.c_int16 * 4), ("mv32_y", ctypes.c_int16 * 4),
+                ("mv16_x", ctypes.c_int16 * 16), ("mv16_y", ctypes.c_int16 * 16), ("mv8_x", ctypes.c_int16 * 64),
+                ("mv8_y", ctypes.c_int16 * 64)]
+
+    @classmethod
+    def make(cls, use64, mv64, split32, split16, mv32, mv16, mv8):
+        """mv64 (x, y); mv32 [4][2], mv16 [16][2], mv8 [64][2] as (x, y)."""
+        m = cls()
+        m.use64, m.mv64_x, m.mv64_y = int(use64), int(mv64[0]), int(mv64[1])
+        for i in range(4):
+            m.split32[i], m.mv32_x[i], m.mv32_y[i] = int(split32[i]), int(mv32[i][0]), int(mv32[i][1])
+        for i in range(16):
+            m.split16[i], m.mv16_x[i], m.mv16_y[i] = int(split16[i]), int(mv16[i][0]), int(mv16[i][1])
+        for i in range(64):
+            m.mv8_x[i], m.mv8_y[i] = int(mv8[i][0]), int(mv8[i][1])
+        return m
+
+
+assert ctypes.sizeof(TfMotion) == 368
+_I16P = ctypes.POINTER(ctypes.c_int16)
+_CONVOLVE_SR = [_P, _I32, _P, _I32, _I32, _I32, _I16P, _I16P, _I32, _I32]
+INTERP_FORMS = ("2d_sr", "x_sr", "y_sr", "2d_copy_sr")
+
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
     "svtgpu_version": (ctypes.c_char_p, []),
@@ -425,6 +452,11 @@ _SIGS = {
                                                         ctypes.c_uint32, ctypes.c_uint32]),
     "svtgpu_tf_get_final_filtered_pixels": (None, [_I32, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_uint16,
                                                    ctypes.c_uint16, ctypes.c_int]),
+    **{"svtgpu_av1_convolve_" + f: (None, _CONVOLVE_SR) for f in INTERP_FORMS},
+    **{"svtgpu_av1_highbd_convolve_" + f: (None, _CONVOLVE_SR + [_I32]) for f in INTERP_FORMS},
+    "svtgpu_interp_tables": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I32)]),
+    "svtgpu_tf_predict_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32, ctypes.POINTER(TfMotion),
+                                               _I32, _I32, ctypes.POINTER(TfPlanes), _P]),
     "svtgpu_me_batch_destroy": (None, [_P]),
     "svtgpu_me_set_origins": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_me_search": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -1503,6 +1535,38 @@ class TfState:
         ba = (TfBlock * max(len(blocks), 1))(*blocks)
         check(lib().svtgpu_tf_filter_frame(self.h, ctypes.byref(centre), ra if n else None, n, ba if n else None,
                                            ctypes.byref(params), ctypes.byref(out), stream))
+
+
+    def predict_frame(self, refs, border_x, border_y, motion, bit_depth, tf_chroma, pred, stream=None):
+        """refs / pred: lists of TfPlanes (refs at sample (0, 0) of the padded pictures); motion: a list of TfMotion,
+        [reference][block] flattened."""
+        n = len(refs)
+        assert len(pred) == n and len(motion) == n * self.nblk, "one TfMotion per (reference, 64x64 block)"
+        ra, pa = (TfPlanes * max(n, 1))(*refs), (TfPlanes * max(n, 1))(*pred)
+        ma = (TfMotion * max(len(motion), 1))(*motion)
+        check(lib().svtgpu_tf_predict_frame(self.h, ra if n else None, n, int(border_x), int(border_y), ma if n else None,
+                                            int(bit_depth), int(tf_chroma), pa if n else None, stream))
+
+
+def interp_tables():
+    """svtgpu_interp_tables: the library's six sub-pel filter tables as an int16 array [6][16][8] (host only)."""
+    t, n = _P(), _I32(0)
+    check(lib().svtgpu_interp_tables(ctypes.byref(t), ctypes.byref(n)))
+    return np.ctypeslib.as_array(ctypes.cast(t, _I16P), (n.value, 16, 8)).copy()
+
+
+def convolve_sr(form, src, x0, y0, w, h, filter_x, filter_y, round_0, round_1, bd, dst, dx0, dy0):
+    """One of the eight interpolation shims (form in INTERP_FORMS): the w x h block at (x0, y0) of the host array `src`
+    (uint8 at bd 8, else uint16) into `dst` at (dx0, dy0), in place."""
+    hbd = src.dtype == np.uint16
+    fn = getattr(lib(), ("svtgpu_av1_highbd_convolve_" if hbd else "svtgpu_av1_convolve_") + form)
+    fx = (ctypes.c_int16 * 8)(*[int(v) for v in filter_x])
+    fy = (ctypes.c_int16 * 8)(*[int(v) for v in filter_y])
+    sp = src.ctypes.data + (y0 * src.strides[0] + x0 * src.itemsize)
+    dp = dst.ctypes.data + (dy0 * dst.strides[0] + dx0 * dst.itemsize)
+    args = [sp, src.strides[0] // src.itemsize, dp, dst.strides[0] // dst.itemsize, int(w), int(h), fx, fy, int(round_0),
+            int(round_1)]
+    fn(*(args + [int(bd)] if hbd else args))
 
 
 def declared_symbols(header=HEADER_PATH):

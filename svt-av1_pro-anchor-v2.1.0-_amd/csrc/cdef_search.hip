@@ -16,8 +16,12 @@
 // S once per secondary strength (3) and P once per primary level (<= 16) — 16x4 + 3x8 tap
 // constraints instead of 64x12 — and each of the 64 strengths costs only the rounding, clamp and
 // distortion statistics.  Everything is packed int16 (two samples per VGPR).
+// The strength loop is VALU-issue bound, so what does not depend on the strength is formed once per lane: a tap
+// keeps |p - x| and sign(p - x) (a constraint is then shift, saturating subtract, min, multiply-add), the sample
+// keeps 16 x + 8 (rounding constant and sample add of the output in one add), and a lane outside the measured set
+// has its sample, range, taps and secondary sums zeroed, so it yields y = 0 with no mask per strength.
 // Lanes own whole rows of 8 samples (4 pairs): a luma 8x8 block is 8 lanes, so its per-strength
-// statistics (sum d, sum d^2, sum (d-s)^2) reduce with 3 DPP steps; the double-precision SSIM-like
+// statistics (sum d, sum d^2, sum d s) reduce with 3 DPP steps; the double-precision SSIM-like
 // distortion (EbEncCdef.c:42-47) runs once per (strength, block) in a lane-parallel epilogue.
 #include "cdef_common.h"
 
@@ -44,9 +48,10 @@ struct SearchArgs {
 };
 
 struct PriPair { // two horizontally adjacent samples, packed int16 (lo half = left sample)
-    s16x2 x, lo, hi;
-    s16x2 d[4]; // p - x of the primary taps: (k0,+), (k0,-), (k1,+), (k1,-) (the magnitude is formed per use: fewer
-                // live registers, so the kernel holds three waves per SIMD)
+    s16x2 xr;     // 16 x + 8: the sample in the tap sum's units plus the rounding constant (see finish)
+    s16x2 lo, hi; // clamp range
+    u16x2 a[4];   // |p - x| of the primary taps: (k0,+), (k0,-), (k1,+), (k1,-)
+    s16x2 sg[4];  // sign(p - x) of the same taps as a multiplier, +-1
 };
 
 // 8 samples from an 8-aligned position of a plane as four packed int16 pairs (one 16-B / 8-B load)
@@ -123,16 +128,13 @@ __device__ __forceinline__ void stage_tile(uint16_t *tile, const void *plane_, i
 __device__ __forceinline__ s16x2 splat16(int v) { return (s16x2){(short)v, (short)v}; }
 __device__ __forceinline__ u16x2 splatu16(int v) { return (u16x2){(unsigned short)v, (unsigned short)v}; }
 
-// constrain(d, thr, damping) = sign(d) * min(|d|, m), m = max(0, thr - (|d| >> shift)) (EbCdef.c:85-91): m >= 0, so it
-// is the clamp of d to [-m, m]
-__device__ __forceinline__ s16x2 constrain2(s16x2 d, s16x2 thr, u16x2 sh) {
-    const s16x2 ad = __builtin_elementwise_max(d, (s16x2){0, 0} - d);
-    const s16x2 m  = __builtin_elementwise_max(thr - (s16x2)(((u16x2)ad) >> sh), (s16x2){0, 0});
-    return __builtin_elementwise_max(__builtin_elementwise_min(d, m), (s16x2){0, 0} - m);
+// constrain(d, thr, damping) = sign(d) * min(|d|, m), m = max(0, thr - (|d| >> shift)) (EbCdef.c:85-91).  thr and
+// |d| >> shift are both non-negative, so m is one saturating unsigned subtract; the sign is applied by the caller's
+// multiply-add with the tap's +-1.
+__device__ __forceinline__ s16x2 constrain_mag(u16x2 ad, u16x2 thr, u16x2 sh) {
+    return (s16x2)__builtin_elementwise_min(ad, __builtin_elementwise_sub_sat(thr, ad >> sh));
 }
 
-// Neighbourhood of the pair at tile (r, c), (r, c+1) for direction `dir`: keeps the primary taps
-// and the clamp range, and returns the secondary sums S[1..3] for the secondary codes in `sec_used`.
 // The pair of samples at 16-bit index a of an LDS tile from two aligned dwords (one ds_read2_b32) and a funnel
 // shift: a dword read at an odd sample index is a misaligned LDS access, which the LDS serves far below its rate.
 __device__ __forceinline__ uint32_t lds_pair_u32(const uint16_t *tile, int a) {
@@ -140,14 +142,21 @@ __device__ __forceinline__ uint32_t lds_pair_u32(const uint16_t *tile, int a) {
     return __builtin_amdgcn_alignbit(w[1], w[0], (a & 1) * 16);
 }
 
+// Neighbourhood of the pair at tile (r, c), (r, c+1) for direction `dir`: keeps the primary taps
+// and the clamp range, and returns the secondary sums S[1..3] for the secondary codes in `sec_used`.
+// `keep` is all ones for a measured pair and 0 otherwise: a pair that is not measured gets x = lo = hi = 0, zero tap
+// magnitudes and zero secondary sums, so every strength gives it clamp(0 + round(0), 0, 0) = 0.
+// All of it is packed: the apron value 0x7F7F plus 0x81 wraps to the int16 minimum, so a running maximum of
+// p + 0x81 skips the apron exactly as `if (p != CDEF_VERY_LARGE) max = ...` does (8- and 10-bit samples are far below 0x7F7F).
 __device__ __forceinline__ void load_pair(PriPair &P, s16x2 S[4], const uint16_t *tile, int ts, int r, int c,
-                                          int dir, int sec_used, int sdamp, int cs) {
-    const int       a0 = (r + CDEF_BORDER) * ts + (c + CDEF_BORDER); // even: ts and c are
-    const uint32_t  xw = *(const uint32_t *)(tile + a0);
-    const int       xa = (int16_t)(xw & 0xFFFF), xb = (int16_t)(xw >> 16);
-    int             loa = xa, hia = xa, lob = xb, hib = xb;
-    const int       ds0 = (dir + 2) & 7, ds1 = (dir + 6) & 7;
-    s16x2           sd[8];
+                                          int dir, int sec_used, int sdamp, int cs, s16x2 keep) {
+    const int   a0 = (r + CDEF_BORDER) * ts + (c + CDEF_BORDER); // even: ts and c are
+    const s16x2 x  = __builtin_bit_cast(s16x2, *(const uint32_t *)(tile + a0));
+    const u16x2 hb = splatu16(0x8000 - CDEF_VERY_LARGE_V);
+    s16x2       lo = x, hi = (s16x2)((u16x2)x + hb);
+    const int   ds0 = (dir + 2) & 7, ds1 = (dir + 6) & 7;
+    u16x2       sa[8];
+    s16x2       ssg[8];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const int op = cdef_dir_dy(dir, k) * ts + cdef_dir_dx(dir, k);
@@ -156,51 +165,54 @@ __device__ __forceinline__ void load_pair(PriPair &P, s16x2 S[4], const uint16_t
         const int o[6] = {op, -op, o0, -o0, o1, -o1};
 #pragma unroll
         for (int t = 0; t < 6; t++) {
-            const uint32_t vw = lds_pair_u32(tile, a0 + o[t]);
-            const int      va = (int16_t)(vw & 0xFFFF), vb = (int16_t)(vw >> 16);
-            if (va != CDEF_VERY_LARGE_V) hia = max(hia, va);
-            if (vb != CDEF_VERY_LARGE_V) hib = max(hib, vb);
-            loa = min(loa, va);
-            lob = min(lob, vb);
-            const s16x2 dd = {(short)(va - xa), (short)(vb - xb)};
+            const s16x2 v = __builtin_bit_cast(s16x2, lds_pair_u32(tile, a0 + o[t]));
+            lo            = __builtin_elementwise_min(lo, v);
+            hi            = __builtin_elementwise_max(hi, (s16x2)((u16x2)v + hb));
+            const s16x2 d  = v - x;
+            const u16x2 ad = (u16x2)__builtin_elementwise_max(d, (s16x2){0, 0} - d);
+            const s16x2 sg = (d >> (s16x2){15, 15}) | (s16x2){1, 1};
             if (t < 2)
-                P.d[2 * k + t] = dd;
+                P.a[2 * k + t] = ad & (u16x2)keep, P.sg[2 * k + t] = sg;
             else
-                sd[4 * k + t - 2] = dd;
+                sa[4 * k + t - 2] = ad, ssg[4 * k + t - 2] = sg;
         }
     }
-    P.x  = (s16x2){(short)xa, (short)xb};
-    P.lo = (s16x2){(short)loa, (short)lob};
-    P.hi = (s16x2){(short)hia, (short)hib};
+    const s16x2 xk = x & keep;
+    P.xr = (xk << (s16x2){4, 4}) + (s16x2){8, 8};
+    P.lo = lo & keep;
+    P.hi = (s16x2)((u16x2)hi - hb) & keep;
     S[0] = (s16x2){0, 0};
 #pragma unroll
     for (int sc = 1; sc < 4; sc++) {
         S[sc] = (s16x2){0, 0};
         if (!(sec_used & (1 << sc))) continue; // workgroup-uniform
         const int   sec = (sc == 3 ? 4 : sc) << cs;
-        const s16x2 thr = splat16(sec);
+        const u16x2 thr = splatu16(sec);
         const u16x2 sh  = splatu16(max(0, sdamp - msb32_dev((uint32_t)sec)));
         s16x2       a0 = {0, 0}, a1 = {0, 0};
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            a0 = a0 + constrain2(sd[t], thr, sh);     // k = 0, tap weight 2
-            a1 = a1 + constrain2(sd[4 + t], thr, sh); // k = 1, tap weight 1
+            a0 = a0 + constrain_mag(sa[t], thr, sh) * ssg[t];         // k = 0, tap weight 2
+            a1 = a1 + constrain_mag(sa[4 + t], thr, sh) * ssg[4 + t]; // k = 1, tap weight 1
         }
-        S[sc] = (a0 << (s16x2){1, 1}) + a1;
+        S[sc] = ((a0 << (s16x2){1, 1}) + a1) & keep;
     }
 }
 
 // primary sum for threshold `thr` (already strength-adjusted), weights {4,2} or {3,3}
-__device__ __forceinline__ s16x2 pri_sum(const PriPair &P, s16x2 thr, u16x2 sh, s16x2 w0, s16x2 w1) {
-    const s16x2 k0 = constrain2(P.d[0], thr, sh) + constrain2(P.d[1], thr, sh);
-    const s16x2 k1 = constrain2(P.d[2], thr, sh) + constrain2(P.d[3], thr, sh);
+__device__ __forceinline__ s16x2 pri_sum(const PriPair &P, u16x2 thr, u16x2 sh, s16x2 w0, s16x2 w1) {
+    const s16x2 k0 = constrain_mag(P.a[0], thr, sh) * P.sg[0] + constrain_mag(P.a[1], thr, sh) * P.sg[1];
+    const s16x2 k1 = constrain_mag(P.a[2], thr, sh) * P.sg[2] + constrain_mag(P.a[3], thr, sh) * P.sg[3];
     return k0 * w0 + k1 * w1;
 }
 
-// y = clamp(x + ((8 + sum - (sum < 0)) >> 4), lo, hi)   (EbCdef.c:298)
+// y = clamp(x + ((8 + sum - (sum < 0)) >> 4), lo, hi)   (EbCdef.c:298).  16 x is a multiple of 16, so it moves inside
+// the arithmetic shift unchanged: x + ((8 + sum - neg) >> 4) = ((sum - neg) + (16 x + 8)) >> 4, and 16 x + 8 is kept
+// per sample (P.xr).  The sign term comes from the unbiased sum (sum >> 15 is -1 exactly when sum < 0).  No int16
+// wrap: 16 x + 8 + |sum| <= 16 * 1023 + 8 + 912.
 __device__ __forceinline__ s16x2 finish(const PriPair &P, s16x2 sum) {
-    const s16x2 rnd = (sum + (s16x2){8, 8} + (sum >> (s16x2){15, 15})) >> (s16x2){4, 4};
-    return __builtin_elementwise_max(__builtin_elementwise_min(P.x + rnd, P.hi), P.lo);
+    const s16x2 r = (sum + (sum >> (s16x2){15, 15}) + P.xr) >> (s16x2){4, 4};
+    return __builtin_elementwise_max(__builtin_elementwise_min(r, P.hi), P.lo);
 }
 
 // sum over the 8 lanes of each aligned octet (quad xor1, quad xor2, row_half_mirror)
@@ -353,7 +365,7 @@ __global__ void __launch_bounds__(NT, 3) cdef_search_kernel(const SearchArgs A) 
         const int b = 32 * pass + bip, by = b >> 3, bx = b & 7;
         const int r = 8 * by + row, c0 = 8 * bx;
         const bool valid = slisted[b] && (row % ss == 0);
-        const unsigned short vm = valid ? 0xFFFF : 0;
+        const s16x2 keep = splat16(valid ? -1 : 0);
         // source row (registers), zeroed outside the measured set
         s16x2 sp[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
         if (valid) ld_seg8<T>(A.src[0], (long)(64 * fbr + r) * A.sstride[0] + 64 * fbc + c0, sp);
@@ -380,38 +392,40 @@ __global__ void __launch_bounds__(NT, 3) cdef_search_kernel(const SearchArgs A) 
             PriPair   P[4];
             s16x2     S[4][4];
 #pragma unroll
-            for (int h = 0; h < 4; h++) load_pair(P[h], S[h], ltile, LT, r, c0 + 2 * h, d, G.sec_used, ldamp, cs);
+            for (int h = 0; h < 4; h++)
+                load_pair(P[h], S[h], ltile, LT, r, c0 + 2 * h, d, G.sec_used, ldamp, cs, keep);
             for (int li = 0; li < G.nlv; li++) {
-                const int pri = G.lv[li] << cs;
-                const int t   = vb ? (pri * (4 + ib) + 8) >> 4 : 0; // adjust_strength (EbCdef.c:130-135)
-                const int odd = (t >> cs) & 1;
-                const s16x2 thr = splat16(t);
-                const u16x2 sh  = splatu16(max(0, ldamp - msb32_dev((uint32_t)t)));
-                const s16x2 w0 = splat16(odd ? 3 : 4), w1 = splat16(odd ? 3 : 2);
-                s16x2 Pv[4];
+                const int pri = __builtin_amdgcn_readfirstlane(G.lv[li]) << cs; // workgroup-uniform
+                s16x2     Pv[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+                if (pri) { // level 0 (all of group A): every constraint is 0
+                    const int t   = vb ? (pri * (4 + ib) + 8) >> 4 : 0; // adjust_strength (EbCdef.c:130-135)
+                    const int odd = (t >> cs) & 1;
+                    const u16x2 thr = splatu16(t);
+                    const u16x2 sh  = splatu16(max(0, ldamp - msb32_dev((uint32_t)t)));
+                    const s16x2 w0 = splat16(odd ? 3 : 4), w1 = splat16(odd ? 3 : 2);
 #pragma unroll
-                for (int h = 0; h < 4; h++) Pv[h] = pri_sum(P[h], thr, sh, w0, w1);
+                    for (int h = 0; h < 4; h++) Pv[h] = pri_sum(P[h], thr, sh, w0, w1);
+                }
 #pragma unroll
                 for (int sc = 0; sc < 4; sc++) {
-                    const int gi = G.gi[li][sc];
+                    const int gi = __builtin_amdgcn_readfirstlane(G.gi[li][sc]);
                     if (gi < 0) continue; // workgroup-uniform
-                    uint32_t sd = 0, sd2 = 0, sse = 0;
+                    // sum d, sum d^2 and sum d s: the epilogue forms sum (d - s)^2 = sum d^2 - 2 sum d s + sum s^2
+                    uint32_t sd = 0, sd2 = 0, sds = 0;
 #pragma unroll
                     for (int h = 0; h < 4; h++) {
-                        s16x2 y = finish(P[h], Pv[h] + S[h][sc]);
-                        y       = (s16x2)((u16x2)y & (u16x2){vm, vm});
-                        const s16x2 df = y - sp[h];
-                        sd  = __builtin_amdgcn_udot2((u16x2)y, (u16x2){1, 1}, sd, false);
-                        sd2 = __builtin_amdgcn_udot2((u16x2)y, (u16x2)y, sd2, false);
-                        sse = (uint32_t)__builtin_amdgcn_sdot2(df, df, (int)sse, false);
+                        const u16x2 y = (u16x2)finish(P[h], Pv[h] + S[h][sc]);
+                        sd  = __builtin_amdgcn_udot2(y, (u16x2){1, 1}, sd, false);
+                        sd2 = __builtin_amdgcn_udot2(y, y, sd2, false);
+                        sds = __builtin_amdgcn_udot2(y, (u16x2)sp[h], sds, false);
                     }
                     sd  = oct_sum(sd);
                     sd2 = oct_sum(sd2);
-                    sse = oct_sum(sse);
+                    sds = oct_sum(sds);
                     if (row == 0) {
                         stats[gi][bip][0] = sd;
                         stats[gi][bip][1] = sd2;
-                        stats[gi][bip][2] = sse;
+                        stats[gi][bip][2] = sds;
                     }
                 }
             }
@@ -426,8 +440,8 @@ __global__ void __launch_bounds__(NT, 3) cdef_search_kernel(const SearchArgs A) 
                 for (int u = 0; u < 8; u++) {
                     const int bb = 8 * sub + u, bg = 32 * pass + bb;
                     if (!slisted[bg]) continue;
-                    acc += cdef_luma_dist(stats[gi][bb][0], sstat[bg][0], stats[gi][bb][1], sstat[bg][1],
-                                          stats[gi][bb][2], cs);
+                    const uint32_t sse = stats[gi][bb][1] + sstat[bg][1] - 2 * stats[gi][bb][2]; // exact: no term wraps
+                    acc += cdef_luma_dist(stats[gi][bb][0], sstat[bg][0], stats[gi][bb][1], sstat[bg][1], sse, cs);
                 }
             }
             acc += __shfl_xor(acc, 1);
@@ -447,7 +461,7 @@ __global__ void __launch_bounds__(NT, 3) cdef_search_kernel(const SearchArgs A) 
         const int by = r >> 2;
         const uint16_t *tile = ctile[pl];
         s16x2 sp[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-        unsigned short vm[4];
+        s16x2 keep[4]; // per pair: the segment's two 4x4 blocks are listed separately
         int  dirb[4];
         const int cb0 = by * 8 + (c0 >> 2); // the segment's two 4x4 chroma blocks: cb0, cb0 + 1
         if (slisted[cb0] || slisted[cb0 + 1]) // inside the plane: listed blocks are in the frame, widths are even
@@ -455,7 +469,7 @@ __global__ void __launch_bounds__(NT, 3) cdef_search_kernel(const SearchArgs A) 
 #pragma unroll
         for (int h = 0; h < 4; h++) {
             const int cb = cb0 + (h >> 1);
-            vm[h]   = slisted[cb] ? 0xFFFF : 0;
+            keep[h] = splat16(slisted[cb] ? -1 : 0);
             dirb[h] = sdir[cb];
             if (!slisted[cb]) sp[h] = (s16x2){0, 0};
         }
@@ -466,25 +480,27 @@ __global__ void __launch_bounds__(NT, 3) cdef_search_kernel(const SearchArgs A) 
             s16x2   S[4][4];
 #pragma unroll
             for (int h = 0; h < 4; h++)
-                load_pair(P[h], S[h], tile, CT, r, c0 + 2 * h, g ? dirb[h] : 0, G.sec_used, cdamp, cs);
+                load_pair(P[h], S[h], tile, CT, r, c0 + 2 * h, g ? dirb[h] : 0, G.sec_used, cdamp, cs, keep[h]);
             for (int li = 0; li < G.nlv; li++) {
-                const int pri = G.lv[li] << cs; // no strength adjustment for chroma (EbCdef.c:401)
-                const int odd = (pri >> cs) & 1;
-                const s16x2 thr = splat16(pri);
-                const u16x2 sh  = splatu16(max(0, cdamp - msb32_dev((uint32_t)pri)));
-                const s16x2 w0 = splat16(odd ? 3 : 4), w1 = splat16(odd ? 3 : 2);
-                s16x2 Pv[4];
+                // no strength adjustment for chroma (EbCdef.c:401)
+                const int pri = __builtin_amdgcn_readfirstlane(G.lv[li]) << cs; // workgroup-uniform
+                s16x2     Pv[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+                if (pri) { // level 0 (all of group A): every constraint is 0
+                    const int odd = (pri >> cs) & 1;
+                    const u16x2 thr = splatu16(pri);
+                    const u16x2 sh  = splatu16(max(0, cdamp - msb32_dev((uint32_t)pri)));
+                    const s16x2 w0 = splat16(odd ? 3 : 4), w1 = splat16(odd ? 3 : 2);
 #pragma unroll
-                for (int h = 0; h < 4; h++) Pv[h] = pri_sum(P[h], thr, sh, w0, w1);
+                    for (int h = 0; h < 4; h++) Pv[h] = pri_sum(P[h], thr, sh, w0, w1);
+                }
 #pragma unroll
                 for (int sc = 0; sc < 4; sc++) {
-                    const int gi = G.gi[li][sc];
-                    if (gi < 0) continue;
+                    const int gi = __builtin_amdgcn_readfirstlane(G.gi[li][sc]);
+                    if (gi < 0) continue; // workgroup-uniform
                     uint32_t sse = 0;
 #pragma unroll
                     for (int h = 0; h < 4; h++) {
-                        s16x2 y = finish(P[h], Pv[h] + S[h][sc]);
-                        y       = (s16x2)((u16x2)y & (u16x2){vm[h], vm[h]});
+                        const s16x2 y  = finish(P[h], Pv[h] + S[h][sc]);
                         const s16x2 df = y - sp[h];
                         sse = (uint32_t)__builtin_amdgcn_sdot2(df, df, (int)sse, false);
                     }

@@ -112,10 +112,12 @@ const char *svtgpu_version(void);
  * SvtGpuCcsoParams; 9: the OBMC shims and svtgpu_obmc_*; 10: the super-resolution upscale svtgpu_superres_*;
  * 11: the non-normative frame resizer svtgpu_resize_* and its two RTCD shims; 12: the temporal filter's filter half
  * svtgpu_tf_*, SvtGpuTfBlock / SvtGpuTfParams / SvtGpuTfPlanes, and its nine RTCD shims; 13: the eight single-reference
- * interpolation shims svtgpu_av1_(highbd_)convolve_*_sr, SvtGpuTfMotion and svtgpu_tf_predict_frame).
+ * interpolation shims svtgpu_av1_(highbd_)convolve_*_sr, SvtGpuTfMotion and svtgpu_tf_predict_frame; 14: the temporal
+ * filter's sub-pel search svtgpu_tf_search_frame / _read, SvtGpuTfFullpel / SvtGpuTfSearchParams, and the device chain
+ * svtgpu_tf_compensate_filter_frame).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 13
+#define SVTGPU_ABI_VERSION 14
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1067,8 +1069,9 @@ SVTGPU_ERROR_T svtgpu_av1_highbd_resize_plane(const uint16_t *const input, int h
  * The temporal filter's filter half (EbTemporalFiltering.c): the noise estimate (svt_estimate_noise_fp16_c /
  * svt_estimate_noise_highbd_fp16_c, :3672-3740) and the block loop of produce_temporally_filtered_pic (:2939-3301) from
  * apply_filtering_central to get_final_filtered_pixels, bit-exact with the reference's C.  The motion half -- motion
- * estimation, the sub-pel searches and the inter prediction -- stays on the host; what it leaves behind is this section's
- * input: the predictor planes of every reference picture and, per (reference, 64x64 block), one SvtGpuTfBlock.
+ * estimation, the sub-pel searches and the inter prediction -- is not in this section (the compensation and the sub-pel
+ * search have their own below; HME / ME stays on the host); what it leaves behind is this section's input: the predictor
+ * planes of every reference picture and, per (reference, 64x64 block), one SvtGpuTfBlock.
  * ========================================================================================= */
 /* What the search left in MeContext for one 64x64 block of one reference (tf_32x32_block_split_flag, tf_32x32_mv_x / _y,
  * tf_16x16_mv_x / _y, tf_32x32_block_error, tf_16x16_block_error); 256 bytes.  Index 4 * idx_32x32 + q is 16x16 quadrant
@@ -1182,7 +1185,8 @@ void svtgpu_tf_get_final_filtered_pixels(int32_t tf_chroma, uint8_t **src_center
  * tf_32x32_inter_prediction (EbTemporalFiltering.c:2230-2580) for every (reference, 64x64 block) of a picture in one launch,
  * bit-exact with the reference's C.  With it the device chain of the temporal filter is: upload the padded reference
  * pictures, svtgpu_tf_predict_frame, svtgpu_tf_filter_frame; the host supplies the per-block motion records only.  The
- * search (ME / HME, the tf_*_sub_pel_search walks), the compound (jnt_) and scaled convolves and intrabc stay on the host.
+ * tf_*_sub_pel_search walks are the next section's; ME / HME, the compound (jnt_) and scaled convolves and intrabc stay on
+ * the host.
  * ========================================================================================= */
 /* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
  * the 8-tap kernel rows already selected for the phase (av1_get_interp_filter_subpel_kernel of the InterpFilterParams);
@@ -1248,6 +1252,67 @@ typedef struct SvtGpuTfMotion {
 int svtgpu_tf_predict_frame(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
                             int32_t border_y, const SvtGpuTfMotion *motion, int32_t bit_depth, int32_t tf_chroma,
                             const SvtGpuTfPlanes *pred, void *stream);
+
+/* =========================================================================================
+ * The temporal filter's sub-pel motion search: the `frame_index != index_center` section of
+ * produce_temporally_filtered_pic (EbTemporalFiltering.c:3087-3261) for every (reference, 64x64 block) of a picture in one
+ * launch -- tf_64x64 / 32x32 / 16x16 / 8x8_sub_pel_search (svt_check_position, tf_subpel_search, :1535-2228), the
+ * 64-vs-32 test, the pred_error_32x32_th bypass and derive_tf_32x32_block_split_flag (:240-289) -- bit-exact with the
+ * reference's C.  It leaves one SvtGpuTfMotion and one SvtGpuTfBlock per (reference, block) in a device buffer of the
+ * state, which svtgpu_tf_compensate_filter_frame consumes in stream order: search -> compensation -> filter without the
+ * records leaving the device.  Only HME / ME (svt_aom_motion_estimation_b64, full-pel) stays on the host.
+ * ========================================================================================= */
+/* What full-pel ME left for one (reference, 64x64 block): p_best_mv64x64[0], p_best_mv32x32, p_best_mv16x16, p_best_mv8x8
+ * as (x, y) in whole samples, in SvtGpuTfMotion's nested raster indices (the caller's adapter applies tab16x16 / tab8x8);
+ * every component within [-2047, 2047] (its eighth-sample form and the 7/8 the walk adds then fit the reference's int16).
+ * force64: the host's `tf_use_pred_64x64_only_th && (th == 0xFF || tf_use_64x64_pred())`; with th == 0xFF the caller
+ * puts hme_sc_x / _y into mv64.  352 bytes. */
+typedef struct SvtGpuTfFullpel {
+    int16_t mv64_x, mv64_y;
+    int16_t mv32_x[4], mv32_y[4];
+    int16_t mv16_x[16], mv16_y[16];
+    int16_t mv8_x[64], mv8_y[64];
+    uint8_t force64, reserved[11];
+} SvtGpuTfFullpel;
+/* tf_ctrls as the search reads them: the three pel modes (0 off, 1 all eight positions, 2 no diagonals), use_2tap (64x64
+ * and 32x32 take BILINEAR, else EIGHTTAP_REGULAR; 16x16 and 8x8 always regular), sub_sampling_shift (0 or 1),
+ * enable_8x8_pred, subpel_early_exit_th (0 .. 255), the bit depth of the planes searched (8 or 10; with use_8bit_subpel a
+ * 10-bit encode passes its 8-bit planes and 8) and pred_error_32x32_th. */
+typedef struct SvtGpuTfSearchParams {
+    int32_t  half_pel_mode, quarter_pel_mode, eight_pel_mode;
+    int32_t  use_2tap;
+    int32_t  sub_sampling_shift;
+    int32_t  enable_8x8_pred;
+    int32_t  subpel_early_exit_th;
+    int32_t  bit_depth;
+    uint64_t pred_error_32x32_th;
+} SvtGpuTfSearchParams;
+/* The search of one picture: luma only.  centre: as svtgpu_tf_filter_frame's (readable over the 64-aligned area, 16-byte
+ * aligned, stride a multiple of 16 bytes); refs[r].plane[0]: sample (0, 0) of the padded reference picture with border_x /
+ * border_y readable samples around it, as svtgpu_tf_predict_frame's (every read coordinate is clamped into the border; from
+ * a border of 72 the clamp never acts).  fullpel[r * nblk + b]: host memory, copied before the call returns.  A field of
+ * the records that neither the compensation nor the filter reads under the block's flags is 0: under use64 everything but
+ * use64, mv64 and the block record's mv32 (= mv64, which the filter reads) -- err32 of such a block is not a search result
+ * and is written by svtgpu_tf_compensate_filter_frame; of an unsplit 32x32 block mv16 / mv8 / split16 / err16; of a split
+ * one mv32 / err32, and mv16 (motion record) or mv8 by split16.  Runs in stream order with no host wait.
+ * SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any launch: a null pointer, n_refs < 0, a bit depth
+ * other than 8 or 10, a mode outside 0 .. 2, another parameter out of range, a full-pel MV beyond 2047, a negative border,
+ * a misaligned or too narrow plane. */
+int svtgpu_tf_search_frame(SvtGpuTfState *state, const SvtGpuTfPlanes *centre, const SvtGpuTfPlanes *refs, int32_t n_refs,
+                           int32_t border_x, int32_t border_y, const SvtGpuTfFullpel *fullpel,
+                           const SvtGpuTfSearchParams *params, void *stream);
+/* Copies the records of the last search (n_refs as searched) to host memory and waits for `stream`. */
+int svtgpu_tf_search_read(SvtGpuTfState *state, int32_t n_refs, SvtGpuTfMotion *motion_out, SvtGpuTfBlock *blocks_out,
+                          void *stream);
+/* The rest of the chain on the state's records: svtgpu_tf_predict_frame's kernel on the motion records (refs, borders and
+ * pred as there; bit depth and tf_chroma are filter_params'), then err32 of every use64 block from the predictor against
+ * the centre (convert_64x64_info_to_32x32_info, :2665-2733: the variance of each 32x32 quadrant over 32 >> sub_sampling_shift
+ * rows at doubled strides, shifted back), then svtgpu_tf_filter_frame's kernel on the block records into `out`.  No record
+ * is uploaded and the host does not wait.  n_refs is the last search's.  Refusals as the two sibling entries'. */
+int svtgpu_tf_compensate_filter_frame(SvtGpuTfState *state, const SvtGpuTfPlanes *centre, const SvtGpuTfPlanes *refs,
+                                      int32_t n_refs, int32_t border_x, int32_t border_y,
+                                      const SvtGpuTfParams *filter_params, int32_t sub_sampling_shift,
+                                      const SvtGpuTfPlanes *pred, const SvtGpuTfPlanes *out, void *stream);
 
 /* =========================================================================================
  * Loop restoration

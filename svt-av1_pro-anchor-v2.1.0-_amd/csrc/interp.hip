@@ -315,20 +315,34 @@ extern "C" int svtgpu_tf_predict_frame(SvtGpuTfState *s, const SvtGpuTfPlanes *r
     const size_t off = (size_t)n_refs * sizeof(PredPlanes), nb = (size_t)n_refs * nblk * sizeof(SvtGpuTfMotion);
     uint8_t     *hm, *dm;
     if (int rc = svtgpu_tf_meta_begin(s, off + nb, &hm, &dm)) return rc;
-    PredPlanes *hp = (PredPlanes *)hm;
+    svtgpu_tf_predict_desc_fill(hm, refs, pred, n_refs);
+    memcpy(hm + off, motion, nb);
+    if (int rc = svtgpu_tf_meta_upload(s, off + nb, st)) return rc;
+    return svtgpu_tf_predict_launch(s, dm, (const SvtGpuTfMotion *)(dm + off), n_refs, border_x, border_y, bit_depth, tf_chroma,
+                                    st);
+}
+
+// tf_predict_kernel on descriptors and motion records that are on the device already (svtgpu_tf_compensate_filter_frame)
+size_t svtgpu_tf_predict_desc_bytes() { return sizeof(PredPlanes); }
+void   svtgpu_tf_predict_desc_fill(void *host, const SvtGpuTfPlanes *refs, const SvtGpuTfPlanes *pred, int n_refs) {
+    PredPlanes *hp = (PredPlanes *)host;
     for (int r = 0; r < n_refs; r++)
         for (int p = 0; p < 3; p++) {
             hp[r].ref[p] = refs[r].plane[p], hp[r].rstride[p] = refs[r].stride[p];
             hp[r].pred[p] = pred[r].plane[p], hp[r].pstride[p] = pred[r].stride[p];
         }
-    memcpy(hm + off, motion, nb);
-    if (int rc = svtgpu_tf_meta_upload(s, off + nb, st)) return rc;
+}
+int svtgpu_tf_predict_launch(SvtGpuTfState *s, const void *d_desc, const SvtGpuTfMotion *d_motion, int n_refs, int border_x,
+                             int border_y, int bit_depth, int tf_chroma, hipStream_t st) {
+    SvtGpuContext *ctx;
+    int32_t        width, height, blk_cols, nblk;
+    svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
     PredArgs a;
-    a.planes = (const PredPlanes *)dm, a.motion = (const SvtGpuTfMotion *)(dm + off);
+    a.planes = (const PredPlanes *)d_desc, a.motion = d_motion;
     a.blk_cols = blk_cols, a.nblk = nblk, a.width = width, a.height = height;
     a.border_x = border_x, a.border_y = border_y, a.bd = bit_depth, a.tf_chroma = tf_chroma;
     const dim3 grid((unsigned)(n_refs * nblk));
-    if (bs == 1)
+    if (bit_depth == 8)
         hipLaunchKernelGGL(tf_predict_kernel<uint8_t>, grid, dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL(tf_predict_kernel<uint16_t>, grid, dim3(256), 0, st, a);

@@ -204,6 +204,24 @@ void svtgpu_tf_state_geometry(const SvtGpuTfState *s, SvtGpuContext **ctx, int32
                               int32_t *blk_cols, int32_t *nblk);
 int  svtgpu_tf_meta_begin(SvtGpuTfState *s, size_t bytes, uint8_t **host, uint8_t **dev);
 int  svtgpu_tf_meta_upload(SvtGpuTfState *s, size_t bytes, hipStream_t st);
+// The device chain of the temporal filter (svtgpu_tf_compensate_filter_frame, tf.hip) launches the existing kernels on
+// device records.  interp.hip: the size of one reference's plane descriptor, its fill, and tf_predict_kernel's launch;
+// tf_search.hip: the (pointer, stride) descriptor of a luma plane and tf_err64_kernel's launch; tf.hip: the state's
+// grow-only record buffer ([n_refs][nblk] SvtGpuTfMotion, then as many SvtGpuTfBlock) and the count of the last search.
+struct SvtGpuTfLuma {
+    const void *plane;
+    int32_t     stride, pad;
+};
+size_t svtgpu_tf_predict_desc_bytes();
+void   svtgpu_tf_predict_desc_fill(void *host, const SvtGpuTfPlanes *refs, const SvtGpuTfPlanes *pred, int n_refs);
+int    svtgpu_tf_predict_launch(SvtGpuTfState *s, const void *d_desc, const SvtGpuTfMotion *d_motion, int n_refs,
+                                int border_x, int border_y, int bit_depth, int tf_chroma, hipStream_t st);
+int    svtgpu_tf_err64_launch(SvtGpuTfState *s, const SvtGpuTfPlanes *centre, const SvtGpuTfLuma *d_pred,
+                              const SvtGpuTfMotion *d_motion, SvtGpuTfBlock *d_blocks, int n_refs, int bit_depth,
+                              int sub_sampling_shift, hipStream_t st);
+int    svtgpu_tf_records_reserve(SvtGpuTfState *s, int n_refs, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks);
+void   svtgpu_tf_records_commit(SvtGpuTfState *s, int n_refs); // the count _get reports: set once a search is queued
+int    svtgpu_tf_records_get(SvtGpuTfState *s, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks); // the last search's n_refs
 
 // Diagnostics (SVTGPU_WGCLK=<file>, never on by default): per workgroup 8 words -- up to 6 time marks on the 100 MHz
 // s_memrealtime clock (slot 0 = start; the kernel's phases after it; unused slots stay 0) and the hardware id words

@@ -1,8 +1,9 @@
 // tf.hip — the filter half of the encoder's temporal filter (EbTemporalFiltering.c) on gfx950: the noise estimate
 // (svt_estimate_noise_fp16_c / svt_estimate_noise_highbd_fp16_c, :3672-3740), and the block loop of
 // produce_temporally_filtered_pic (:2939-3301) from apply_filtering_central to get_final_filtered_pixels as one launch per
-// picture.  The motion half (ME, sub-pel search, inter prediction) stays on the host: the caller passes what it leaves
-// behind, the predictor pictures and one SvtGpuTfBlock per (reference, 64x64 block).
+// picture.  The entry takes what the motion half leaves behind, the predictor pictures and one SvtGpuTfBlock per
+// (reference, 64x64 block): from the host (svtgpu_tf_filter_frame), or from the device records of tf_search.hip with the
+// compensation of interp.hip in front (svtgpu_tf_compensate_filter_frame); only HME / ME stays on the host.
 //
 //   tf_frame_kernel   a workgroup owns a 64x64 block (luma and both chroma), a wave one 32x32 block of it (idx_32x32 =
 //                     the wave).  A lane holds 2 x 8 adjacent luma samples (rows l >> 2 and 16 + (l >> 2), columns
@@ -544,6 +545,9 @@ struct SvtGpuTfState {
     size_t         cap_meta;        // bytes of each
     hipEvent_t     copied;          // the last upload of h_meta has left it
     hipStream_t    last;            // the stream of the last filter call
+    uint8_t       *d_records;       // the search's records: [refs][nblk] SvtGpuTfMotion, then [refs][nblk] SvtGpuTfBlock
+    int32_t        cap_records;     // in references; only grows
+    int32_t        search_refs;     // the references of the last search
 };
 
 namespace {
@@ -574,6 +578,26 @@ bool planes_ok(const SvtGpuTfPlanes *p, int aw, int bs) {
     }
     return true;
 }
+
+// tf_frame_kernel on `a`, whose refs / blocks already point at device memory
+int launch_frame(SvtGpuTfState *s, TfFrameArgs &a, const SvtGpuTfPlanes *centre, const SvtGpuTfPlanes *out,
+                 const SvtGpuTfParams *params, int n_refs, hipStream_t st) {
+    for (int p = 0; p < 3; p++) {
+        a.centre[p] = centre->plane[p], a.cstride[p] = centre->stride[p];
+        a.out[p] = out->plane[p], a.ostride[p] = out->stride[p];
+        a.decay[p] = params->decay_factor_fp16[p];
+    }
+    a.n_refs = n_refs, a.blk_cols = s->blk_cols, a.nblk = s->nblk;
+    a.thr_shr8 = tf_threshold_shr8(params->mv_dist_th);
+    a.tf_chroma = params->tf_chroma, a.bd = params->bit_depth, a.zz = params->use_zz_based_filter;
+    s->last = st;
+    if (params->bit_depth == 8)
+        hipLaunchKernelGGL(tf_frame_kernel<uint8_t>, dim3(s->nblk), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(tf_frame_kernel<uint16_t>, dim3(s->nblk), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return SVTGPU_OK;
+}
 } // namespace
 
 // The state's metadata buffer for svtgpu_tf_predict_frame (interp.hip), under the filter's rule: one pinned host copy,
@@ -594,6 +618,30 @@ int svtgpu_tf_meta_upload(SvtGpuTfState *s, size_t bytes, hipStream_t st) {
     svtgpu_count_xfer(0, bytes);
     s->last = st;
     return SVTGPU_OK;
+}
+
+// The search's record buffer (tf_search.hip writes it, svtgpu_tf_compensate_filter_frame reads it): grown for n_refs, never
+// shrunk; growing waits for the work queued on the state, which may still read the old buffer.
+int svtgpu_tf_records_reserve(SvtGpuTfState *s, int n_refs, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks) {
+    if (n_refs > s->cap_records) {
+        if (s->d_records) {
+            HIP_TRY(hipStreamSynchronize(s->last));
+            (void)hipFree(s->d_records);
+            s->d_records = nullptr, s->cap_records = 0;
+        }
+        if (hipMalloc(&s->d_records, (size_t)n_refs * s->nblk * (sizeof(SvtGpuTfMotion) + sizeof(SvtGpuTfBlock))) != hipSuccess)
+            return SVTGPU_ERR_OOM;
+        s->cap_records = n_refs;
+    }
+    *motion = (SvtGpuTfMotion *)s->d_records;
+    *blocks = (SvtGpuTfBlock *)(s->d_records + (size_t)n_refs * s->nblk * sizeof(SvtGpuTfMotion));
+    return SVTGPU_OK;
+}
+void svtgpu_tf_records_commit(SvtGpuTfState *s, int n_refs) { s->search_refs = n_refs; }
+int  svtgpu_tf_records_get(SvtGpuTfState *s, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks) {
+    *motion = (SvtGpuTfMotion *)s->d_records;
+    *blocks = (SvtGpuTfBlock *)(s->d_records + (size_t)s->search_refs * s->nblk * sizeof(SvtGpuTfMotion));
+    return s->search_refs;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -652,6 +700,7 @@ extern "C" void svtgpu_tf_state_destroy(SvtGpuTfState *s) {
     (void)hipEventDestroy(s->copied);
     if (s->d_meta) (void)hipFree(s->d_meta);
     if (s->h_meta) (void)hipHostFree(s->h_meta);
+    if (s->d_records) (void)hipFree(s->d_records);
     (void)hipFree(s->d_noise);
     delete s;
 }
@@ -707,21 +756,57 @@ extern "C" int svtgpu_tf_filter_frame(SvtGpuTfState *s, const SvtGpuTfPlanes *ce
         svtgpu_count_xfer(0, off + nb);
         a.refs = (const TfRef *)s->d_meta, a.blocks = (const SvtGpuTfBlock *)(s->d_meta + off);
     }
-    for (int p = 0; p < 3; p++) {
-        a.centre[p] = centre->plane[p], a.cstride[p] = centre->stride[p];
-        a.out[p] = out->plane[p], a.ostride[p] = out->stride[p];
-        a.decay[p] = params->decay_factor_fp16[p];
+    return launch_frame(s, a, centre, out, params, n_refs, st);
+}
+
+// The device chain after svtgpu_tf_search_frame: the compensation on the state's motion records, err32 of the use64
+// blocks, the filter on the state's block records.  One small upload of plane descriptors; no record leaves the device.
+extern "C" int svtgpu_tf_compensate_filter_frame(SvtGpuTfState *s, const SvtGpuTfPlanes *centre, const SvtGpuTfPlanes *refs,
+                                                 int32_t n_refs, int32_t border_x, int32_t border_y,
+                                                 const SvtGpuTfParams *params, int32_t sub_sampling_shift,
+                                                 const SvtGpuTfPlanes *pred, const SvtGpuTfPlanes *out, void *stream) {
+    if (n_refs > kMaxRefs) return SVTGPU_ERR_UNSUPPORTED;
+    if (!s || !params || n_refs < 0 || (n_refs && (!refs || !pred)) || !bits_ok(params->bit_depth) || border_x < 0 ||
+        border_y < 0 || (sub_sampling_shift != 0 && sub_sampling_shift != 1) || n_refs != s->search_refs)
+        return SVTGPU_ERR_INVALID_ARG;
+    const int bs = params->bit_depth > 8 ? 2 : 1, aw = s->blk_cols * 64, nplanes = params->tf_chroma ? 3 : 1;
+    if (!planes_ok(centre, aw, bs) || !planes_ok(out, aw, bs)) return SVTGPU_ERR_INVALID_ARG;
+    for (int r = 0; r < n_refs; r++) {
+        if (!planes_ok(&pred[r], aw, bs)) return SVTGPU_ERR_INVALID_ARG; // the filter reads all three predictor planes
+        for (int p = 0; p < nplanes; p++) {
+            const int ss = p > 0;
+            if (!refs[r].plane[p] || ((uintptr_t)refs[r].plane[p] & (bs - 1)) ||
+                refs[r].stride[p] < (s->width >> ss) + 2 * (border_x >> ss))
+                return SVTGPU_ERR_INVALID_ARG;
+        }
     }
-    a.n_refs = n_refs, a.blk_cols = s->blk_cols, a.nblk = s->nblk;
-    a.thr_shr8 = tf_threshold_shr8(params->mv_dist_th);
-    a.tf_chroma = params->tf_chroma, a.bd = params->bit_depth, a.zz = params->use_zz_based_filter;
-    s->last = st;
-    if (bs == 1)
-        hipLaunchKernelGGL(tf_frame_kernel<uint8_t>, dim3(s->nblk), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(tf_frame_kernel<uint16_t>, dim3(s->nblk), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return SVTGPU_OK;
+    hipStream_t st = pick_stream(s->ctx, stream);
+    TfFrameArgs a;
+    memset(&a, 0, sizeof a);
+    if (n_refs) {
+        const size_t o_ref = (size_t)n_refs * svtgpu_tf_predict_desc_bytes(), o_luma = o_ref + (size_t)n_refs * sizeof(TfRef);
+        const size_t total = o_luma + (size_t)n_refs * sizeof(SvtGpuTfLuma);
+        uint8_t     *hm, *dm;
+        if (int rc = svtgpu_tf_meta_begin(s, total, &hm, &dm)) return rc;
+        svtgpu_tf_predict_desc_fill(hm, refs, pred, n_refs);
+        TfRef        *hr = (TfRef *)(hm + o_ref);
+        SvtGpuTfLuma *hl = (SvtGpuTfLuma *)(hm + o_luma);
+        for (int r = 0; r < n_refs; r++) {
+            for (int p = 0; p < 3; p++) hr[r].plane[p] = pred[r].plane[p], hr[r].stride[p] = pred[r].stride[p];
+            hr[r].pad = 0, hl[r].plane = pred[r].plane[0], hl[r].stride = pred[r].stride[0], hl[r].pad = 0;
+        }
+        if (int rc = svtgpu_tf_meta_upload(s, total, st)) return rc;
+        SvtGpuTfMotion *dmo;
+        SvtGpuTfBlock  *dbl;
+        svtgpu_tf_records_get(s, &dmo, &dbl);
+        if (int rc = svtgpu_tf_predict_launch(s, dm, dmo, n_refs, border_x, border_y, params->bit_depth, params->tf_chroma, st))
+            return rc;
+        if (int rc = svtgpu_tf_err64_launch(s, centre, (const SvtGpuTfLuma *)(dm + o_luma), dmo, dbl, n_refs, params->bit_depth,
+                                            sub_sampling_shift, st))
+            return rc;
+        a.refs = (const TfRef *)(dm + o_ref), a.blocks = dbl;
+    }
+    return launch_frame(s, a, centre, out, params, n_refs, st);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -294,6 +294,45 @@ class TfMotion(ctypes.Structure):
 
 
 assert ctypes.sizeof(TfMotion) == 368
+
+
+class TfFullpel(ctypes.Structure):
+    """Mirror of SvtGpuTfFullpel: the full-pel MVs ME left for one (reference, 64x64 block) and force64, 352 bytes."""
+    _fields_ = [("mv64_x", ctypes.c_int16), ("mv64_y", ctypes.c_int16), ("mv32_x", ctypes.c_int16 * 4),
+                ("mv32_y", ctypes.c_int16 * 4), ("mv16_x", ctypes.c_int16 * 16), ("mv16_y", ctypes.c_int16 * 16),
+                ("mv8_x", ctypes.c_int16 * 64), ("mv8_y", ctypes.c_int16 * 64), ("force64", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 11)]
+
+    @classmethod
+    def make(cls, mv64, mv32, mv16, mv8, force64=0):
+        """mv64 (x, y); mv32 [4][2], mv16 [16][2], mv8 [64][2] as (x, y), whole samples."""
+        f = cls()
+        f.mv64_x, f.mv64_y, f.force64 = int(mv64[0]), int(mv64[1]), int(force64)
+        for i in range(4):
+            f.mv32_x[i], f.mv32_y[i] = int(mv32[i][0]), int(mv32[i][1])
+        for i in range(16):
+            f.mv16_x[i], f.mv16_y[i] = int(mv16[i][0]), int(mv16[i][1])
+        for i in range(64):
+            f.mv8_x[i], f.mv8_y[i] = int(mv8[i][0]), int(mv8[i][1])
+        return f
+
+
+class TfSearchParams(ctypes.Structure):
+    """Mirror of SvtGpuTfSearchParams, 40 bytes."""
+    _fields_ = [("half_pel_mode", _I32), ("quarter_pel_mode", _I32), ("eight_pel_mode", _I32), ("use_2tap", _I32),
+                ("sub_sampling_shift", _I32), ("enable_8x8_pred", _I32), ("subpel_early_exit_th", _I32), ("bit_depth", _I32),
+                ("pred_error_32x32_th", ctypes.c_uint64)]
+
+    @classmethod
+    def make(cls, modes, use_2tap, sub_sampling_shift, enable_8x8_pred, subpel_early_exit_th, pred_error_32x32_th, bit_depth):
+        p = cls()
+        p.half_pel_mode, p.quarter_pel_mode, p.eight_pel_mode = (int(v) for v in modes)
+        p.use_2tap, p.sub_sampling_shift, p.enable_8x8_pred = int(use_2tap), int(sub_sampling_shift), int(enable_8x8_pred)
+        p.subpel_early_exit_th, p.pred_error_32x32_th, p.bit_depth = int(subpel_early_exit_th), int(pred_error_32x32_th), int(bit_depth)
+        return p
+
+
+assert ctypes.sizeof(TfFullpel) == 352 and ctypes.sizeof(TfSearchParams) == 40 and ctypes.sizeof(TfBlock) == 256
 _I16P = ctypes.POINTER(ctypes.c_int16)
 _CONVOLVE_SR = [_P, _I32, _P, _I32, _I32, _I32, _I16P, _I16P, _I32, _I32]
 INTERP_FORMS = ("2d_sr", "x_sr", "y_sr", "2d_copy_sr")
@@ -457,6 +496,12 @@ _SIGS = {
     "svtgpu_interp_tables": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I32)]),
     "svtgpu_tf_predict_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32, ctypes.POINTER(TfMotion),
                                                _I32, _I32, ctypes.POINTER(TfPlanes), _P]),
+    "svtgpu_tf_search_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
+                                              ctypes.POINTER(TfFullpel), ctypes.POINTER(TfSearchParams), _P]),
+    "svtgpu_tf_search_read": (ctypes.c_int, [_P, _I32, ctypes.POINTER(TfMotion), ctypes.POINTER(TfBlock), _P]),
+    "svtgpu_tf_compensate_filter_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32,
+                                                         _I32, ctypes.POINTER(TfParams), _I32, ctypes.POINTER(TfPlanes),
+                                                         ctypes.POINTER(TfPlanes), _P]),
     "svtgpu_me_batch_destroy": (None, [_P]),
     "svtgpu_me_set_origins": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_me_search": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -1546,6 +1591,32 @@ class TfState:
         ma = (TfMotion * max(len(motion), 1))(*motion)
         check(lib().svtgpu_tf_predict_frame(self.h, ra if n else None, n, int(border_x), int(border_y), ma if n else None,
                                             int(bit_depth), int(tf_chroma), pa if n else None, stream))
+
+    def search_frame(self, centre, refs, border_x, border_y, fullpel, params, stream=None):
+        """centre: TfPlanes (luma read); refs: a list of TfPlanes at sample (0, 0) of the padded pictures; fullpel: a list
+        of TfFullpel, [reference][block] flattened; params: TfSearchParams.  The records stay on the device."""
+        n = len(refs)
+        assert len(fullpel) == n * self.nblk, "one TfFullpel per (reference, 64x64 block)"
+        ra = (TfPlanes * max(n, 1))(*refs)
+        fa = (TfFullpel * max(len(fullpel), 1))(*fullpel)
+        check(lib().svtgpu_tf_search_frame(self.h, ctypes.byref(centre), ra if n else None, n, int(border_x), int(border_y),
+                                           fa if n else None, ctypes.byref(params), stream))
+
+    def search_read(self, n_refs, stream=None):
+        """The records of the last search: (a TfMotion array, a TfBlock array), [reference][block] flattened."""
+        mo, bl = (TfMotion * (n_refs * self.nblk))(), (TfBlock * (n_refs * self.nblk))()
+        check(lib().svtgpu_tf_search_read(self.h, int(n_refs), mo, bl, stream))
+        return mo, bl
+
+    def compensate_filter_frame(self, centre, refs, border_x, border_y, params, sub_sampling_shift, pred, out, stream=None):
+        """The chain behind search_frame on the state's records: compensation into pred, err32 of the use64 blocks, the
+        filter into out.  centre / out: TfPlanes; refs / pred: lists of TfPlanes; params: TfParams."""
+        n = len(refs)
+        assert len(pred) == n
+        ra, pa = (TfPlanes * max(n, 1))(*refs), (TfPlanes * max(n, 1))(*pred)
+        check(lib().svtgpu_tf_compensate_filter_frame(self.h, ctypes.byref(centre), ra if n else None, n, int(border_x),
+                                                      int(border_y), ctypes.byref(params), int(sub_sampling_shift),
+                                                      pa if n else None, ctypes.byref(out), stream))
 
 
 def interp_tables():

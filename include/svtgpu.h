@@ -114,10 +114,10 @@ const char *svtgpu_version(void);
  * svtgpu_tf_*, SvtGpuTfBlock / SvtGpuTfParams / SvtGpuTfPlanes, and its nine RTCD shims; 13: the eight single-reference
  * interpolation shims svtgpu_av1_(highbd_)convolve_*_sr, SvtGpuTfMotion and svtgpu_tf_predict_frame; 14: the temporal
  * filter's sub-pel search svtgpu_tf_search_frame / _read, SvtGpuTfFullpel / SvtGpuTfSearchParams, and the device chain
- * svtgpu_tf_compensate_filter_frame).
+ * svtgpu_tf_compensate_filter_frame); 15: the diagnostic read-back svtgpu_lr_read_sgr_planes).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 14
+#define SVTGPU_ABI_VERSION 15
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1431,6 +1431,15 @@ int svtgpu_lr_read_result(SvtGpuLrState *s, int32_t frame_type_out[3], void *str
 /* The state's units of one plane (the RestorationUnitInfo the frame header / tile coding writes: the last search's
  * picks, NONE units for a plane whose frame type is NONE); waits for an asynchronous search first. */
 int svtgpu_lr_read_units(SvtGpuLrState *s, int32_t plane, SvtGpuRestUnit *units_out, void *stream);
+/* Diagnostic read-back of the self-guided filter planes the last search of `s` left on the device (no reference
+ * counterpart: the reference keeps them in flt0 / flt1 of search_selfguided_restoration).  `slot` counts the eps the
+ * search tried on `plane`, in its order (0 .. their number - 1; with sg_filter_lvl 1 slot == ep); *ep_out receives the
+ * ep.  flt0 / flt1 (plane width x plane height int16 each, rows contiguous) receive g = flt - (dgd << 4) of the ep's
+ * r = 2 and r = 1 pass, every sample of the plane; a pass the ep does not have (sgr_params r == 0) leaves its array
+ * untouched.  Waits for an asynchronous search.  SVTGPU_ERR_INVALID_ARG: no search yet, none on this plane, or no
+ * such slot. */
+int svtgpu_lr_read_sgr_planes(SvtGpuLrState *s, int32_t plane, int32_t slot, int32_t *ep_out, int16_t *flt0,
+                              int16_t *flt1, void *stream);
 /* Per-unit part of the search for a band of unit rows: the units of unit rows [row_begin[p], row_end[p]) of each
  * searched plane (restoration_seg_search restricted to those units; every unit's search is independent of the
  * others).  Writes those units' records into search_out[p] (arrays of all units of the plane, row-major; other

@@ -41,6 +41,10 @@ struct SvtGpuLrState {
     int32_t             *h_fout, *h_fout_dev;
     int32_t              fin_seq, fin_pending;
     int32_t              last_ft[3];
+    // the self-guided filter planes the last search left in d_flt (svtgpu_lr_read_sgr_planes): per plane the base, row
+    // stride and size, the searched eps and the slot that holds each slot's r = 1 plane; sg_ne 0: none
+    int16_t             *sg_flt[3];
+    int32_t              sg_fstride[3], sg_w[3], sg_h[3], sg_ne[3], sg_eps[3][16], sg_f1e[3][16];
 };
 void lr_profiler_destroy(void *prof);
 int  lr_make_wiener_stream(SvtGpuLrState *s); // the search's Wiener-chain stream and its fork / join events

@@ -50,6 +50,7 @@ const int     kHostSgrR[16][2] = {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}
                               {2, 1}, {2, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 1}, {2, 0}, {2, 0}};
 // r = 1 s values of the sets (c_sgr_s[.][1]): eps 2/11, 5/12 and 8/13 share theirs, so their r = 1 filters are equal
 const int     kHostSgrS1[16] = {3236, 2158, 1618, 1438, 1295, 1177, 1079, 996, 925, 863, 2589, 1618, 1177, 925, -1, -1};
+const int     kHostSgrS0[16] = {140, 112, 93, 80, 70, 58, 47, 37, 30, 25, -1, -1, -1, -1, 56, 22}; // r = 2 (c_sgr_s[.][0])
 
 struct PlaneArgs {
     const void *dgd, *src;
@@ -59,6 +60,8 @@ struct PlaneArgs {
     int32_t     unit_base, pair_base, ne; // SGR pair of (unit, k) = pair_base + (unit - unit_base) * ne + k
     int32_t     eps[16];
     int32_t     f1e[16];                  // the ep slot whose r = 1 plane holds slot k's (equal s: same filter)
+    int32_t     es0[16], es1[16];         // sgr_flt_kernel: the s of slot k's r = 2 pass and of the r = 1 pass it
+                                          // builds (0: the ep has no such pass, or slot f1e[k] != k holds its r = 1 plane)
     int32_t     win, nval;                // Wiener window and statistics values per unit
     int64_t     mh_off;                   // this plane's statistics in the M/H buffer (int64 elements)
 };
@@ -390,36 +393,58 @@ __global__ void reduce_parts_kernel(const long long *part, const int32_t *unit_t
 
 // ---------------------------------------------------------------------------------------------
 // self-guided filters of every searched ep of a tile.  The 3x3 and 5x5 box sums do not depend on ep and stay in
-// registers; per ep the A/B maps (packed B << 9 | A) go to LDS and the filters to HBM as g = flt - (dgd << 4), the
-// projection's operand (int16: |g| < 2^15), so the resident search (sgr_res_kernel) needs no dgd to form it.
+// registers; per ep the A/B maps (packed B << 11 | 256 - A) go to LDS and the filters to HBM as g = flt - (dgd << 4),
+// the projection's operand (int16: |g| < 2^15), so the resident search (sgr_res_kernel) needs no dgd to form it.
 // ---------------------------------------------------------------------------------------------
 constexpr int SG_V = 70, SG_B = 66, SG_NT = 1024, SG_NQ = (SG_B * SG_B + SG_NT - 1) / SG_NT;
 constexpr int SG_NQ2 = ((SG_B + 1) / 2 * SG_B + SG_NT - 1) / SG_NT; // r = 2 map positions per lane (odd rows only)
+// The map word is B << 11 | Am, Am = 256 - A.  Am <= 255 and B <= (255 * 25575 * 164 + 2048) >> 12 = 261121 < 2^18, so
+// a sum of up to five words keeps both fields apart and inside 32 bits (Am part <= 1275 < 2^11, B part <= 1305605 <
+// 2^21): the filters add whole words per weight class (at most five: the r = 1 cross) and split each class sum once,
+// with one AND and one shift, instead of masking every word
+constexpr int      SG_AB = 11;
+constexpr uint32_t SG_AM = (1u << SG_AB) - 1;
 
 // A, B of a self-guided pass from its box sums with 24-bit multiplies where the operands provably fit:
-// b <= 25*1023 >> (bd-8) < 2^24; a*n <= 1.64e6*25 < 2^32 with a < 2^24; (256-A)*sum <= 255*25575 < 2^24 and
-// times one_by_x (<= 455) < 2^32.  Only p*s wraps like the reference's u32 product and keeps the full multiply.
-// Split in two so that a lane's table lookups (A = x_by_xplus1[z]) of all its positions are issued together:
-// sgr_z gives the clamped table index, sgr_ab_pack the packed map word (B << 9 | A).  sh = bd - 8.
-__device__ inline uint32_t sgr_z(int sum, int sq, int n, int s, int sh) {
+// b <= 25*1023 >> (bd-8) < 2^24; a*n <= 1.64e6*25 < 2^32 with a < 2^24; sum*one_by_x <= 25575*164 resp. 9207*455
+// < 2^24 and times (256-A) <= 255 < 2^32.  Only p*s wraps like the reference's u32 product and keeps the full multiply.
+// What does not depend on the ep is formed once per tile: sgr_p gives p = max(a*n - b*b, 0), and the lane keeps
+// sum*one_by_x in place of the sum.  Per ep sgr_z gives the clamped table index (the LDS table holds 256 - A) and
+// sgr_ab_pack the packed map word, split in two so that a lane's table lookups (x_by_xplus1[z]) of all its positions
+// are issued together.  sh = bd - 8.
+__device__ inline uint32_t sgr_p(int sum, int sq, int n, int sh) {
     const uint32_t a = (uint32_t)((sq + ((1 << (2 * sh)) >> 1)) >> (2 * sh));
     const uint32_t b = (uint32_t)((sum + ((1 << sh) >> 1)) >> sh);
     const uint32_t an = __umul24(a, (uint32_t)n), bb = __umul24(b, b);
-    const uint32_t p  = an < bb ? 0u : an - bb;
-    return min((p * (uint32_t)s + (1u << 19)) >> 20, 255u);
+    return an < bb ? 0u : an - bb;
 }
-__device__ inline int sgr_ab_pack(int A, int sum, int n) {
-    const int B = (int)((__umul24(__umul24((uint32_t)(256 - A), (uint32_t)sum), (uint32_t)c_one_by_x[n - 1]) + (1u << 11)) >> 12);
-    return (B << 9) | A;
+__device__ inline uint32_t sgr_z(uint32_t p, int s) { return min((p * (uint32_t)s + (1u << 19)) >> 20, 255u); }
+__device__ inline int sgr_ab_pack(int Am, uint32_t so) { // Am = 256 - A, so = sum * one_by_x[n - 1]
+    const uint32_t x = __umul24((uint32_t)Am, so) + (1u << 11); // B = x >> 12
+    return (int)(((x >> 1) & ~SG_AM) | (uint32_t)Am);
+}
+// One pixel of a filter from the word sums ca, cb of its two weight classes (weights WA, WB; all weights of a filter
+// sum to 2^(SH - 4)).  The words carry Am = 256 - A, so with npix = -pix
+//   sum_i w_i (Am_i npix + B_i) = sum_i w_i (A_i pix + B_i) - (pix << 4) << SH,
+// and the rounding shift leaves g = flt - (pix << 4) itself (the subtrahend is a multiple of 2^SH: the arithmetic
+// shift gives the same integer).  Per class |Am-part * pix| + B-part <= 1275 * 1023 + 1305605 < 2^23: the 24-bit
+// multiplies are exact
+template <int WA, int WB, int SH>
+__device__ inline int sgr_pixel(uint32_t ca, uint32_t cb, int npix) {
+    const int ma = __mul24((int)(ca & SG_AM), npix) + (int)(ca >> SG_AB);
+    const int mb = __mul24((int)(cb & SG_AM), npix) + (int)(cb >> SG_AB);
+    return (__mul24(ma, WA) + (__mul24(mb, WB) + (1 << (SH - 1)))) >> SH;
 }
 
+// two workgroups (32 waves) per CU, the LDS bound: 8 waves per SIMD, at most 64 VGPRs
 template <typename T>
-__global__ __launch_bounds__(SG_NT) void sgr_flt_kernel(const SearchArgs A, unsigned long long *tk) {
+__global__ __launch_bounds__(SG_NT) __attribute__((amdgpu_waves_per_eu(8))) void sgr_flt_kernel(const SearchArgs A,
+                                                                                                unsigned long long *tk) {
     PROF_BEGIN(tk);
-    // packed B << 9 | A (A <= 256, B < 2^19) of the r = 1 and r = 2 passes, double-buffered over eps: the maps of
-    // ep e + 1 are built while ep e is filtered, one barrier per ep
+    // packed B << 11 | 256 - A of the r = 1 and r = 2 passes, double-buffered over eps: the maps of ep e + 1 are built
+    // while ep e is filtered, one barrier per ep
     __shared__ int ab1[2][SG_B * SG_B], ab2[2][SG_B * SG_B];
-    __shared__ int      xby[256];
+    __shared__ int xby[256]; // 256 - x_by_xplus1
     // the tile with its 3-pixel border lives in ab1[1] until the box sums are taken (ab1[1] is first written by
     // build_ab(1), after the barrier that follows build_ab(0)): 70 KB of LDS, two workgroups per CU
     static_assert(SG_V * SG_V * 2 <= SG_B * SG_B * 4, "tile image fits the aliased map buffer");
@@ -431,7 +456,7 @@ __global__ __launch_bounds__(SG_NT) void sgr_flt_kernel(const SearchArgs A, unsi
         const int r = i / (t.w + 6), c = i % (t.w + 6);
         v[r * SG_V + c] = (uint16_t)px(d, P.dstride, P.W, P.H, t.y0 + r - 3, t.x0 + c - 3);
     }
-    if (threadIdx.x < 256) xby[threadIdx.x] = c_x_by_xplus1[threadIdx.x];
+    if (threadIdx.x < 256) xby[threadIdx.x] = 256 - c_x_by_xplus1[threadIdx.x];
     __syncthreads();
     const uint16_t *v0 = v + 3 * SG_V + 3;
     // The box sums read a row's 3 / 5 samples as aligned dword pairs and a funnel shift (sr_lds_pair) plus one 16-bit
@@ -443,8 +468,10 @@ __global__ __launch_bounds__(SG_NT) void sgr_flt_kernel(const SearchArgs A, unsi
     };
     const int       bw = t.w + 2, nq = (t.h + 2) * bw, nq2 = (t.h + 3) / 2 * bw;
     // the r = 1 map at every position q (map row q / bw = pixel row - 1 .. t.h); the r = 2 map only on the odd pixel
-    // rows (-1, 1, ..): dense position i -> map row 2 (i / bw), so no lane idles on the even rows
+    // rows (-1, 1, ..): dense position i -> map row 2 (i / bw), so no lane idles on the even rows.
+    // After the box sums s / q hold what the eps share: s the sum times one_by_x, q the variance term p (sgr_p)
     int s1[SG_NQ], q1[SG_NQ], s2[SG_NQ2], q2[SG_NQ2], m2q[SG_NQ2];
+    const int sh = P.bd - 8;
 #pragma unroll
     for (int k = 0; k < SG_NQ; k++) {
         const int q = threadIdx.x + k * SG_NT;
@@ -460,6 +487,7 @@ __global__ __launch_bounds__(SG_NT) void sgr_flt_kernel(const SearchArgs A, unsi
                 for (int j = 0; j < 3; j++) s1[k] += p[j], q1[k] += p[j] * p[j];
             }
         }
+        q1[k] = (int)sgr_p(s1[k], q1[k], 9, sh), s1[k] = (int)__umul24((uint32_t)s1[k], 455u); // one_by_x[8]
     }
 #pragma unroll
     for (int k = 0; k < SG_NQ2; k++) {
@@ -476,106 +504,111 @@ __global__ __launch_bounds__(SG_NT) void sgr_flt_kernel(const SearchArgs A, unsi
                 for (int j = 0; j < 5; j++) s2[k] += p[j], q2[k] += p[j] * p[j];
             }
         }
+        q2[k] = (int)sgr_p(s2[k], q2[k], 25, sh), s2[k] = (int)__umul24((uint32_t)s2[k], 164u); // one_by_x[24]
     }
-    // this lane's pixels: a column of 4 rows (fy0 .. fy0 + 3, fy0 even) at column fx, so the 3-wide map rows a filter
-    // reads are loaded and summed once for the column (6 rows for the r = 1 filter, 3 for r = 2) instead of once
-    // per pixel.  The division by the tile width is done once here, not per ep
-    const int fr = (int)threadIdx.x / t.w, fx = (int)threadIdx.x - fr * t.w, fy0 = 4 * fr;
-    const bool fon = fy0 < t.h;
-    int        pix[4];
+    // this lane's pixels: two columns (fx, fx + 1; fx even) of two rows (fy0, fy0 + 1; fy0 even), so the 4-wide map
+    // rows a filter reads are loaded once for the four pixels (4 rows for the r = 1 filter, 2 for r = 2) and the two
+    // samples of a row leave as one dword.  The division by the pair count is done once here, not per ep.  Lanes
+    // past the tile take pixel pair (0, 0) and store nothing
+    const int  cpn = (t.w + 1) >> 1, fr = (int)threadIdx.x / cpn;
+    const bool fon = 2 * fr < t.h;
+    const int  fx = fon ? 2 * ((int)threadIdx.x - fr * cpn) : 0, fy0 = fon ? 2 * fr : 0;
+    const bool row1 = fy0 + 1 < t.h, col1 = fx + 1 < t.w; // the pair's second row / column is inside the tile
+    int        npix[2][2];                                // the negated samples (sgr_pixel)
 #pragma unroll
-    for (int k = 0; k < 4; k++) pix[k] = fon && fy0 + k < t.h ? v0[(fy0 + k) * SG_V + fx] : 0;
-    const int   fq  = fx + 1;                                             // map column of the lane's pixels
-    const size_t fo = (size_t)(t.y0 + fy0) * P.fstride + t.x0 + fx;       // filter-plane offset of row fy0
-    const size_t pn = (size_t)P.fstride * P.H;
-    const int sh = P.bd - 8;
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 2; i++) npix[j][i] = -(int)v0[(fy0 + j) * SG_V + fx + i];
+    // map word offsets of the rows the lane reads, at the column left of fx: pixel rows fy0 - 1 .. fy0 + 2 (the last
+    // clamped to the map's last row t.h; its pixels are not stored then), clamped once here, not per ep
+    int mrow[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) mrow[j] = (min(fy0 - 1 + j, t.h) + 1) * bw + fx;
+    // byte offset of the lane's first row in a filter plane (all planes of a frame stay below 2^32 bytes: the
+    // pointers below are wave-uniform, the lane part is 32 bits)
+    const uint32_t fob = 2u * ((uint32_t)(t.y0 + fy0) * (uint32_t)P.fstride + (uint32_t)(t.x0 + fx));
+    const size_t   pn  = (size_t)P.fstride * P.H;
+    // es0 / es1: the s of the r = 2 pass and of the r = 1 pass slot e builds and filters (0: none, or another slot's)
     auto build_ab = [&](int e) { // A/B maps of ep index e into buffer e & 1
-        const int ep = P.eps[e], r0 = c_sgr_r[ep][0], r1 = c_sgr_r[ep][1];
+        const int sp0 = P.es0[e], sp1 = P.es1[e];
         int      *m1 = ab1[e & 1], *m2 = ab2[e & 1];
-        if (r1 && P.f1e[e] == e) { // r = 1 (3x3) at every map position
-            const int sp = c_sgr_s[ep][1];
-            uint32_t  z[SG_NQ];
-            int       a[SG_NQ];
+        if (sp1) { // r = 1 (3x3) at every map position
+            uint32_t z[SG_NQ];
+            int      a[SG_NQ];
 #pragma unroll
-            for (int k = 0; k < SG_NQ; k++) z[k] = sgr_z(s1[k], q1[k], 9, sp, sh);
+            for (int k = 0; k < SG_NQ; k++) z[k] = sgr_z((uint32_t)q1[k], sp1);
 #pragma unroll
             for (int k = 0; k < SG_NQ; k++) a[k] = xby[z[k]]; // the lookups in flight together
 #pragma unroll
             for (int k = 0; k < SG_NQ; k++) {
                 const int q = threadIdx.x + k * SG_NT;
-                if (q < nq) m1[q] = sgr_ab_pack(a[k], s1[k], 9);
+                if (q < nq) m1[q] = sgr_ab_pack(a[k], (uint32_t)s1[k]);
             }
         }
-        if (r0) { // r = 2 (5x5) on the odd rows
-            const int sp = c_sgr_s[ep][0];
-            uint32_t  z[SG_NQ2];
-            int       a[SG_NQ2];
+        if (sp0) { // r = 2 (5x5) on the odd rows
+            uint32_t z[SG_NQ2];
+            int      a[SG_NQ2];
 #pragma unroll
-            for (int k = 0; k < SG_NQ2; k++) z[k] = sgr_z(s2[k], q2[k], 25, sp, sh);
+            for (int k = 0; k < SG_NQ2; k++) z[k] = sgr_z((uint32_t)q2[k], sp0);
 #pragma unroll
             for (int k = 0; k < SG_NQ2; k++) a[k] = xby[z[k]];
 #pragma unroll
             for (int k = 0; k < SG_NQ2; k++)
-                if (m2q[k] >= 0) m2[m2q[k]] = sgr_ab_pack(a[k], s2[k], 25);
+                if (m2q[k] >= 0) m2[m2q[k]] = sgr_ab_pack(a[k], (uint32_t)s2[k]);
         }
+    };
+    // a map row's four words at the lane's columns: the word sums of the row triples of both pixels and their centres
+    struct Row { uint32_t s[2], c[2]; };
+    auto row = [&](const int *M, int j) {
+        const int     *Q  = M + mrow[j];
+        const uint32_t w0 = (uint32_t)Q[0], w1 = (uint32_t)Q[1], w2 = (uint32_t)Q[2], w3 = (uint32_t)Q[3];
+        Row            w;
+        w.c[0] = w1, w.c[1] = w2, w.s[0] = w0 + w1 + w2, w.s[1] = w1 + w2 + w3;
+        return w;
+    };
+    // the two samples of a row as one dword (fx, fstride and the tile origins are even: aligned); the unpaired last
+    // column of an odd-width plane as one int16, so nothing lands in the stride padding
+    auto store2 = [&](int16_t *plane_row, int g0, int g1) {
+        char *a = (char *)plane_row + fob;
+        if (col1)
+            *(uint32_t *)a = pack2(g0, g1);
+        else
+            *(int16_t *)a = (int16_t)g0;
     };
     build_ab(0);
     __syncthreads();
     for (int e = 0; e < P.ne; e++) {
         if (e + 1 < P.ne) build_ab(e + 1);
-        const int  ep = P.eps[e], r0 = c_sgr_r[ep][0], r1 = c_sgr_r[ep][1];
+        const int  sp0 = P.es0[e], sp1 = P.es1[e];
         const int *ab1e = ab1[e & 1], *ab2e = ab2[e & 1];
-        int16_t  *f0g = P.flt + (size_t)e * 2 * pn, *f1g = f0g + pn;
+        int16_t   *f0g = P.flt + (size_t)e * 2 * pn, *f1g = f0g + pn;
         if (fon) {
-            // 3-wide sums of map row ry (pixel-row coordinates -1 .. t.h; rows past the tile are clamped, their
-            // pixels are not stored): packed (B << 9 | A) and A-only sums of the row triple and of its centre
-            struct Row { int s, sa, c, ca; };
-            auto row = [&](const int *M, int ry) {
-                const int *Q = M + (min(ry, t.h) + 1) * bw + fq;
-                const int  l = Q[-1], c = Q[0], r = Q[1];
-                Row        w;
-                w.c = c, w.ca = c & 511, w.s = l + c + r, w.sa = (l & 511) + w.ca + (r & 511);
-                return w;
-            };
-            const int nk = min(4, t.h - fy0);
-            if (r0) { // r = 2 maps exist on odd rows: fy0 - 1, fy0 + 1, fy0 + 3
-                Row up = row(ab2e, fy0 - 1);
+            if (sp0) { // r = 2 maps exist on the odd rows fy0 - 1 and fy0 + 1
+                const Row up = row(ab2e, 0), dn = row(ab2e, 2);
+                int       g[2][2];
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int k = 2 * h;
-                    if (k >= nk) break;
-                    const Row dn = row(ab2e, fy0 + k + 1);
-                    { // even row fy0 + k: rows above and below, weights 6 (centres) and 5 (corners)
-                        const int c6 = up.c + dn.c, a6 = up.ca + dn.ca;
-                        const int c5 = up.s - up.c + dn.s - dn.c, a5 = up.sa - up.ca + dn.sa - dn.ca;
-                        const int aa = a6 * 6 + a5 * 5, bb = ((c6 - a6) >> 9) * 6 + ((c5 - a5) >> 9) * 5;
-                        f0g[fo + (size_t)k * P.fstride] =
-                            (int16_t)((((int)__umul24((uint32_t)aa, (uint32_t)pix[k]) + bb + (1 << 8)) >> 9) - (pix[k] << 4));
-                    }
-                    if (k + 1 < nk) { // odd row fy0 + k + 1: its own row, weights 6 (centre) and 5 (sides)
-                        const int a6 = dn.ca, a5 = dn.sa - dn.ca;
-                        const int aa = a6 * 6 + a5 * 5, bb = ((dn.c - a6) >> 9) * 6 + ((dn.s - dn.c - a5) >> 9) * 5;
-                        f0g[fo + (size_t)(k + 1) * P.fstride] =
-                            (int16_t)((((int)__umul24((uint32_t)aa, (uint32_t)pix[k + 1]) + bb + (1 << 7)) >> 8) -
-                                      (pix[k + 1] << 4));
-                    }
-                    up = dn;
+                for (int i = 0; i < 2; i++) {
+                    // even row fy0: the rows above and below, weights 6 (centres) and 5 (corners)
+                    const uint32_t c6 = up.c[i] + dn.c[i], c5 = up.s[i] + dn.s[i] - c6;
+                    g[0][i] = sgr_pixel<6, 5, 9>(c6, c5, npix[0][i]);
+                    // odd row fy0 + 1: its own row, weights 6 (centre) and 5 (sides)
+                    g[1][i] = sgr_pixel<6, 5, 8>(dn.c[i], dn.s[i] - dn.c[i], npix[1][i]);
                 }
+                store2(f0g, g[0][0], g[0][1]);
+                if (row1) store2(f0g + P.fstride, g[1][0], g[1][1]);
             }
-            if (r1 && P.f1e[e] == e) { // an ep sharing an earlier slot's r = 1 filter reads that plane
-                Row pv = row(ab1e, fy0 - 1), cu = row(ab1e, fy0);
+            if (sp1) { // an ep sharing an earlier slot's r = 1 filter reads that plane
+                const Row r0 = row(ab1e, 0), r1 = row(ab1e, 1), r2 = row(ab1e, 2), r3 = row(ab1e, 3);
+                int       g[2][2];
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    if (k >= nk) break;
-                    const Row nx = row(ab1e, fy0 + k + 1);
+                for (int i = 0; i < 2; i++) {
                     // weights 4: the row triple and the centres above/below; 3: the four corners
-                    const int c4 = cu.s + pv.c + nx.c, a4 = cu.sa + pv.ca + nx.ca;
-                    const int c3 = pv.s - pv.c + nx.s - nx.c, a3 = pv.sa - pv.ca + nx.sa - nx.ca;
-                    const int aa = a4 * 4 + a3 * 3, bb = ((c4 - a4) >> 9) * 4 + ((c3 - a3) >> 9) * 3;
-                    f1g[fo + (size_t)k * P.fstride] =
-                        (int16_t)((((int)__umul24((uint32_t)aa, (uint32_t)pix[k]) + bb + (1 << 8)) >> 9) - (pix[k] << 4));
-                    pv = cu, cu = nx;
+                    const uint32_t cn0 = r0.c[i] + r2.c[i], cn1 = r1.c[i] + r3.c[i];
+                    g[0][i] = sgr_pixel<4, 3, 9>(r1.s[i] + cn0, r0.s[i] + r2.s[i] - cn0, npix[0][i]);
+                    g[1][i] = sgr_pixel<4, 3, 9>(r2.s[i] + cn1, r1.s[i] + r3.s[i] - cn1, npix[1][i]);
                 }
+                store2(f1g, g[0][0], g[0][1]);
+                if (row1) store2(f1g + P.fstride, g[1][0], g[1][1]);
             }
         }
         __syncthreads(); // ep e + 2 rewrites this ep's buffer; ep e + 1's maps are complete
@@ -3168,9 +3201,19 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
                     break;
                 }
         }
+        for (int k = 0; k < pp[p].ne; k++) {
+            P.es0[k] = kHostSgrR[P.eps[k]][0] ? kHostSgrS0[P.eps[k]] : 0;
+            P.es1[k] = kHostSgrR[P.eps[k]][1] && P.f1e[k] == k ? kHostSgrS1[P.eps[k]] : 0;
+        }
         P.win = pp[p].win, P.nval = pp[p].nval, P.mh_off = (int64_t)pp[p].mh_off;
         P.dxp = pp[p].sg ? P.flt + (size_t)pp[p].ne * 2 * P.fstride * P.H : nullptr;
         if (pp[p].sg) flt_off += (size_t)(pp[p].ne * 2 + 1) * P.fstride * P.H;
+    }
+    for (int p = 0; p < 3; p++) { // what svtgpu_lr_read_sgr_planes reads back
+        const bool sg = p < nplanes && pp[p].sg;
+        s->sg_flt[p] = sg ? A.pl[p].flt : nullptr, s->sg_ne[p] = sg ? A.pl[p].ne : 0;
+        s->sg_fstride[p] = A.pl[p].fstride, s->sg_w[p] = A.pl[p].W, s->sg_h[p] = A.pl[p].H;
+        for (int k = 0; k < 16; k++) s->sg_eps[p][k] = A.pl[p].eps[k], s->sg_f1e[p][k] = A.pl[p].f1e[k];
     }
     A.tiles = (const Tile *)dp(o_tiles), A.units = (const URect *)dp(o_units), A.tile0 = (const int32_t *)dp(o_t0);
     auto *d_t0 = (int32_t *)dp(o_t0);
@@ -3808,6 +3851,26 @@ extern "C" int svtgpu_lr_read_units(SvtGpuLrState *s, int32_t plane, SvtGpuRestU
     const size_t n = (size_t)s->hunits[plane] * s->vunits[plane];
     HIP_TRY(hipMemcpyAsync(units_out, s->d_units[plane], sizeof(SvtGpuRestUnit) * n, hipMemcpyDeviceToHost, st));
     svtgpu_count_xfer(1, sizeof(SvtGpuRestUnit) * n);
+    HIP_TRY(hipStreamSynchronize(st));
+    return SVTGPU_OK;
+}
+
+extern "C" int svtgpu_lr_read_sgr_planes(SvtGpuLrState *s, int32_t plane, int32_t slot, int32_t *ep_out, int16_t *flt0,
+                                        int16_t *flt1, void *stream) {
+    if (!s || plane < 0 || plane > 2 || !ep_out || !flt0 || !flt1) return SVTGPU_ERR_INVALID_ARG;
+    if (!s->sg_flt[plane] || slot < 0 || slot >= s->sg_ne[plane]) return SVTGPU_ERR_INVALID_ARG;
+    hipStream_t st = pick_stream(s->ctx, stream);
+    if (s->fin_pending)
+        if (int rc = lr_collect(s, st, nullptr)) return rc;
+    const int    ep = s->sg_eps[plane][slot], W = s->sg_w[plane], H = s->sg_h[plane], fs = s->sg_fstride[plane];
+    const size_t pn = (size_t)fs * H;
+    *ep_out = ep;
+    if (kHostSgrR[ep][0])
+        HIP_TRY(hipMemcpy2DAsync(flt0, 2 * (size_t)W, s->sg_flt[plane] + (size_t)slot * 2 * pn, 2 * (size_t)fs, 2 * (size_t)W,
+                                 H, hipMemcpyDeviceToHost, st));
+    if (kHostSgrR[ep][1]) // the slot that holds this slot's r = 1 plane (equal s: one filter)
+        HIP_TRY(hipMemcpy2DAsync(flt1, 2 * (size_t)W, s->sg_flt[plane] + (size_t)s->sg_f1e[plane][slot] * 2 * pn + pn,
+                                 2 * (size_t)fs, 2 * (size_t)W, H, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return SVTGPU_OK;
 }

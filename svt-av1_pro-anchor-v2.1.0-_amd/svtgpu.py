@@ -556,6 +556,7 @@ _SIGS = {
     "svtgpu_lr_search_frame_async": (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(LrSearchControls), _P]),
     "svtgpu_lr_read_result": (ctypes.c_int, [_P, _P, _P]),
     "svtgpu_lr_read_units": (ctypes.c_int, [_P, _I32, _P, _P]),
+    "svtgpu_lr_read_sgr_planes": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(_I32), _P, _P, _P]),
     "svtgpu_lr_profile": (ctypes.c_int, [_P, _I32, _P]),
     "svtgpu_transfer_bytes": (ctypes.c_int, [_P, _P, _I32]),
     "svtgpu_comm_unique_id": (ctypes.c_int, [_P]),
@@ -1256,6 +1257,16 @@ class LrState:
         check(lib().svtgpu_lr_read_units(self.h, plane, ptr(u), stream))
         return u
 
+    def read_sgr_planes(self, plane, slot, stream=None):
+        """svtgpu_lr_read_sgr_planes: (ep, flt0, flt1) of ep slot `slot` of `plane` after a search: the int16 planes
+        g = flt - (dgd << 4) of the r = 2 and r = 1 pass (None for a pass the ep does not have)."""
+        w = (self.width + 1) >> 1 if plane else self.width
+        h = (self.height + 1) >> 1 if plane else self.height
+        f0, f1, ep = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16), _I32()
+        check(lib().svtgpu_lr_read_sgr_planes(self.h, plane, slot, ctypes.byref(ep), ptr(f0), ptr(f1), stream))
+        r0, r1 = SGR_RADII[ep.value]
+        return ep.value, f0 if r0 else None, f1 if r1 else None
+
     def read_result(self, stream=None):
         """svtgpu_lr_read_result: waits for the last asynchronous search and returns its frame types."""
         ft = np.zeros(3, np.int32)
@@ -1321,6 +1332,10 @@ class LrState:
             self.close()
         except Exception:
             pass
+
+
+# radii (r = 2 pass, r = 1 pass) of the 16 self-guided parameter sets (svt_aom_eb_sgr_params)
+SGR_RADII = [(2, 1)] * 10 + [(0, 1)] * 4 + [(2, 0)] * 2
 
 
 def lr_controls(wn_level, sg_level, rdmult=0, switchable=(0, 0, 0), wiener=(0, 0), sgrproj=(0, 0)):

@@ -261,6 +261,14 @@ def block_dist(src, ref, w, h, bd):
     return sad, sse.value, var
 
 
+def block_sse(src, ref, w, h, bd):
+    """svt_aom_sse_c / svt_aom_highbd_sse_c of one block: the 64-bit sum of squared differences."""
+    dt = np.uint16 if bd > 8 else np.uint8
+    s, r = np.ascontiguousarray(src, dt), np.ascontiguousarray(ref, dt)
+    fn = lib().oracle_sse16 if bd > 8 else lib().oracle_sse
+    return fn(ptr(s), s.shape[1], ptr(r), r.shape[1], w, h)
+
+
 def md_dist_batch(src_y, ref_ys, bd, mv, sb_range=None):
     """Batched MD distortion over all SBs (or SBs [b, e) of sb_range) / refs / shapes; returns uint32
     [nsb][nref][3][849]."""
@@ -347,6 +355,16 @@ def lr_controls(wn, sg, rdmult=0, switchable=(0, 0, 0), wiener=(0, 0), sgrproj=(
     for i, v in enumerate(sgrproj):
         c.sgrproj_restore_cost[i] = v
     return c
+
+
+def compute_stats(win, dgd, src, w, h, bd):
+    """svt_av1_compute_stats(_highbd)_c of the w x h unit at (4, 4) of two uint16 [h + 8][stride] planes (the border
+    holds the samples the window reads past the unit); returns (M [win^2], H [win^4]) int64."""
+    d, s = np.ascontiguousarray(dgd, np.uint16), np.ascontiguousarray(src, np.uint16)
+    assert d.shape == s.shape and d.shape[0] == h + 8 and d.shape[1] >= w + 8
+    M, H = np.zeros(win * win, np.int64), np.zeros(win ** 4, np.int64)
+    lib().oracle_compute_stats(win, ptr(d), ptr(s), d.shape[1], w, h, bd, ptr(M), ptr(H))
+    return M, H
 
 
 def lr_search_frame(rec, src, bd, unit_size, ctrls):

@@ -110,9 +110,13 @@ struct Planes { // the planes of one search launch: plane = plane0 + blockIdx.z 
     int32_t           strip; // rows per bins workgroup: 64 for pictures of many blocks (fewer, longer workgroups), else 32
 };
 
-// LDS cells: the count and the squared-error sum share one 64-bit word (count << 50 | sum of squares: a workgroup sees
-// at most 64 x 256 samples and 12-bit errors, so neither field overflows) and the error sum is kept biased by +4096 per
-// sample (non-negative, < 2^26); every sample costs at most two LDS atomics, fewer where lanes share a bin
+// LDS cells: the count and the squared-error sum share one 64-bit word (count << NQ_SHIFT | sum of squares).  A
+// workgroup sees at most 64 x 256 = 2^14 samples, all of which may fall in one bin (flat luma): the count then needs
+// 15 bits, exactly what is left above bit 49, and the squares of 10-bit errors sum to at most 2^14 * 1023^2 < 2^34,
+// far below 2^49.  The error sum is kept biased by +4096 per sample, so it is non-negative and at most
+// 2^14 * (1023 + 4096) = 83 869 696 < 2^27 in its uint32 (errors of +maxv and of -maxv on every sample of a one-bin
+// workgroup: tests/test_extreme_content_gpu.py); every sample costs at most two LDS atomics, fewer where lanes share
+// a bin
 constexpr int      NQ_SHIFT = 49;
 constexpr uint32_t S1_BIAS  = 4096;
 constexpr int      RUN      = 4; // wave-wide bin groups summed per step before the per-lane atomics

@@ -19,9 +19,10 @@
 //   tf_block_kernel / tf_central_kernel / tf_final_kernel: the per-block RTCD shims' kernels, one small launch each.
 //
 // Integer arithmetic follows the reference's types: uint32 wrap-around where its C has uint32, and the avg_err product
-// (combined >> 3) * (d_factor >> 3) is a 32-bit product (:1098).  OD_DIVU's table branch (count < 1024, that is, count ==
-// 1000: only the centre contributed) equals plain division for every accum the filter can form (the fixture's generator
-// checks all of them), so the normalisation divides.
+// (combined >> 3) * (d_factor >> 3) is a 32-bit product (:1098).  OD_DIVU's table branch (count < 1024: the centre's 1000
+// and references whose weights add up to at most 23) equals plain division for every accum the filter can form with such
+// a count (the fixtures' generators check them all: divisor 1000 in gen_golden_tf.c, 1000 .. 1023 in
+// gen_golden_tf_search.c --extreme), so the normalisation divides.
 //
 // Bounds: the frame kernel reads and writes the 64-aligned area only (the entry's contract), metadata index r * nblk +
 // block < n_refs * nblk; the noise kernel guards every row and column against h and w; the shim kernels index packed

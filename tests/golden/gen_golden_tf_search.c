@@ -59,6 +59,71 @@
  *   nchain, c<i>_par i32[6] {bd of the pictures, bd searched, set, mv_dist_th, tf_chroma, i}, c<i>_decay I[3], the records
  *             of the search as above with prefix c<i>, c<i>_err32p Q[2][6][4] (err32 after convert_64x64_info_to_32x32_info),
  *             c<i>_pred<r>_<p> the predictor pictures over the aligned area, c<i>_out<p> the filtered picture.
+ *
+ *   gen_golden_tf_search --extreme tests/golden/tf_extreme.bin    worst-case and all-tie content through the same walk,
+ *   replay and SIMD second pass; the filter records are made a second time through the _avx2 planewise / central / final
+ *   functions and must be equal.  The whole recipe, from the repository root after build() (REF = the reference checkout;
+ *   the objects and the binary go outside the repository):
+ *
+ *     S=$REF/Source; C=$S/Lib/Common; E=$S/Lib/Encoder; O=/tmp/tf_search_simd; mkdir -p $O
+ *     INC="-I$S/API -I$C/Codec -I$C/C_DEFAULT -I$E/Codec -I$E/C_DEFAULT -I$E/Globals -I$REF/third_party/fastfeat -I$REF \
+ *       -Ioracle/_ref/enc/gen"
+ *     SIMD="-O2 -mavx2 -ffunction-sections -fdata-sections -DARCH_X86_64=1 -w $INC -I$C/ASM_AVX2 -I$C/ASM_SSE2 -I$C/ASM_SSSE3 \
+ *       -I$C/ASM_SSE4_1"
+ *     for f in ASM_AVX2/convolve_avx2 ASM_AVX2/convolve_2d_avx2 ASM_AVX2/highbd_convolve_avx2 \
+ *         ASM_AVX2/highbd_convolve_2d_avx2 ASM_SSSE3/highbd_convolve_ssse3 ASM_SSSE3/highbd_convolve_2d_ssse3 \
+ *         ASM_SSE2/EbPictureOperators_Intrinsic_SSE2; do gcc $SIMD -c $C/$f.c -o $O/$(basename $f).o; done
+ *     for f in ASM_AVX2/variance_avx2 ASM_AVX2/highbd_variance_avx2 ASM_SSE2/variance_sse2 \
+ *         ASM_AVX2/EbTemporalFiltering_AVX2; do
+ *       gcc $SIMD -I$E/ASM_AVX2 -I$E/ASM_SSE2 -c $E/$f.c -o $O/$(basename $f).o; done
+ *     gcc -O2 -w -std=gnu99 -ffunction-sections $INC -Ioracle/ref_harness tests/golden/gen_golden_tf_search.c $O/*.o \
+ *       -o /tmp/gen_golden_tf_search -Wl,--gc-sections -Loracle/_ref/enc -lsvtenc -Wl,-rpath,$PWD/oracle/_ref/enc -lm -lpthread
+ *     /tmp/gen_golden_tf_search tests/golden/tf_search.bin
+ *     /tmp/gen_golden_tf_search --extreme tests/golden/tf_extreme.bin
+ *
+ *   (EbTemporalFiltering_AVX2.c is needed by --extreme alone; tf_search.bin is the same with or without it.)  The file
+ *   regenerates byte-identically; tests/tf_extreme_cases.py rebuilds the inputs.  The same geometry; every plane from a
+ *   formula of the plane's own picture coordinates (x, y) (chroma: the same formula at half size), maxv = 2^bd - 1:
+ *     content 0 max_zero    centre maxv; reference 0 all 0, reference 1 all maxv (the all-equal twin)
+ *             1 checker     centre (x + y) & 1 ? maxv : 0; the references its inverse
+ *             2 flat_ref    centre the drawn pictures' (above); the references 100 * sc everywhere
+ *             3 v_stripes   s(u) = ((u + 800) >> 2) & 1 ? maxv : 0; centre s(x), references s(x + 3)
+ *             4 h_stripes   centre s(y), references s(y + 3)
+ *             5 checker2    cells of 2 x 2: centre (((x + 800) >> 1) + ((y + 800) >> 1)) & 1 ? maxv : 0; references its inverse
+ *             6 near_max    centre maxv - (x & 1); the references all 0
+ *     full-pel MVs 0, but flat_ref's: level lvl (0: 64x64 .. 3: 8x8), index i, block b, reference r: ((i + b + r) % 5 - 2,
+ *     (i + 2 * b + lvl) % 3 - 1).
+ *   Records: nset; s<k>_* as above with s<k>_par[10] the class and [11] the content, at 8 and at 10 bits each:
+ *     class 0 max_zero            content 0, modes (1, 1, 1): sum^2 beyond 2^32 with variance 0, everything split to 8x8
+ *           1 inv_checker_pinned  content 1, modes (0, 0, 0): the start alone; 32x32 error 66 585 600 / 66 977 856
+ *           2 inv_checker_walk    content 5, eight rows over modes (1,1,1) / (2,2,2), use_2tap, sub_sampling_shift and
+ *                                 enable_8x8_pred (every pair of values of two switches occurs).  Content 1 was tried first:
+ *                                 no convolve form leaves the sample range on it, so no clip acts
+ *           3 flat_ref            content 2: all 25 positions tie on a non-zero best, the start stays
+ *           4 v_stripes, 5 h_stripes   contents 3, 4: positions that differ along the stripes tie
+ *           6 th32_wide           class 1 with pred_error_32x32_th = 2^32
+ *           7 near_max            content 6, modes (0, 0, 0): the 64x64 error decides use64.  At 10 bits the 64x64 sse is
+ *                                 4 282 394 624, in (2^31, 2^32), the sum 4 188 160, the error 64 against 4 x 16 for the 32x32
+ *                                 blocks: 64 * 14 < 64 * 16, so every block ends on the 64x64 path (checked)
+ *     The generator stops unless each set reaches its point (max_zero: all split, positions skipped by best == 0; pinned:
+ *     the stated errors and no split in the 32x32 blocks at x <= 96, y <= 32 -- further out the MV clamp moves the zero MV
+ *     of blocks that start more than 3 samples past the picture by whole samples, an odd move gives error 0, and parents
+ *     split; walk, stripes: the best moves; flat, stripes: ties; th32_wide: all 48 16x16 searches skipped).
+ *     nchain = 2, c<i>_* as above plus c<i>_force64: max_zero at 8 bits and the first row of inv_checker_walk at 10 bits
+ *     (searched at 10), tf_chroma 1, blocks (reference 0, 1) and (reference 1, 4) forced to the 64x64 path.
+ *     nfilter = 3, x<i>_par i32[6] {bd, w, h, n_refs, mv_dist_th, i}, x<i>_decay, x<i>_split / _mv32 / _mv16 / _err32 / _err16 as
+ *     gen_golden_tf.c's frame records, x<i>_out<p>, x<i>_wt H[nblk][n_refs][4][12] every quadrant's weight (count's increment;
+ *     [idx_32x32][plane * 4 + quadrant]), x<i>_wide B[..] 1 where (combined >> 3) * (d_factor >> 3) passes 2^32 (from the
+ *     reference's own pieces, as gen_golden_tf.c finds it), x<i>_occ i32[2][4] luma / chroma quadrants of weight 1000, of
+ *     weight 0, strictly between, wide.  Predictor pictures are given over the aligned area, no search:
+ *       x0 wide_frame  10 bits, 136x72, 3 predictors of a (x + y) & 1 checker centre: the centre; its inverse; the centre +
+ *                      draw(0x5458000000000000 + plane, i, 601) - 300, clamped.  mv_dist_th 16.  Reference 0: zero MVs, errors
+ *                      graded from 0; reference 1: MVs of 100 .. 240, d_factor >= 17 000; reference 2: MVs of +-16 383.  The
+ *                      generator stops unless all four occ counts are non-zero in luma and in chroma.
+ *       x1, x2 refs26  8 and 10 bits, 64x64, 26 predictors: even ones the checker centre, odd ones its inverse, zero MVs and
+ *                      errors: 13 weights of 1000 and 13 of 0 in every quadrant (checked), count 14 000.
+ *   Before the records the mode checks OD_DIVU_SMALL(x, d) == x / d for d = 1000 .. 1023 and every x <= d * 1023 + d / 2.
+ *   No input had to be left out: the reference's C took every one, and its AVX2 forms agree on all of them.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -654,9 +719,384 @@ static void time_reference(void) {
     }
 }
 
+/* ---- --extreme: tests/golden/tf_extreme.bin (the header lists the contents and the records) ---- */
+enum { XK_MAX_ZERO, XK_CHECKER, XK_FLAT, XK_VSTRIPE, XK_HSTRIPE, XK_CHECKER2, XK_NEAR_MAX, XK_N };
+enum { XC_MAX_ZERO, XC_PINNED, XC_WALK, XC_FLAT, XC_VSTRIPE, XC_HSTRIPE, XC_TH32, XC_NEAR_MAX };
+/* sample (x, y) of a plane, in the picture's coordinates of that plane; r < 0: the centre */
+static int xval(int kind, int r, int x, int y, int maxv, int sc) {
+    const int u = kind == XK_VSTRIPE ? x : y;
+    switch (kind) {
+    case XK_MAX_ZERO: return r == 0 ? 0 : maxv;
+    case XK_CHECKER: return ((x + y) & 1) == (r < 0) ? maxv : 0;
+    case XK_CHECKER2: return ((((x + 800) >> 1) + ((y + 800) >> 1)) & 1) == (r < 0) ? maxv : 0;
+    case XK_NEAR_MAX: return r < 0 ? maxv - (x & 1) : 0;
+    case XK_FLAT: return 100 * sc;
+    default: return ((u + (r < 0 ? 0 : 3) + 800) >> 2) & 1 ? maxv : 0;
+    }
+}
+static void make_extreme(Pics *p, int bd, int kind) {
+    const int sc = 1 << (bd - 8), maxv = (1 << bd) - 1;
+    make_pics(p, bd, 0); /* the allocations, and flat_ref's centre */
+    for (int k = 0; k < 3; k++) {
+        const int ss = k > 0, cw = AW >> ss, ch = AH >> ss, rs = RS >> ss, rh = RH >> ss, pad = PAD >> ss;
+        for (int y = 0; kind != XK_FLAT && y < ch; y++)
+            for (int x = 0; x < cw; x++) p->cen[k][y * cw + x] = (uint16_t)xval(kind, -1, x, y, maxv, sc), p->cen8[k][y * cw + x] = (uint8_t)p->cen[k][y * cw + x];
+        for (int r = 0; r < NR; r++)
+            for (int y = 0; y < rh; y++)
+                for (int x = 0; x < rs; x++)
+                    p->ref[r][k][y * rs + x] = (uint16_t)xval(kind, r, x - pad, y - pad, maxv, sc), p->ref8[r][k][y * rs + x] = (uint8_t)p->ref[r][k][y * rs + x];
+    }
+    /* full-pel MVs: 0, but flat_ref's, which the walk must leave as they are */
+    for (int r = 0; r < NR; r++)
+        for (int b = 0; b < NBLK; b++)
+            for (int lvl = 0; lvl < 4; lvl++)
+                for (int i = 0; i < 1 << (2 * lvl); i++) {
+                    const int rb = r * NBLK + b;
+                    int16_t  *dst = lvl == 0 ? p->fp64[rb] : lvl == 1 ? p->fp32[rb][i] : lvl == 2 ? p->fp16[rb][i] : p->fp8[rb][i];
+                    dst[0] = (int16_t)(kind == XK_FLAT ? (i + b + r) % 5 - 2 : 0), dst[1] = (int16_t)(kind == XK_FLAT ? (i + 2 * b + lvl) % 3 - 1 : 0);
+                }
+}
+
+/* the filter half on given predictor pictures, as gen_golden_tf.c walks it; every quadrant's weight (count's increment)
+ * and whether its avg_err product passes 2^32 are kept, [nblk][n_refs][idx_32x32][plane][quadrant] */
+typedef struct XMeta {
+    int32_t  split[4];
+    int16_t  mv32[4][2], mv16[16][2];
+    uint64_t err32[4], err16[16];
+} XMeta;
+extern __typeof__(svt_av1_apply_temporal_filter_planewise_medium_c)     svt_av1_apply_temporal_filter_planewise_medium_avx2;
+extern __typeof__(svt_av1_apply_temporal_filter_planewise_medium_hbd_c) svt_av1_apply_temporal_filter_planewise_medium_hbd_avx2;
+extern __typeof__(svt_aom_get_final_filtered_pixels_c)                  svt_aom_get_final_filtered_pixels_avx2;
+extern __typeof__(svt_aom_apply_filtering_central_c)                    svt_aom_apply_filtering_central_avx2;
+extern __typeof__(svt_aom_apply_filtering_central_highbd_c)             svt_aom_apply_filtering_central_highbd_avx2;
+static void bind_filter(int pass) {
+    svt_av1_apply_temporal_filter_planewise_medium = pass ? svt_av1_apply_temporal_filter_planewise_medium_avx2 : svt_av1_apply_temporal_filter_planewise_medium_c;
+    svt_av1_apply_temporal_filter_planewise_medium_hbd = pass ? svt_av1_apply_temporal_filter_planewise_medium_hbd_avx2 : svt_av1_apply_temporal_filter_planewise_medium_hbd_c;
+    get_final_filtered_pixels      = pass ? svt_aom_get_final_filtered_pixels_avx2 : svt_aom_get_final_filtered_pixels_c;
+    apply_filtering_central        = pass ? svt_aom_apply_filtering_central_avx2 : svt_aom_apply_filtering_central_c;
+    apply_filtering_central_highbd = pass ? svt_aom_apply_filtering_central_highbd_avx2 : svt_aom_apply_filtering_central_highbd_c;
+}
+static uint32_t xwindow(const uint16_t *s, int ss, const uint16_t *p, int ps, int hw, int bd) { /* window_error_quad_fp8 */
+    uint32_t sum = 0;
+    for (int y = 0; y < hw; y++)
+        for (int x = 0; x < hw; x++) {
+            const int df = s[y * ss + x] - p[y * ps + x];
+            sum += (uint32_t)(df * df);
+        }
+    sum >>= 2 * (bd - 8);
+    return (((sum << 4) / hw) << 4) / hw;
+}
+static void xfilter(int bd, int w, int h, uint16_t *cen[3], uint16_t *(*pred)[3], int nr, const XMeta *meta, const uint32_t *decay,
+                    int mv_dist_th, uint16_t *out[3], uint16_t *wt, uint8_t *wide) {
+    DECLARE_ALIGNED(32, uint32_t, accumulator[BLK_PELS * COLOR_CHANNELS]);
+    DECLARE_ALIGNED(32, uint16_t, counter[BLK_PELS * COLOR_CHANNELS]);
+    DECLARE_ALIGNED(32, uint16_t, pr16[BLK_PELS * COLOR_CHANNELS]);
+    DECLARE_ALIGNED(32, uint8_t, pr8[BLK_PELS * COLOR_CHANNELS]);
+    uint32_t *accum[3] = {accumulator, accumulator + BLK_PELS, accumulator + 2 * BLK_PELS};
+    uint16_t *count[3] = {counter, counter + BLK_PELS, counter + 2 * BLK_PELS};
+    uint16_t *pred16[3] = {pr16, pr16 + BLK_PELS, pr16 + 2 * BLK_PELS};
+    uint8_t  *pred8[3] = {pr8, pr8 + BLK_PELS, pr8 + 2 * BLK_PELS};
+    const int aw = (w + 63) & ~63, ah = (h + 63) & ~63, bcols = aw / 64, nblk = bcols * (ah / 64);
+    uint32_t  stride[3] = {aw, aw / 2, aw / 2}, stride_pred[3] = {BW, BW / 2, BW / 2};
+    MeContext *ctx = calloc(1, sizeof *ctx);
+    uint8_t   *c8[3], *o8[3];
+    EbPictureBufferDesc cdesc;
+    memset(&cdesc, 0, sizeof cdesc);
+    cdesc.stride_y = aw;
+    memcpy(ctx->tf_decay_factor_fp16, decay, 3 * sizeof(uint32_t));
+    ctx->tf_mv_dist_th = (uint16_t)mv_dist_th, ctx->tf_chroma = 1;
+    const uint32_t thr = AOMMAX((ctx->tf_mv_dist_th << 16) / 10, 1 << 16);
+    for (int k = 0; k < 3; k++) {
+        const size_t n = (size_t)(aw >> (k > 0)) * (ah >> (k > 0));
+        c8[k] = malloc(n), o8[k] = malloc(n);
+        memcpy(out[k], cen[k], n * 2);
+        for (size_t i = 0; i < n; i++) c8[k][i] = o8[k][i] = (uint8_t)cen[k][i];
+    }
+    for (int blk = 0; blk < nblk; blk++) {
+        const int yoff = (blk % bcols) * 64 + (blk / bcols) * 64 * aw, coff = (blk % bcols) * 32 + (blk / bcols) * 32 * (aw / 2);
+        uint8_t  *s8[3] = {c8[0] + yoff, c8[1] + coff, c8[2] + coff};
+        uint16_t *s16[3] = {cen[0] + yoff, cen[1] + coff, cen[2] + coff};
+        memset(accumulator, 0, sizeof accumulator), memset(counter, 0, sizeof counter);
+        if (bd == 8)
+            apply_filtering_central(ctx, &cdesc, s8, accum, count, BW, BH, 1, 1);
+        else
+            apply_filtering_central_highbd(ctx, &cdesc, s16, accum, count, BW, BH, 1, 1);
+        for (int r = 0; r < nr; r++) {
+            const XMeta *m = &meta[r * nblk + blk];
+            for (int k = 0; k < 3; k++) {
+                const int bw = k ? 32 : 64, st = aw >> (k > 0), off = k ? coff : yoff;
+                for (int y = 0; y < bw; y++)
+                    for (int x = 0; x < bw; x++) pred16[k][y * bw + x] = pred[r][k][off + y * st + x], pred8[k][y * bw + x] = (uint8_t)pred16[k][y * bw + x];
+            }
+            for (int i = 0; i < 4; i++) {
+                ctx->tf_32x32_block_split_flag[i] = m->split[i], ctx->tf_32x32_block_error[i] = m->err32[i];
+                ctx->tf_32x32_mv_x[i] = m->mv32[i][0], ctx->tf_32x32_mv_y[i] = m->mv32[i][1];
+            }
+            for (int i = 0; i < 16; i++)
+                ctx->tf_16x16_mv_x[i] = m->mv16[i][0], ctx->tf_16x16_mv_y[i] = m->mv16[i][1], ctx->tf_16x16_block_error[i] = m->err16[i];
+            for (int idx = 0; idx < 4; idx++) {
+                const int row = idx >> 1, col = idx & 1;
+                uint16_t  before[3][4];
+                uint32_t  lw[4];
+                uint16_t *wq = wt + (((size_t)blk * nr + r) * 4 + idx) * 12;
+                uint8_t  *dq = wide + (((size_t)blk * nr + r) * 4 + idx) * 12;
+                for (int k = 0; k < 3; k++)
+                    for (int q = 0; q < 4; q++) {
+                        const int bw = k ? 32 : 64, hw = bw / 4, o = (row * (bw / 2) + (q >> 1) * hw) * bw + col * (bw / 2) + (q & 1) * hw;
+                        const int so = (row * (bw / 2) + (q >> 1) * hw) * (aw >> (k > 0)) + col * (bw / 2) + (q & 1) * hw;
+                        before[k][q] = count[k][o];
+                        /* the product of :1093-1098 in 64 bits, from the reference's own pieces */
+                        uint32_t we = xwindow(s16[k] + so, aw >> (k > 0), pred16[k] + o, bw, hw, bd);
+                        if (!k) lw[q] = we;
+                        else we = (we * 5 + lw[q]) / 6;
+                        const int      sp = m->split[idx], mx = sp ? m->mv16[idx * 4 + q][0] : m->mv32[idx][0];
+                        const int      my = sp ? m->mv16[idx * 4 + q][1] : m->mv32[idx][1];
+                        const uint32_t d = AOMMAX((sqrt_fast(((uint32_t)(mx * mx + my * my)) << 8) << 12) / (thr >> 8), 1 << 8);
+                        const uint32_t be = sp ? (uint32_t)(m->err16[idx * 4 + q] >> (bd > 8 ? 4 : 0)) : (uint32_t)(m->err32[idx] >> (bd > 8 ? 6 : 2));
+                        const uint64_t comb = (uint32_t)(we * 5 + be) / 6;
+                        dq[k * 4 + q] = (comb >> 3) * (uint64_t)(d >> 3) >= ((uint64_t)1 << 32);
+                    }
+                ctx->tf_block_col = col, ctx->tf_block_row = row;
+                apply_filtering_block_plane_wise(ctx, row, col, s8, s16, pred8, pred16, accum, count, stride, stride_pred, BW >> 1, BH >> 1, 1, 1, bd);
+                for (int k = 0; k < 3; k++)
+                    for (int q = 0; q < 4; q++) {
+                        const int bw = k ? 32 : 64, hw = bw / 4, o = (row * (bw / 2) + (q >> 1) * hw) * bw + col * (bw / 2) + (q & 1) * hw;
+                        wq[k * 4 + q] = (uint16_t)(count[k][o] - before[k][q]);
+                    }
+            }
+        }
+        get_final_filtered_pixels(ctx, o8, out, accum, count, stride, yoff, coff, BW / 2, BH / 2, bd > 8);
+    }
+    for (int k = 0; k < 3; k++) {
+        const size_t n = (size_t)(aw >> (k > 0)) * (ah >> (k > 0));
+        for (size_t i = 0; bd == 8 && i < n; i++) out[k][i] = o8[k][i];
+        free(c8[k]), free(o8[k]);
+    }
+    free(ctx);
+}
+
+/* one filter record: both passes, compared; the counts of what the quadrants met into occ[2][4] (luma / chroma: weight 1000,
+ * weight 0, strictly between, product beyond 2^32) */
+static void put_filter(int i, int bd, int w, int h, uint16_t *cen[3], uint16_t *(*pred)[3], int nr, const XMeta *meta, const uint32_t *decay,
+                       int mv_dist_th, int32_t occ[2][4]) {
+    const int aw = (w + 63) & ~63, ah = (h + 63) & ~63, nblk = (aw / 64) * (ah / 64), nq = nblk * nr * 48;
+    uint16_t *out[2][3], *wt[2];
+    uint8_t  *wide[2];
+    for (int pass = 0; pass <= g_simd; pass++) {
+        for (int k = 0; k < 3; k++) out[pass][k] = calloc((size_t)(aw >> (k > 0)) * (ah >> (k > 0)), 2);
+        wt[pass] = calloc(nq, 2), wide[pass] = calloc(nq, 1);
+        bind_filter(pass);
+        xfilter(bd, w, h, cen, pred, nr, meta, decay, mv_dist_th, out[pass], wt[pass], wide[pass]);
+        bind_filter(0);
+        if (pass && memcmp(wt[0], wt[1], (size_t)nq * 2)) fprintf(stderr, "avx2 != c: filter %d weights\n", i), exit(3);
+        for (int k = 0; pass && k < 3; k++)
+            if (memcmp(out[0][k], out[1][k], (size_t)(aw >> (k > 0)) * (ah >> (k > 0)) * 2)) fprintf(stderr, "avx2 != c: filter %d plane %d\n", i, k), exit(3);
+    }
+    memset(occ, 0, 8 * sizeof(int32_t));
+    for (int q = 0; q < nq; q++) {
+        int32_t *o = occ[(q % 12) >= 4];
+        o[0] += wt[0][q] == 1000, o[1] += wt[0][q] == 0, o[2] += wt[0][q] > 0 && wt[0][q] < 1000, o[3] += wide[0][q];
+    }
+    int32_t   par[6] = {bd, w, h, nr, mv_dist_th, i};
+    int32_t  *sp = malloc(sizeof(int32_t) * 4 * nr * nblk);
+    int16_t  *m32 = malloc(sizeof(int16_t) * 8 * nr * nblk), *m16 = malloc(sizeof(int16_t) * 32 * nr * nblk);
+    uint64_t *e32 = malloc(sizeof(uint64_t) * 4 * nr * nblk), *e16 = malloc(sizeof(uint64_t) * 16 * nr * nblk);
+    for (int k = 0; k < nr * nblk; k++) {
+        memcpy(sp + 4 * k, meta[k].split, 16), memcpy(m32 + 8 * k, meta[k].mv32, 16), memcpy(m16 + 32 * k, meta[k].mv16, 64);
+        memcpy(e32 + 4 * k, meta[k].err32, 32), memcpy(e16 + 16 * k, meta[k].err16, 128);
+    }
+    put(nm("x", i, "par"), 'i', 1, 6, 0, 0, 0, par), put(nm("x", i, "decay"), 'I', 1, 3, 0, 0, 0, decay);
+    put(nm("x", i, "split"), 'i', 3, nr, nblk, 4, 0, sp), put(nm("x", i, "mv32"), 'h', 4, nr, nblk, 4, 2, m32);
+    put(nm("x", i, "mv16"), 'h', 4, nr, nblk, 16, 2, m16), put(nm("x", i, "err32"), 'Q', 3, nr, nblk, 4, 0, e32);
+    put(nm("x", i, "err16"), 'Q', 3, nr, nblk, 16, 0, e16);
+    put(nm("x", i, "wt"), 'H', 4, nblk, nr, 4, 12, wt[0]), put(nm("x", i, "wide"), 'B', 4, nblk, nr, 4, 12, wide[0]);
+    put(nm("x", i, "occ"), 'i', 2, 2, 4, 0, 0, occ);
+    for (int k = 0; k < 3; k++) {
+        char suf[16];
+        snprintf(suf, sizeof suf, "out%d", k);
+        put_plane(nm("x", i, suf), bd, h >> (k > 0), w >> (k > 0), out[0][k], aw >> (k > 0));
+    }
+    fprintf(stderr, "filter %d (%d bits, %d references): luma %d %d %d %d, chroma %d %d %d %d\n", i, bd, nr, occ[0][0], occ[0][1], occ[0][2],
+            occ[0][3], occ[1][0], occ[1][1], occ[1][2], occ[1][3]);
+    free(sp), free(m32), free(m16), free(e32), free(e16);
+    for (int pass = 0; pass <= g_simd; pass++) {
+        for (int k = 0; k < 3; k++) free(out[pass][k]);
+        free(wt[pass]), free(wide[pass]);
+    }
+}
+
+static int extreme(const char *path) {
+    GoldenFile g = golden_open(path);
+    g_file       = &g;
+    setup_reference();
+    /* OD_DIVU_SMALL against plain division for every divisor below OD_DIVU_DMAX a count can be (1000 .. 1023: the centre
+     * and references of small weight) and every accum + (count >> 1) a 10-bit picture can form with it */
+    for (uint32_t d = 1000; d < 1024; d++)
+        for (uint32_t x = 0; x <= d * 1023u + (d >> 1); x++)
+            if (OD_DIVU_SMALL(x, d) != x / d) fprintf(stderr, "OD_DIVU_SMALL(%u, %u) differs from the quotient\n", x, d), exit(3);
+    static const struct { int cls, kind; } rows[] = {{XC_MAX_ZERO, XK_MAX_ZERO}, {XC_PINNED, XK_CHECKER}, {XC_WALK, XK_CHECKER2}, {XC_FLAT, XK_FLAT},
+                                                     {XC_VSTRIPE, XK_VSTRIPE}, {XC_HSTRIPE, XK_HSTRIPE}, {XC_TH32, XK_CHECKER}, {XC_NEAR_MAX, XK_NEAR_MAX}};
+    static Pics pics[2][XK_N];
+    for (int d = 0; d < 2; d++)
+        for (int k = 0; k < XK_N; k++) make_extreme(&pics[d][k], d ? 10 : 8, k);
+    int  nset = 0, chain_set[2] = {-1, -1};
+    Set  chain_s[2];
+    for (size_t row = 0; row < sizeof rows / sizeof rows[0]; row++)
+        for (int d = 0; d < 2; d++)
+            for (int v = 0; v < (rows[row].cls == XC_WALK ? 8 : 1); v++) {
+                const int bd = d ? 10 : 8, cls = rows[row].cls, kind = rows[row].kind;
+                Pics     *p = &pics[d][kind];
+                Set       s;
+                memset(&s, 0, sizeof s);
+                s.mode[0] = s.mode[1] = s.mode[2] = 1, s.enable8 = 1;
+                if (cls == XC_PINNED || cls == XC_TH32 || cls == XC_NEAR_MAX) s.mode[0] = s.mode[1] = s.mode[2] = 0;
+                if (cls == XC_TH32) s.th32 = (uint64_t)1 << 32;
+                if (cls == XC_WALK) { /* the eight rows of the orthogonal array over the four switches */
+                    const int m = v & 1, t = v >> 1 & 1, sh = v >> 2 & 1;
+                    s.mode[0] = s.mode[1] = s.mode[2] = 1 + m, s.use_2tap = t, s.shift = sh, s.enable8 = !(m ^ t ^ sh);
+                }
+                Out     out[NR * NBLK];
+                int32_t kinds[NK] = {0}, par[12] = {bd, s.mode[0], s.mode[1], s.mode[2], s.use_2tap, s.shift, s.enable8, 0, NR, PAD, cls, kind};
+                int     dummy = 0;
+                static uint64_t pp_sink[2 * 6 * 85];
+                run_picture(p, &s, bd, bd, out, kinds, NULL, NULL, pp_sink, &dummy, NULL, NULL, NULL);
+                run_simd_check(p, &s, bd, bd, out, "extreme set", nset);
+                /* what the content is there for */
+                int n64 = 0, nsp32 = 0, nsp16 = 0, moved = 0;
+                for (int k = 0; k < NR * NBLK; k++) {
+                    n64 += out[k].use64;
+                    for (int i = 0; i < 4; i++) nsp32 += out[k].split32[i], moved += !out[k].split32[i] && (out[k].mv32[i][0] || out[k].mv32[i][1]);
+                    for (int i = 0; i < 16; i++) nsp16 += out[k].split16[i];
+                }
+                int ok = 1;
+                if (cls == XC_MAX_ZERO) ok = !n64 && nsp32 == NR * NBLK * 4 && nsp16 == NR * NBLK * 16 && kinds[11] > 0;
+                if (cls == XC_PINNED) { /* the 32x32 blocks none of whose sub-blocks the MV clamp moves: x <= 96, y <= 32 */
+                    ok = !n64;
+                    for (int k = 0; k < NR * NBLK; k++)
+                        for (int i = 0; i < 4; i++)
+                            if ((k % NBLK % BCOLS) * 64 + (i & 1) * 32 <= 96 && (k % NBLK / BCOLS) * 64 + (i >> 1) * 32 <= 32)
+                                ok &= !out[k].split32[i] && out[k].err32[i] == (d ? 66977856u : 66585600u);
+                }
+                if (cls == XC_TH32) ok = !n64 && !nsp32 && kinds[6] == NR * NBLK * 4;
+                if (cls == XC_WALK) ok = kinds[7] > 0 && moved > 0;
+                if (cls == XC_NEAR_MAX) ok = n64 == NR * NBLK && kinds[0] == NR * NBLK;
+                if (cls == XC_FLAT) ok = kinds[12] > 0 && !kinds[7] && !kinds[8] && !kinds[9];
+                if (cls == XC_VSTRIPE || cls == XC_HSTRIPE) ok = kinds[12] > 0 && kinds[7] > 0;
+                if (!ok) fprintf(stderr, "extreme set %d (class %d, %d bits) does not reach its point: %d use64, %d split32, %d split16, err32 %llu\n", nset, cls, bd, n64, nsp32, nsp16, (unsigned long long)out[0].err32[0]), exit(3);
+                put(nm("s", nset, "par"), 'i', 1, 12, 0, 0, 0, par);
+                put(nm("s", nset, "th32"), 'Q', 1, 1, 0, 0, 0, &s.th32);
+                put(nm("s", nset, "force64"), 'B', 2, NR, NBLK, 0, 0, s.force64);
+                put(nm("s", nset, "kinds"), 'i', 1, NK, 0, 0, 0, kinds);
+                put_outs("s", nset, out);
+                fprintf(stderr, "%2d bits class %d kind %d:", bd, cls, kind);
+                for (int k = 0; k < NK; k++) fprintf(stderr, " %d", kinds[k]);
+                fprintf(stderr, "\n");
+                /* the chains' parameter sets: max_zero at 8 bits, the default row of the walk at 10 */
+                if ((cls == XC_MAX_ZERO && !d) || (cls == XC_WALK && d && v == 0)) chain_set[d] = nset, chain_s[d] = s;
+                nset++;
+            }
+    int32_t ns = nset;
+    put("nset", 'i', 1, 1, 0, 0, 0, &ns);
+    /* the chains, tf_chroma 1: one block of each reference forced to the 64x64 path */
+    static const uint32_t decay[3] = {6000000, 9000000, 12000000};
+    for (int c = 0; c < 2; c++) {
+        const int bd = c ? 10 : 8;
+        Pics     *p = &pics[c][c ? XK_CHECKER2 : XK_MAX_ZERO];
+        Set      *s = &chain_s[c];
+        s->force64[0][1] = s->force64[1][4] = 1;
+        Out       out[NR * NBLK];
+        int32_t   kinds[NK] = {0}, par[6] = {bd, bd, chain_set[c], 1080, 1, c};
+        uint16_t *predpic[NR][3], *filt[3];
+        uint64_t  pp_sink[NR * NBLK * 85], e32p[NR * NBLK * 4];
+        int       dummy = 0;
+        for (int k = 0; k < 3; k++) {
+            const size_t n = (size_t)(AW >> (k > 0)) * (AH >> (k > 0));
+            filt[k] = calloc(n, 2);
+            for (int r = 0; r < NR; r++) predpic[r][k] = calloc(n, 2);
+        }
+        run_picture(p, s, bd, bd, out, kinds, NULL, NULL, pp_sink, &dummy, predpic, filt, decay);
+        run_simd_check(p, s, bd, bd, out, "extreme chain", c);
+        if (!out[1].use64 || !out[NBLK + 4].use64) fprintf(stderr, "extreme chain %d: no forced block\n", c), exit(3);
+        for (int k = 0; k < NR * NBLK; k++) memcpy(e32p + 4 * k, out[k].err32p, 32);
+        put(nm("c", c, "par"), 'i', 1, 6, 0, 0, 0, par), put(nm("c", c, "decay"), 'I', 1, 3, 0, 0, 0, decay);
+        put(nm("c", c, "force64"), 'B', 2, NR, NBLK, 0, 0, s->force64);
+        put_outs("c", c, out);
+        put(nm("c", c, "err32p"), 'Q', 3, NR, NBLK, 4, 0, e32p);
+        for (int r = 0; r < NR; r++)
+            for (int k = 0; k < 3; k++) {
+                char suf[16];
+                snprintf(suf, sizeof suf, "pred%d_%d", r, k);
+                put_plane(nm("c", c, suf), bd, AH >> (k > 0), AW >> (k > 0), predpic[r][k], AW >> (k > 0));
+            }
+        for (int k = 0; k < 3; k++) {
+            char suf[16];
+            snprintf(suf, sizeof suf, "out%d", k);
+            put_plane(nm("c", c, suf), bd, H >> (k > 0), W >> (k > 0), filt[k], AW >> (k > 0));
+        }
+    }
+    int32_t nc = 2;
+    put("nchain", 'i', 1, 1, 0, 0, 0, &nc);
+    /* the filter records: wide_frame, refs26 at 8 and 10 bits */
+    for (int f = 0; f < 3; f++) {
+        const int bd = f == 1 ? 8 : 10, w = f ? 64 : W, h = f ? 64 : H, nr = f ? 26 : 3, aw = (w + 63) & ~63, ah = (h + 63) & ~63;
+        const int nblk = (aw / 64) * (ah / 64), maxv = (1 << bd) - 1, th = f ? 1080 : 16;
+        uint16_t *cen[3], *(*pred)[3] = calloc(nr, sizeof *pred);
+        XMeta    *meta = calloc((size_t)nr * nblk, sizeof *meta);
+        for (int k = 0; k < 3; k++) {
+            const int cw = aw >> (k > 0), ch = ah >> (k > 0);
+            cen[k] = malloc(sizeof(uint16_t) * cw * ch);
+            for (int r = 0; r < nr; r++) pred[r][k] = malloc(sizeof(uint16_t) * cw * ch);
+            for (int y = 0; y < ch; y++)
+                for (int x = 0; x < cw; x++) {
+                    const int v = (x + y) & 1 ? maxv : 0, i = y * cw + x;
+                    cen[k][i] = (uint16_t)v;
+                    for (int r = 0; r < nr; r++)
+                        pred[r][k][i] = (uint16_t)(f ? (r & 1 ? maxv - v : v)
+                                                     : r == 0 ? v : r == 1 ? maxv - v
+                                                              : clampi(v + (int)draw(0x5458000000000000ull + k, (uint64_t)i, 601) - 300, 0, maxv));
+                }
+        }
+        /* wide_frame's metadata: reference 0 (the centre) has errors graded from 0 so that its weights run from 1000 down,
+         * reference 1 (full range) MVs of 100 to 240 eighths, whose d_factor of 17 000 and more takes the product past 2^32,
+         * reference 2 MVs of +-16 383, where (col^2 + row^2) << 8 wraps 32 bits */
+        for (int r = 0; !f && r < nr; r++)
+            for (int b = 0; b < nblk; b++) {
+                XMeta *m = &meta[r * nblk + b];
+                for (int i = 0; i < 4; i++) {
+                    m->split[i] = (b + i + r) & 1;
+                    m->err32[i] = r == 0 ? (uint64_t)((b * 4 + i) % 8) * 8000000 : r == 1 ? 1000000 : 4000000;
+                    m->mv32[i][0] = (int16_t)(r == 0 ? 0 : r == 1 ? 100 + 20 * i : (i & 1 ? -16383 : 16383));
+                    m->mv32[i][1] = (int16_t)(r == 0 ? 0 : r == 1 ? -(120 + 10 * b) : (b & 1 ? 16383 : -16383));
+                }
+                for (int i = 0; i < 16; i++) {
+                    m->err16[i] = r == 0 ? (uint64_t)((b + i) % 8) * 1000000 : r == 1 ? 300000 : 1000000;
+                    m->mv16[i][0] = (int16_t)(r == 0 ? 0 : r == 1 ? 110 + 8 * i : (i & 2 ? 16383 : -16383));
+                    m->mv16[i][1] = (int16_t)(r == 0 ? 0 : r == 1 ? 130 - 4 * i : (i & 1 ? 16383 : -16383));
+                }
+            }
+        int32_t occ[2][4];
+        put_filter(f, bd, w, h, cen, pred, nr, meta, decay, th, occ);
+        for (int c = 0; c < 2; c++)
+            for (int k = 0; k < (f ? 2 : 4); k++)
+                if (!occ[c][k]) fprintf(stderr, "filter %d: %s count %d is zero\n", f, c ? "chroma" : "luma", k), exit(3);
+        if (f && (occ[0][0] != 13 * 16 || occ[0][1] != 13 * 16)) fprintf(stderr, "filter %d: not 13 + 13\n", f), exit(3);
+        for (int k = 0; k < 3; k++) {
+            free(cen[k]);
+            for (int r = 0; r < nr; r++) free(pred[r][k]);
+        }
+        free(pred), free(meta);
+    }
+    int32_t nf = 3;
+    put("nfilter", 'i', 1, 1, 0, 0, 0, &nf);
+    golden_close(&g);
+    fprintf(stderr, "%d search records, 2 chain records, 3 filter records; %s\n", nset,
+            g_simd ? "every record equal with the convolve, variance and filter pointers on the SIMD functions" : "no AVX2 on this host: the _c functions only");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <out.bin> | --time\n", argv[0]);
+        fprintf(stderr, "usage: %s <out.bin> | --extreme <out.bin> | --time\n", argv[0]);
         return 2;
     }
     g_simd = __builtin_cpu_supports("avx2") ? 1 : 0;
@@ -665,6 +1105,7 @@ int main(int argc, char **argv) {
         time_reference();
         return 0;
     }
+    if (!strcmp(argv[1], "--extreme") && argc > 2) return extreme(argv[2]);
     GoldenFile g = golden_open(argv[1]);
     g_file       = &g;
     setup_reference();

@@ -46,21 +46,22 @@ def _rnd(v, n):  # ROUND_POWER_OF_TWO on signed values: an arithmetic shift
     return (v + ((1 << n) >> 1)) >> n
 
 
-def convolve(win, w, h, fx, fy, form, bd):
+def convolve(win, w, h, fx, fy, form, bd, clip=True):
     """One block.  `win` is the (h + 7) x (w + 7) window with the block at (3, 3); fx / fy the 8-tap rows; form 0 copy, 1 x,
-    2 y, 3 2d."""
+    2 y, 3 2d.  clip=False (tests only) leaves out the final clip to the sample range."""
     win = np.asarray(win, dtype=np.int64)
     fx, fy = np.asarray(fx, dtype=np.int64), np.asarray(fy, dtype=np.int64)
     r0, r1 = rounds(bd)
     maxv = (1 << bd) - 1
+    lo, maxv = (0, maxv) if clip else (-(1 << 62), 1 << 62)
     if form == 0:
         return win[3:3 + h, 3:3 + w].copy()
     if form == 1:
         s = sum(fx[k] * win[3:3 + h, k:k + w] for k in range(8))
-        return np.clip(_rnd(_rnd(s, r0), 7 - r0), 0, maxv)
+        return np.clip(_rnd(_rnd(s, r0), 7 - r0), lo, maxv)
     if form == 2:
         s = sum(fy[k] * win[k:k + h, 3:3 + w] for k in range(8))
-        return np.clip(_rnd(s, 7), 0, maxv)
+        return np.clip(_rnd(s, 7), lo, maxv)
     im = (1 << (bd + 6)) + sum(fx[k] * win[:, k:k + w] for k in range(8))
     im = _rnd(im, r0).astype(np.int16).astype(np.int64)
     ob = bd + 14 - r0
@@ -68,7 +69,7 @@ def convolve(win, w, h, fx, fy, form, bd):
     res = _rnd(s, r1) - ((1 << (ob - r1)) + (1 << (ob - r1 - 1)))
     if bd == 8:
         res = res.astype(np.int16).astype(np.int64)
-    return np.clip(_rnd(res, 14 - r0 - r1), 0, maxv)
+    return np.clip(_rnd(res, 14 - r0 - r1), lo, maxv)
 
 
 def block_source(bd, w, h, content, index):

@@ -104,9 +104,11 @@ def cost_tables(it, joint, comp_row, comp_col):
     return np.array(list(joint) + rows + cols, np.int32)
 
 
-def walk(padded, pad, it, wsrc, mask, cost):
+def walk(padded, pad, it, wsrc, mask, cost, neighbors=None):
     """svt_av1_obmc_full_pixel_search (av1me.c:721-776) of one item: (col, row, best_sad, variance, sse, moves).
-    it: dict of PAR fields (frame / errorperbit unused); cost: the item's tables (cost_mode 1) or None."""
+    it: dict of PAR fields (frame / errorperbit unused); cost: the item's tables (cost_mode 1) or None.  neighbors (tests
+    only): another order of the eight sites than the reference's."""
+    neighbors = NEIGHBORS if neighbors is None else neighbors
     w, h, R = it["w"], it["h"], it["search_range"]
     fr, fc = it["ref_mv_row"] >> 3, it["ref_mv_col"] >> 3
     sr = min(max(it["mvp_row"], it["row_min"]), it["row_max"])
@@ -129,7 +131,7 @@ def walk(padded, pad, it, wsrc, mask, cost):
     best = (obmc_sad(pre(row, col), wsrc, mask) + mv_cost(row, col)) & 0xFFFFFFFF
     for _ in range(R):
         site = -1
-        for j, (nr, nc) in enumerate(NEIGHBORS[:8 if it["search_diag"] else 4]):
+        for j, (nr, nc) in enumerate(neighbors[:8 if it["search_diag"] else 4]):
             r, c = row + nr, col + nc
             if not (it["col_min"] <= c <= it["col_max"] and it["row_min"] <= r <= it["row_max"]):
                 continue
@@ -140,7 +142,7 @@ def walk(padded, pad, it, wsrc, mask, cost):
                     best, site = sad, j
         if site < 0:
             break
-        row, col, moves = row + NEIGHBORS[site][0], col + NEIGHBORS[site][1], moves + 1
+        row, col, moves = row + neighbors[site][0], col + neighbors[site][1], moves + 1
     var, sse = obmc_variance(pre(row, col), wsrc, mask)
     return col, row, best, var, sse, moves
 
@@ -198,6 +200,67 @@ def mixed_batch(seed=0x0B3C):
         masks.append(mask)
         costs.append(cost_tables(it, joint, comp[0], comp[1]) if mode else None)
     return frames, items, wsrcs, masks, costs
+
+
+# ---- tie and full-magnitude content for the device test: 192 x 136 ------------------------------------------------------
+EXTREME_SIZES = [(4, 4), (16, 16), (64, 64), (128, 128)]
+CORNER_X, CORNER_Y = 150, 130  # full magnitude: the frame is 255 from here to its far corner, 0 elsewhere
+SWAPPED = {"v_stripes": [NEIGHBORS[k] for k in (0, 2, 1, 3, 4, 5, 6, 7)],  # the tied pair (0, -1) / (0, 1) swapped
+           "h_stripes": [NEIGHBORS[k] for k in (3, 1, 2, 0, 4, 5, 6, 7)]}  # the tied pair (-1, 0) / (1, 0) swapped
+
+
+def extreme_batch():
+    """(frames [4] u8 (136, 192), items, wsrc list, mask list, cost list, kinds): 24 items of the sizes 4x4, 16x16, 64x64 and
+    128x128, both cost modes, search_diag 0 (range 8) and 1 (range 16).  One frame per content (the batch takes up to 8):
+      flat (frame 0, all 128): every neighbour's SAD equals the start's; the start is the centre of the MV cost
+        (ref_mv = 8 * the clamped start), so no neighbour is cheaper either: 0 steps, the result is the clamped start.
+        Every second item's mvp lies outside its limits.
+      v_stripes / h_stripes (frames 1, 2: period 4, two samples of 255 and two of 0), wsrc = 4096 * the frame displaced by
+        2 samples (half a period) across the stripes, mask 4096, start = ref_mv = 0: the start sees the inverse, the two
+        neighbours across the stripes see half of it and tie, in SAD and in cost; the first in NEIGHBORS order takes over
+        and the next step ends on SAD 0, two samples to that side.  (The neighbours along the stripes tie too, with each
+        other and with the position itself, but cost more than it: they never take over.)
+      full (frame 3: 0, but 255 at x >= CORNER_X, y >= CORNER_Y), wsrc = WSRC_MAX, mask 4096: SAD = sum of 255 - pre.  The
+        block starts with its last row just above the corner, 255 * w * h exactly (128x128: 4 177 920), its columns
+        overlapping the corner's, so every step down takes 255 * overlap off.  With cost mode 1 the tables are times 1024
+        and sad_per_bit is 6000: bits * sad_per_bit passes 2^32 and wraps as the reference's unsigned product does."""
+    W, H = 192, 136
+    yy, xx = np.mgrid[0:H, 0:W]
+    frames = [np.full((H, W), 128, np.uint8), (((xx >> 1) & 1) * 255).astype(np.uint8), (((yy >> 1) & 1) * 255).astype(np.uint8),
+              np.where((xx >= CORNER_X) & (yy >= CORNER_Y), 255, 0).astype(np.uint8)]
+    rng = np.random.default_rng(0x0B3D)
+    joint = [310, 1187, 1243, 1920]
+    v = np.arange(MV_LOW, MV_UPP + 1)
+    comp = [(400 + 37 * np.floor(np.log2(np.abs(v) + 1)) * 8 + (np.abs(v) * (13 + 4 * c)) % 29).astype(np.int64) for c in range(2)]
+    items, wsrcs, masks, costs, kinds = [], [], [], [], []
+
+    def add(kind, frame, x, y, w, h, mvp, ref_mv, lim, mode, diag, wsrc, mask, spb=60, scale=1):
+        it = dict(frame=frame, x=x, y=y, w=w, h=h, mvp_col=mvp[0], mvp_row=mvp[1], ref_mv_col=ref_mv[0], ref_mv_row=ref_mv[1],
+                  col_min=lim[0], col_max=lim[1], row_min=lim[2], row_max=lim[3], sad_per_bit=spb, search_range=16 if diag else 8,
+                  search_diag=diag, cost_mode=mode, errorperbit=0)
+        items.append(it), wsrcs.append(wsrc.astype(np.int32)), masks.append(mask.astype(np.int32)), kinds.append(kind)
+        costs.append(cost_tables(it, [j * scale for j in joint], comp[0] * scale, comp[1] * scale) if mode else None)
+
+    for k, (w, h) in enumerate(EXTREME_SIZES):
+        for mode in (0, 1):
+            diag, n = (k + mode) & 1, len(items)
+            mvp, lim = ((5 - k, k - 3), (-20, 19, -18, 20)) if n & 1 == 0 else ((60 + k, -70), (-20, 19, -18, 20))
+            start = (min(max(mvp[0], lim[0]), lim[1]), min(max(mvp[1], lim[2]), lim[3]))
+            mask = rng.integers(1024, 4097, (h, w))
+            add("flat", 0, 32, 4, w, h, mvp, (8 * start[0], 8 * start[1]), lim, mode, diag,
+                np.clip(128 * mask + rng.integers(-90000, 90001, (h, w)), 0, WSRC_MAX), mask)
+    for kind, frame in (("v_stripes", 1), ("h_stripes", 2)):
+        for k, (w, h) in enumerate(EXTREME_SIZES):
+            x, y = 32, 4
+            dx, dy = (2, 0) if frame == 1 else (0, 2)
+            add(kind, frame, x, y, w, h, (0, 0), (0, 0), (-20, 19, -18, 20), k & 1, k >> 1 & 1,
+                4096 * frames[frame][y + dy:y + dy + h, x + dx:x + dx + w].astype(np.int64), np.full((h, w), 4096))
+    for k, (w, h) in enumerate(EXTREME_SIZES):
+        for mode in (0, 1):
+            x, y = min(152, W - w), CORNER_Y - h - 2
+            add("full", 3, x, y, w, h, (0, 2), (0, 16), (-48, 47, -46, 48), mode, (k + mode) & 1, np.full((h, w), WSRC_MAX),
+                np.full((h, w), 4096), spb=6000 if mode else 60, scale=1024 if mode else 1)
+    return frames, items, wsrcs, masks, costs, kinds
 
 
 def pack(items, wsrcs, masks, costs):

@@ -106,3 +106,55 @@ def test_obmc_install_point_before_init_fn_ptr():
         res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert res.returncode == 0, res.stderr[-2000:]
     assert res.stdout.split() == ["documented", "66/66", "late", "0/66"], res.stdout
+
+
+def test_extreme_batch_reaches_its_points():
+    """obmc_cases.extreme_batch on the restatement: the flat items stay on the clamped start with every neighbour's SAD equal
+    to the start's; on the stripes the two neighbours across the stripes tie, the first in NEIGHBORS order takes over, and
+    the walk with that pair swapped ends elsewhere; the full-magnitude items start on 255 * w * h, walk their whole range,
+    and with cost mode 1 form bits * sad_per_bit beyond 2^32."""
+    frames, items, wsrcs, masks, costs, kinds = oc.extreme_batch()
+    assert len(items) == 24 and len(frames) == 4 and all(f.shape == (136, 192) for f in frames)
+    for kind in ("flat", "v_stripes", "h_stripes", "full"):
+        sub = [it for it, k in zip(items, kinds) if k == kind]
+        assert {(it["w"], it["h"]) for it in sub} == set(oc.EXTREME_SIZES), kind
+        assert {it["cost_mode"] for it in sub} == {0, 1} and {it["search_diag"] for it in sub} == {0, 1}, kind
+    padded = [oc.pad_frame(f) for f in frames]
+    outside = 0
+    for i, (it, ws, mk, ct, kind) in enumerate(zip(items, wsrcs, masks, costs, kinds)):
+        pf, pad = padded[it["frame"]]
+        col, row, best, var, sse, steps = oc.walk(pf, pad, it, ws, mk, ct)
+        sc = min(max(it["mvp_col"], it["col_min"]), it["col_max"])
+        sr = min(max(it["mvp_row"], it["row_min"]), it["row_max"])
+
+        def sad(r, c):
+            y, x = it["y"] + r + pad, it["x"] + c + pad
+            return oc.obmc_sad(pf[y:y + it["h"], x:x + it["w"]], ws, mk)
+        if kind == "flat":
+            assert steps == 0 and (col, row) == (sc, sr), (i, it)
+            assert {sad(sr + dr, sc + dc) for dr, dc in oc.NEIGHBORS} == {sad(sr, sc)} and sad(sr, sc) > 0, i
+            outside += (sc, sr) != (it["mvp_col"], it["mvp_row"])
+        elif kind in oc.SWAPPED:
+            a, b = ((0, -1), (0, 1)) if kind == "v_stripes" else ((-1, 0), (1, 0))  # across the stripes; a is first in NEIGHBORS
+            n = 255 * it["w"] * it["h"]
+            assert sad(0, 0) == n and sad(*a) == sad(*b) == n // 2 and sad(2 * a[0], 2 * a[1]) == 0, i
+            along = ((-1, 0), (1, 0)) if kind == "v_stripes" else ((0, -1), (0, 1))
+            assert sad(*along[0]) == sad(*along[1]) == n  # these tie as well, at every step, and never take over
+            assert (row, col, steps, var, sse) == (2 * a[0], 2 * a[1], 2, 0, 0), (i, it)
+            other = oc.walk(pf, pad, it, ws, mk, ct, neighbors=oc.SWAPPED[kind])
+            assert (other[1], other[0]) == (2 * b[0], 2 * b[1]) and other[2:] == (best, var, sse, steps), (i, other)
+        else:
+            n = 255 * it["w"] * it["h"]
+            assert sad(sr, sc) == n and (n == 4177920) == (it["w"] == 128), i
+            if it["cost_mode"] == 0:
+                # down until the range ends or the block lies wholly in the corner; the large blocks stay near 255 * w * h
+                assert steps == min(it["search_range"], it["h"]) and row == sr + steps, (i, steps)
+                assert it["w"] < 64 or best > n * 3 // 4, (i, best)
+            else:  # the product the restatement masks; no record of obmc.bin reaches it
+                bits = int(ct[0]) + int(ct[4 + it["search_range"]]) + int(ct[4 + 3 * it["search_range"] + 1])
+                assert bits * it["sad_per_bit"] > 1 << 32 and it["sad_per_bit"] == 6000, i
+    assert outside == 4
+    # the fixture's own walk records never reach that product: the 32-bit mask there rests on the restatement alone
+    for it, _, _, cost, _ in oc.walk_cases():
+        if cost is not None:
+            assert int(np.max(cost[:4])) + 2 * int(np.max(cost[4:])) < (1 << 32) // it["sad_per_bit"]

@@ -140,3 +140,14 @@ def test_argument_checks(ctx, mixed):
     assert L.svtgpu_obmc_search(b.h, None, 0, 4, None) == INVALID_ARG
     b.search(refs)
     assert len(b.read()) == 4
+
+
+def test_batch_matches_restatement_on_tie_and_full_magnitude_content(ctx):
+    """obmc_cases.extreme_batch (tests/test_obmc.py asserts what its items reach): a flat frame, stripes whose two
+    neighbours across tie at the first step, and WSRC_MAX against a zero frame with a 255 corner, with an MV cost whose
+    32-bit product wraps.  mv_col, mv_row, best_sad, variance, sse and steps, exactly."""
+    frames, items, wsrcs, masks, costs, _ = oc.extreme_batch()
+    padded = [oc.pad_frame(f) for f in frames]
+    want = [oc.walk(*padded[it["frame"]], it, ws, mk, ct) for it, ws, mk, ct in zip(items, wsrcs, masks, costs)]
+    _, got = run_batch(ctx, frames, items, wsrcs, masks, costs)
+    check_results(got, want, items)

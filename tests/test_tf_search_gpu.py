@@ -83,7 +83,7 @@ class Search:
     """The device copies of a case's search planes, kept alive while calls are queued."""
 
     def __init__(self, c, refs=None):
-        pics = tc.pictures(c["pic_bd"], c["low8"])
+        pics = tc.case_pictures(c)
         self.c, self.refs = c, [r for r in pics["ref8"]] if refs is None else refs
         self.dc = [_dev(a) for a in pics["cen8"]]
         self.dr = [[_dev(a) for a in r] for r in self.refs]
@@ -116,7 +116,7 @@ class Chain:
     """The device planes of a chain case at the pictures' bit depth: centre, references, predictors, output."""
 
     def __init__(self, c):
-        pics = tc.pictures(c["pic_bd"], c["low8"])
+        pics = tc.case_pictures(c)
         dt = pics["cen"][0].dtype
         self.c, self.dt = c, dt
         self.dc = [_dev(a) for a in pics["cen"]]

@@ -147,9 +147,11 @@ def _i32(v):
     return ((int(v) + (1 << 31)) & M32) - (1 << 31)
 
 
-def subpel_search(ref, pad, cen, w, h, bd, px, py, b, start, kind, P, border=None):
+def subpel_search(ref, pad, cen, w, h, bd, px, py, b, start, kind, P, border=None, y_outer=False, trace=None):
     """tf_subpel_search of the b x b block at (px, py): ref the padded luma plane, cen the centre's, start the full-pel MV;
-    kind the filter table.  Returns (error, mv_x, mv_y)."""
+    kind the filter table.  Returns (error, mv_x, mv_y).  Test-only switches: y_outer walks the positions of a stage with y
+    outer and x inner (not the reference's order); trace, a list, receives one dict per evaluated position (block size,
+    MV, convolve form, sse, sum, distortion, and with P["trace_clip"] whether the convolve's final clip changed a sample)."""
     t, shift, hbd = ic.tables(), P["shift"], int(bd > 8)
     n, thr = b * (b >> shift), ((b * b * P["early"]) << hbd) & M32
     c = cen[py:py + b:1 << shift, px:px + b].astype(np.int64)
@@ -161,14 +163,22 @@ def subpel_search(ref, pad, cen, w, h, bd, px, py, b, start, kind, P, border=Non
         if border is not None:
             xs, ys = np.clip(xs, -border[0], w + border[0] - 1), np.clip(ys, -border[1], h + border[1] - 1)
         assert xs.min() >= -pad and ys.min() >= -pad and xs.max() < w + pad and ys.max() < h + pad
-        pr = ic.convolve(ref[np.ix_(ys + pad, xs + pad)], b, b, t[kind][phx], t[kind][phy], (1 if phx else 0) | (2 if phy else 0), bd)
+        form = (1 if phx else 0) | (2 if phy else 0)
+        pr = ic.convolve(ref[np.ix_(ys + pad, xs + pad)], b, b, t[kind][phx], t[kind][phy], form, bd)
         d = pr[::1 << shift] - c
         sse, sm = int((d * d).sum()), int(d.sum())
+        if trace is not None:
+            trace.append(dict(b=b, px=px, py=py, mv=(mvx, mvy), form=form, sse=sse, sum=sm))
+            if P.get("trace_clip"):
+                raw = ic.convolve(ref[np.ix_(ys + pad, xs + pad)], b, b, t[kind][phx], t[kind][phy], form, bd, clip=False)
+                trace[-1]["clipped"] = bool((raw != pr).any())
         if not hbd:
             v = (sse - (((sm * sm) // n) & M32)) & M32
         else:
             m = (sm + 2) >> 2
             v = max((((sse + 8) >> 4) & M32) - (m * m) // n, 0)
+        if trace is not None:
+            trace[-1]["dist"] = (v << shift) & M32
         return (v << shift) & M32
 
     best, bx, by = INT_MAX, _i16(start[0] * 8), _i16(start[1] * 8)
@@ -182,17 +192,22 @@ def subpel_search(ref, pad, cen, w, h, bd, px, py, b, start, kind, P, border=Non
                     continue
                 if (md >= 2 and i and j) or best == 0 or (P["early"] and best < thr):
                     continue
-                mx, my = _i16(cx + i * step), _i16(cy + j * step)
+                mx, my = (_i16(cx + j * step), _i16(cy + i * step)) if y_outer else (_i16(cx + i * step), _i16(cy + j * step))
                 d = dist(mx, my)
                 if d < best:
                     best, bx, by = d, mx, my
     return best, bx, by
 
 
-def search_frame(c, border=None, refs=None):
+def case_pictures(c):
+    """The pictures of case c: its own (a `pics` entry, as pictures() lays them out) or the drawn ones."""
+    return c["pics"] if "pics" in c else pictures(c["pic_bd"], c["low8"])
+
+
+def search_frame(c, border=None, refs=None, y_outer=False, trace=None):
     """The whole walk for case c (a search or chain case): records in the fixture's layout.  refs: other padded luma planes
-    than the case's own (the read-clamp test)."""
-    P, pics = c["P"], pictures(c["pic_bd"], c["low8"])
+    than the case's own (the read-clamp test).  y_outer / trace: subpel_search's test-only switches."""
+    P, pics = c["P"], case_pictures(c)
     cen = pics["cen8"][0]
     rec = dict(use64=np.zeros((NR, NBLK), np.uint8), mv64=np.zeros((NR, NBLK, 2), np.int16), split32=np.zeros((NR, NBLK, 4), np.uint8),
                split16=np.zeros((NR, NBLK, 16), np.uint8), mv32=np.zeros((NR, NBLK, 4, 2), np.int16),
@@ -205,7 +220,7 @@ def search_frame(c, border=None, refs=None):
         ref = pics["ref8"][r][0] if refs is None else refs[r]
 
         def go(px, py, b, start, kind):
-            return subpel_search(ref, c["pad"], cen, W, H, P["bd"], px, py, b, start, kind, P, border)
+            return subpel_search(ref, c["pad"], cen, W, H, P["bd"], px, py, b, start, kind, P, border, y_outer, trace)
         for blk in range(NBLK):
             bx, by = (blk % 3) * 64, (blk // 3) * 64
             e64, mx, my = go(bx, by, 64, fp["mv64"][r][blk], k64)

@@ -357,7 +357,10 @@ int svtgpu_cdef_search_frame(SvtGpuCdefFrameState *s, const SvtGpuFrame *recon, 
  * use_reference_cdef_fs its first branch (:744-789): one strength pair {pred_y_f, pred_uv_f}, index 0 everywhere.
  * lambda = full_lambda of the frame (computed by the encoder's lambda function table).
  * Writes params and the per-FB strength index (int8 per FB, host array of nfb entries) and keeps
- * the per-FB index on the device for svtgpu_cdef_apply_frame.  Synchronous (returns host data). */
+ * the per-FB index on the device for svtgpu_cdef_apply_frame.  Synchronous (returns host data).  It hands the
+ * parameters to the caller only: the device parameters of an earlier svtgpu_cdef_pick_async are dropped, so
+ * svtgpu_cdef_apply_frame(params = NULL) and svtgpu_cdef_read_params return SVTGPU_ERR_INVALID_ARG until the next
+ * svtgpu_cdef_pick_async. */
 int svtgpu_cdef_pick(SvtGpuCdefFrameState *s, const SvtGpuCdefControls *ctrls, int32_t base_q_idx,
                      uint64_t lambda, SvtGpuCdefParams *params_out, int8_t *fb_strength_out, void *stream);
 
@@ -377,7 +380,8 @@ int svtgpu_cdef_set_fb_strength(SvtGpuCdefFrameState *s, const int8_t *fb_streng
 /* ≙ svt_av1_cdef_frame (EbEncCdef.c:284-610): apply params to `recon` (DLF output) and write the
  * filtered picture to `out` (out-of-place; the reference's in-place result with its saved
  * unfiltered line/column buffers is identical).  Uses dir/var of the last search.  params == NULL: the parameters
- * of the last svtgpu_cdef_pick_async, read from device memory in stream order. */
+ * of the last svtgpu_cdef_pick_async, read from device memory in stream order -- with nothing in between: no
+ * asynchronous pick yet, or a svtgpu_cdef_pick on the state since, is SVTGPU_ERR_INVALID_ARG. */
 int svtgpu_cdef_apply_frame(SvtGpuCdefFrameState *s, const SvtGpuFrame *recon, SvtGpuFrame *out,
                             const SvtGpuCdefParams *params, void *stream);
 
@@ -515,7 +519,9 @@ int svtgpu_dlf_frame_to(SvtGpuDlfState *s, const SvtGpuFrame *in, SvtGpuFrame *o
  * on the filter level per plane with a device trial per level (filter + SSE vs `source` + restore).
  * `params` carries the previous levels in and the picked levels out; `recon` is left unfiltered.
  * dlf_avg_uv/temporal_layer_index select the reference's "use averaged chroma levels" shortcut.
- * Synchronous. */
+ * Synchronous.  The levels go to the caller only: the device levels of an earlier svtgpu_dlf_pick_async are dropped,
+ * so svtgpu_dlf_frame(_to)(..., params = NULL, ...) and svtgpu_dlf_read_levels return SVTGPU_ERR_INVALID_ARG until
+ * the next svtgpu_dlf_pick_async. */
 int svtgpu_dlf_pick(SvtGpuDlfState *s, SvtGpuFrame *recon, const SvtGpuFrame *source, SvtGpuLfParams *params,
                     int32_t dlf_avg, int32_t dlf_avg_uv, int32_t temporal_layer_index,
                     int32_t early_exit_convergence, int32_t tx_mode_only_4x4, void *stream);
@@ -524,7 +530,8 @@ int svtgpu_dlf_pick(SvtGpuDlfState *s, SvtGpuFrame *recon, const SvtGpuFrame *so
  * step, a final one-workgroup kernel completes a search still open after the rounds enqueued (sized from the previous
  * search) -- and the picked levels stay there.  `params` carries the previous levels in (read at the call).
  * svtgpu_dlf_frame(_to)(..., params = NULL, ...) then filters with the picked levels in stream order, and
- * svtgpu_dlf_read_levels waits for them (the frame header's levels).  A picture tiled over GPUs runs the synchronous
+ * svtgpu_dlf_read_levels waits for them (the frame header's levels).  The NULL form refers to the last
+ * svtgpu_dlf_pick_async with no svtgpu_dlf_pick on the state since.  A picture tiled over GPUs runs the synchronous
  * search here and keeps its levels. */
 int svtgpu_dlf_pick_async(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *source,
                           const SvtGpuLfParams *params, int32_t dlf_avg, int32_t dlf_avg_uv,
@@ -1533,7 +1540,9 @@ int svtgpu_ccso_search_plane(SvtGpuCcsoState *s, const uint16_t *ext, const uint
                              uint8_t *flags_out, void *stream);
 /* ≙ ccso_search (EbPickccso.c:785-815): rdmult weighted by clamp(base_q_idx, 1, 63), the three planes searched side by
  * side (one launch per pass).  Returns 1 and searches nothing when the weighted rdmult reaches INT_MAX (the reference
- * returns early); *frame_flag = ccso_frame_flag (any plane enabled).  params_out = NULL: nothing is read back and
+ * returns early): the state's device result is then cleared in stream order (every plane enable = 0), so a following
+ * svtgpu_ccso_apply_plane(..., NULL, ...) filters nothing instead of applying an earlier frame's search; the host
+ * outputs are left as they were.  *frame_flag = ccso_frame_flag (any plane enabled).  params_out = NULL: nothing is read back and
  * nothing waited for (*frame_flag = 0); the results stay in the state for svtgpu_ccso_apply_plane(..., NULL, ...). */
 int svtgpu_ccso_search_frame(SvtGpuCcsoState *s, const uint16_t *ext, const uint16_t *const org[3],
                              const uint16_t *const rec[3], int32_t bit_depth, int32_t rdmult, int32_t base_q_idx,

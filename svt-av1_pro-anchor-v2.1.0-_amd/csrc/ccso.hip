@@ -681,8 +681,14 @@ extern "C" int svtgpu_ccso_search_frame(SvtGpuCcsoState *s, const uint16_t *ext,
     for (int p = 0; p < 3; p++)
         if (!org[p] || !rec[p]) return SVTGPU_ERR_INVALID_ARG;
     const int64_t r = (int64_t)rdmult * std::min(std::max(base_q_idx, 1), 63); // EbPickccso.c:788-793
-    if (r >= INT_MAX) return 1;
     hipStream_t st = pick_stream(s->ctx, stream);
+    if (r >= INT_MAX) {
+        // nothing is searched and the frame's CCSO is off: the state's device result (an earlier frame's) is cleared
+        // in stream order, so svtgpu_ccso_apply_plane with params = NULL filters nothing, as the reference does
+        HIP_TRY(hipMemsetAsync(s->params, 0, 3 * sizeof(SvtGpuCcsoParams), st));
+        HIP_TRY(hipMemsetAsync(s->flags, 0, (size_t)3 * s->nb_max, st));
+        return 1;
+    }
     if (int rc = launch_search(s, ext, org, rec, 0, 3, bit_depth, (int32_t)r, st)) return rc;
     *frame_flag = 0;
     if (!params_out) return SVTGPU_OK; // the result stays on the device (apply with params = NULL)

@@ -336,6 +336,10 @@ static int cdef_pick_common(SvtGpuCdefFrameState *s, const SvtGpuCdefControls *c
         s->gathered = 1;
     }
     if (async_) s->apick_ref = ctrls->use_reference_cdef_fs != 0, s->apick_pending = 1, s->apick_ready = 1;
+    // a synchronous pick hands its parameters to the caller only (and rewrites d_fb_strength): the device parameters
+    // of an earlier svtgpu_cdef_pick_async are another frame's, so the NULL-parameter apply and
+    // svtgpu_cdef_read_params refuse until the next asynchronous pick
+    else s->apick_pending = 0, s->apick_ready = 0;
     if (ctrls->use_reference_cdef_fs) { // EbEncCdef.c:744-789: index 0 for every filter block, one pair
         SvtGpuCdefParams q;
         memset(&q, 0, sizeof(q));

@@ -1446,6 +1446,9 @@ extern "C" int svtgpu_dlf_pick(SvtGpuDlfState *s, SvtGpuFrame *recon, const SvtG
     if (!s || !frame_matches(s, recon) || !frame_matches(s, source) || source->bit_depth != recon->bit_depth ||
         !valid_params(params) || !s->have_mi)
         return SVTGPU_ERR_INVALID_ARG;
+    // this pick's levels go to the caller only: an earlier svtgpu_dlf_pick_async's device levels are another frame's,
+    // so the NULL-parameter filter and svtgpu_dlf_read_levels refuse until the next asynchronous pick
+    s->dev_ready = 0, s->dev_pending = 0;
     hipStream_t    st = pick_stream(s->ctx, stream);
     SvtGpuLfParams p  = *params;
     p.sharpness_level = 0;

@@ -77,12 +77,35 @@ CASES = {
                          seed=113),
     "sbdlf8_key": _case(w=200, h=136, bd=8, q=90, dlf_level=3, frame_type=KEY_FRAME, update_type=KF_UPDATE,
                         slice=I_SLICE, mesad=0, mi=("random", 24, 0.3), seed=114),
+    # frames that follow one another on one set of stage states (GROUPS below; tests/test_frames_in_flight*.py): the
+    # size, bit depth and LR unit sizes of an existing case, everything a stage decides different -- content, q, start
+    # levels and sharpness, the CDEF level (48 / 20 / 9 strengths in the 320x200 group: the pick's exchange words and
+    # its strength map change size between frames), the LR levels, the mode-info grid and its share of skipped blocks
+    "seq10_b": _case(w=320, h=200, bd=10, q=96, cdef_level=4, dlf_level=1, wn_level=1, sg_level=3, lf=(34, 30, 18, 16),
+                     sharp=5, tl=0, us=(128, 64), mi=("random", 26, 0.05), seed=116),
+    "seq10_c": _case(w=320, h=200, bd=10, q=232, cdef_level=7, dlf_level=2, wn_level=3, sg_level=1, lf=(6, 8, 3, 2),
+                     sharp=0, mrd=1, ref_deltas=(2, 0, -1, 0, -1, 0, 1, -2), mode_deltas=(1, -1), tl=2,
+                     update_type=LF_UPDATE, us=(128, 64), mi=("random", 27, 0.6), seed=117),
+    "seq8_c": _case(w=200, h=136, bd=8, q=136, cdef_level=5, dlf_level=2, wn_level=2, sg_level=3, lf=(24, 18, 12, 10),
+                    sharp=3, tl=1, update_type=INTNL_ARF_UPDATE, mi=("random", 28, 0.15), seed=118),
     # BASELINE.json configs[1] (1080p 8-bit) and configs[2] (4K 10-bit, the bench workload): digests only
     "c1_1080p8": _case(w=1920, h=1080, bd=8, us=(256, 128), mi=("bench", 0x5EED0002), seed=0x5EED0002,
                        digest=True),
     "c3_4k10": _case(w=3840, h=2160, bd=10, us=(256, 128), mi=("bench", 0x5EED0003), seed=0x5EED0003, digest=True),
 }
 SMALL = [k for k, c in CASES.items() if not c["digest"]]
+# cases of one picture size, bit depth and LR unit size: the frames one set of stage states sees in turn
+GROUPS = {
+    "320x200_10": ("mini10", "seq10_b", "seq10_c"),
+    "200x136_8": ("reffs_8", "sbdlf8_key", "seq8_c"),
+    "256x192_10": ("reffs_10", "sbdlf10_uv0"),
+}
+
+
+def sequence(group, start=0, n=5):
+    """n frames of a group in turn from case `start` on (A, B, C, A, B; a pair: A, B, A, B, A)."""
+    names = GROUPS[group]
+    return [names[(start + i) % len(names)] for i in range(n)]
 
 
 def frame_pair(w, h, bd, seed):

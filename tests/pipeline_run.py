@@ -47,7 +47,7 @@ def sb_dlf_params(c, levels):
     return LfParams.make(*levels, 0)
 
 
-def gpu_dlf_pick(dl, R, S, c):
+def gpu_dlf_pick(dl, R, S, c, stream=None):
     """The frame's loop-filter levels on libsvtgpu: the device level search (DLF levels 1, 2) or LPF_PICK_FROM_Q (the
     SB-based levels 3-5: every SB's ME distortion the case's `mesad`, no listed references)."""
     import svtgpu
@@ -55,7 +55,7 @@ def gpu_dlf_pick(dl, R, S, c):
     if dc["sb_based"]:
         return sb_dlf_params(c, svtgpu.dlf_pick_by_q(c["bd"], c["q"], c["frame_type"], c["slice"], c["tl"], c["tl"],
                                                      c["in_res"], dc["zero_lvl"], [c["mesad"]] * nsb64(c), []))
-    return dl.pick(R, S, pc.lf_params(c), dc["avg"], dc["avg_uv"], c["tl"], dc["early_exit"], c["only4x4"])
+    return dl.pick(R, S, pc.lf_params(c), dc["avg"], dc["avg_uv"], c["tl"], dc["early_exit"], c["only4x4"], stream)
 
 
 def cdef_ctrl_row(level):
@@ -182,6 +182,175 @@ def run_oracle(case):
                 fbs=fbs, applied=applied, cdef=cdef, ft=ft, units=units, recs=recs, lrc=lrc, lr=lr)
 
 
+_INPUTS = {}
+
+
+def _pinned(a):
+    """`a` in page-locked host memory (torch's allocator), so a copy from it is asynchronous to the host."""
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint16:
+        return torch.from_numpy(a.view(np.int16)).pin_memory().numpy().view(np.uint16)
+    return torch.from_numpy(a).pin_memory().numpy()
+
+
+def case_inputs(case, device=False):
+    """What a frame slot hands the library for `case`, made once and never written again: the source / recon planes in
+    the frames' sample type and the block mask (page-locked, so their uploads do not wait on the host), the mode info,
+    the SB128 block sizes, the reference's lambda; device=True adds the mode-info grid as a device tensor."""
+    import torch
+    inp = _INPUTS.get(case)
+    if inp is None:
+        c = pc.CASES[case]
+        src, rec, mi = pc.inputs(case)
+        dt = np.uint16 if c["bd"] > 8 else np.uint8
+        inp = dict(src=src, rec=rec, mi=mi, lam=int(pc.load(case)["cdef_lambda"][0]),
+                   src_up=[_pinned(np.asarray(a, dt)) for a in src], rec_up=[_pinned(np.asarray(a, dt)) for a in rec],
+                   mask=_pinned(pc.cdef_mask(mi)),
+                   fbb=np.ascontiguousarray(mi)["bsize"][::16, ::16].reshape(-1).copy() if c["sb"] == 128 else None)
+        if not c["digest"]:  # the small cases are kept for the process; a 1080p / 4K case is made per run
+            _INPUTS[case] = inp
+    if device and "mi_dev" not in inp:
+        inp["mi_dev"] = torch.from_numpy(np.ascontiguousarray(inp["mi"]).view(np.uint8).copy()).cuda()
+        torch.cuda.synchronize()
+    return inp
+
+
+class FrameSlot:
+    """One frame in flight, as bench.py keeps it: one DlfState / CdefState / LrState that persist from frame to frame,
+    the input frames S and R, output frames D (deblocked), C (CDEF), O (LR) per step, and one stream that every
+    library call of the slot is given.  enqueue() runs a case's frame exactly as run_gpu always has -- the same calls
+    in the same order -- and collect() returns what check() takes.
+
+    Calls of the asynchronous form that still wait on the host, by the library's design:
+    * svtgpu_dlf_set_mode_info waits for the previous frame's copy out of its one staging buffer (mi_free) before it
+      rewrites it; mi_device=True hands the grid over from device memory instead (bench.py's form), which queues;
+    * svtgpu_cdef_set_fb_bsize with an SB128 array synchronizes the stream (its host array may be reused at once);
+    * with a device grid, a filter with explicit levels (the SB-based DLF levels, which have no device search) waits
+      for the grid's verdict;
+    * svtgpu_lr_search_frame_async waits for the previous search's plan upload out of its one page-locked buffer
+      (pin_free) before it rewrites it, i.e. until the frame before has reached its LR stage on the device.
+    Everything else of the asynchronous form queues: uploads from page-locked memory, the block mask, the level
+    search, the filter, the CDEF search / pick / apply, and the LR finish / apply behind the search.  So a thread
+    runs ahead of its stream by one whole frame plus the next frame's DLF and CDEF stages."""
+
+    def __init__(self, ctx, w, h, bd, us, stream=None, mi_device=False):
+        import svtgpu
+        self.ctx, self.w, self.h, self.bd, self.stream, self.mi_device = ctx, w, h, bd, stream, mi_device
+        self.us = [us[0], us[1], us[1]]
+        self.S, self.R = svtgpu.Frame(ctx, w, h, bd), svtgpu.Frame(ctx, w, h, bd)
+        self.dl = svtgpu.DlfState(ctx, w, h)
+        self.st = svtgpu.CdefState(ctx, w, h)
+        self.lr = svtgpu.LrState(ctx, w, h, self.us)
+        self.pool, self.frames, self.last = [], [self.S, self.R], None
+
+    @classmethod
+    def for_case(cls, ctx, case, stream=None, mi_device=False):
+        c = pc.CASES[case]
+        return cls(ctx, c["w"], c["h"], c["bd"], c["us"], stream, mi_device)
+
+    def _upload(self, F, planes):
+        import svtgpu
+        for p, a in enumerate(planes):
+            assert a.shape == F.plane_shape(p) and a.dtype == F.dtype
+            svtgpu.check(svtgpu.lib().svtgpu_frame_upload(F.h, p, svtgpu.ptr(a), a.shape[1], self.stream))
+
+    def enqueue(self, case, async_, at_lr=None):
+        """One frame of `case` on the slot's states and stream.  async_: svtgpu_dlf_pick_async (the levels that have a
+        device search), svtgpu_cdef_pick_async and svtgpu_lr_search_frame_async with the NULL-parameter filter /
+        apply calls, and no host wait of this method's own; else the synchronous picks, applied with explicit
+        parameters.  at_lr: an event set when the frame reaches its LR stage.  Returns the step's handle: its output
+        frames, the decisions the host already has, and every host array a queued copy may still read."""
+        import svtgpu
+        c = pc.CASES[case]
+        assert (c["w"], c["h"], c["bd"], [c["us"][0], c["us"][1], c["us"][1]]) == (self.w, self.h, self.bd, self.us)
+        inp = case_inputs(case, self.mi_device)
+        s, S, R, dl, st, lr = self.stream, self.S, self.R, self.dl, self.st, self.lr
+        if not self.pool:
+            self.pool.append([svtgpu.Frame(self.ctx, self.w, self.h, self.bd) for _ in range(3)])
+            self.frames += self.pool[-1]
+        D, C, O = outs = self.pool.pop()
+        hd = dict(case=case, async_=async_, outs=outs, keep=[inp], lf=None, tables=None, prm=None, ft=None)
+        self._upload(S, inp["src_up"])
+        self._upload(R, inp["rec_up"])
+        if self.mi_device:
+            dl.set_mode_info_device(inp["mi_dev"], s)
+        else:
+            dl.set_mode_info(inp["mi"], s)
+        dc = dlf_ctrls(c["dlf_level"])
+        hd["dlf_async"] = bool(async_ and not dc["sb_based"])
+        if hd["dlf_async"]:
+            dl.pick_async(R, S, pc.lf_params(c), dc["avg"], dc["avg_uv"], c["tl"], dc["early_exit"], c["only4x4"], s)
+            dl.filter_to(R, D, None, stream=s)
+        else:
+            hd["lf"] = gpu_dlf_pick(dl, R, S, c, s)
+            dl.filter_to(R, D, hd["lf"], stream=s)
+        hd["keep"].append(inp["mask"])
+        st.set_block_mask(inp["mask"], s)
+        st.set_fb_bsize(inp["fbb"], s)  # every frame: SB128 after SB64 and SB64 after SB128 are both reset
+        ctrls = svtgpu.cdef_controls(c["cdef_level"])
+        ctrls.pred_y_f, ctrls.pred_uv_f = c["pred"]
+        st.search(D, S, ctrls, c["q"], s)
+        if async_:  # the pick in stream order; the apply reads its parameters on the device (zero strengths: a copy)
+            st.pick_async(ctrls, c["q"], inp["lam"], s)
+            st.apply(D, C, None, s)
+        else:
+            hd["tables"] = st.read(s)
+            prm, fbs = hd["prm"], hd["fbs"] = st.pick(ctrls, c["q"], inp["lam"], s)
+            if prm.cdef_y_strength[0] != 0 or prm.cdef_uv_strength[0] != 0 or prm.cdef_bits != 0:
+                st.apply(D, C, prm, s)
+            else:
+                svtgpu.check(svtgpu.lib().svtgpu_frame_copy(C.h, D.h, s))
+        if at_lr is not None:
+            at_lr.set()
+        lrc = hd["lrc"] = svtgpu.lr_controls(c["wn_level"], c["sg_level"], c["rdmult"], c["sw"], c["wc"], c["sc"])
+        hd["keep"] += [ctrls, lrc]
+        if async_:
+            lr.search_async(C, S, lrc, s)
+            lr.apply(D, C, O, None, s)
+            hd["recs"] = None
+        else:
+            ft, hd["recs"] = lr.search(C, S, lrc, s, records=True)
+            hd["ft"], hd["units"] = ft, svtgpu.lr_finish_frame(lrc, hd["recs"])[1]
+            if any(ft):
+                lr.apply(D, C, O, ft, s)
+            else:
+                svtgpu.check(svtgpu.lib().svtgpu_frame_copy(O.h, C.h, s))
+        self.last = hd
+        return hd
+
+    def collect(self, hd, last):
+        """Wait for the stream and download the step's planes.  last (the last step enqueued on the slot, only): the
+        decisions the asynchronous calls left in the states are read back too -- the levels, the CDEF tables,
+        parameters and per-block strengths, the LR frame types and units.  Returns run_gpu's dict; a step of the
+        asynchronous form that is not the last has its decisions overwritten and returns the planes alone
+        (planes_only, which check() honours)."""
+        s, inp = self.stream, hd["keep"][0]
+        assert not last or hd is self.last
+        self.ctx.synchronize(s)
+        D, C, O = hd["outs"]
+        out = dict(src=inp["src"], rec=inp["rec"], mi=inp["mi"], dlf=D.download(s), cdef=C.download(s),
+                   lr=O.download(s), lrc=hd["lrc"], recs=hd["recs"], planes_only=bool(hd["async_"] and not last))
+        self.pool.append(hd["outs"])
+        if out["planes_only"]:
+            return out
+        if hd["async_"]:
+            lf = self.dl.read_levels(s) if hd["dlf_async"] else hd["lf"]
+            tables = self.st.read(s)
+            prm, fbs = self.st.read_params(s)
+            ft, units = self.lr.read_result(s), [self.lr.read_units(p, s) for p in range(3)]
+        else:
+            lf, tables, prm, fbs, ft, units = (hd[k] for k in ("lf", "tables", "prm", "fbs", "ft", "units"))
+        nb = 1 << prm.cdef_bits
+        applied = int(prm.cdef_y_strength[0] != 0 or prm.cdef_uv_strength[0] != 0 or nb != 1)
+        out.update(lf=lf.levels(), tables=tables, prm=prm, nb=nb, fbs=fbs, applied=applied, ft=ft, units=units)
+        return out
+
+    def close(self):
+        for x in self.frames + [self.dl, self.st, self.lr]:
+            x.close()
+
+
 def run_gpu(case, ctx=None, async_=None):
     """The MI355X library (libsvtgpu) on the whole path, one stream, frames resident on the device.  async_ (default:
     SVTGPU_TEST_ASYNC=1 in the environment): the DLF level search and the LR search + RD finish in their asynchronous
@@ -191,67 +360,9 @@ def run_gpu(case, ctx=None, async_=None):
     if async_ is None:
         async_ = os.environ.get("SVTGPU_TEST_ASYNC") == "1"
     import svtgpu
-    c = pc.CASES[case]
-    g = pc.load(case)
-    src, rec, mi = pc.inputs(case)
-    bd, w, h = c["bd"], c["w"], c["h"]
-    ctx = ctx or svtgpu.Context()
-    S, R, D, C, O = (svtgpu.Frame(ctx, w, h, bd) for _ in range(5))
-    S.upload(src)
-    R.upload(rec)
-    dl = svtgpu.DlfState(ctx, w, h)
-    dl.set_mode_info(mi)
-    if async_ and not dlf_ctrls(c["dlf_level"])["sb_based"]:
-        dc = dlf_ctrls(c["dlf_level"])
-        dl.pick_async(R, S, pc.lf_params(c), dc["avg"], dc["avg_uv"], c["tl"], dc["early_exit"], c["only4x4"])
-        dl.filter_to(R, D, None)
-        lfp = dl.read_levels()
-    else:
-        lfp = gpu_dlf_pick(dl, R, S, c)
-        dl.filter_to(R, D, lfp)
-    st = svtgpu.CdefState(ctx, w, h)
-    st.set_block_mask(pc.cdef_mask(mi))
-    if c["sb"] == 128:
-        st.set_fb_bsize(np.ascontiguousarray(mi)["bsize"][::16, ::16].reshape(-1))
-    ctrls = svtgpu.cdef_controls(c["cdef_level"])
-    ctrls.pred_y_f, ctrls.pred_uv_f = c["pred"]
-    st.search(D, S, ctrls, c["q"])
-    tables = st.read()
-    if async_:  # the pick in stream order; the apply reads its parameters on the device (zero strengths: a copy)
-        st.pick_async(ctrls, c["q"], int(g["cdef_lambda"][0]))
-        st.apply(D, C, None)
-    else:
-        prm, fbs = st.pick(ctrls, c["q"], int(g["cdef_lambda"][0]))
-        nb = 1 << prm.cdef_bits
-        applied = int(prm.cdef_y_strength[0] != 0 or prm.cdef_uv_strength[0] != 0 or nb != 1)
-        if applied:
-            st.apply(D, C, prm)
-        else:
-            svtgpu.check(svtgpu.lib().svtgpu_frame_copy(C.h, D.h, None))
-    us = [c["us"][0], c["us"][1], c["us"][1]]
-    lr = svtgpu.LrState(ctx, w, h, us)
-    lrc = svtgpu.lr_controls(c["wn_level"], c["sg_level"], c["rdmult"], c["sw"], c["wc"], c["sc"])
-    if async_:
-        lr.search_async(C, S, lrc)
-        lr.apply(D, C, O, None)
-        ft, recs = lr.read_result(), None
-        units = [lr.read_units(p) for p in range(3)]
-    else:
-        ft, recs = lr.search(C, S, lrc, records=True)
-        units = svtgpu.lr_finish_frame(lrc, recs)[1]
-        if any(ft):
-            lr.apply(D, C, O, ft)
-        else:
-            svtgpu.check(svtgpu.lib().svtgpu_frame_copy(O.h, C.h, None))
-    ctx.synchronize()
-    if async_:
-        prm, fbs = st.read_params()
-        nb = 1 << prm.cdef_bits
-        applied = int(prm.cdef_y_strength[0] != 0 or prm.cdef_uv_strength[0] != 0 or nb != 1)
-    out = dict(src=src, rec=rec, mi=mi, lf=lfp.levels(), dlf=D.download(), tables=tables, prm=prm, nb=nb, fbs=fbs,
-               applied=applied, cdef=C.download(), ft=ft, units=units, recs=recs, lrc=lrc, lr=O.download())
-    for x in (S, R, D, C, O, dl, st, lr):
-        x.close()
+    slot = FrameSlot.for_case(ctx or svtgpu.Context(), case)
+    out = slot.collect(slot.enqueue(case, async_), last=True)
+    slot.close()
     return out
 
 
@@ -265,13 +376,19 @@ def _planes_equal(g, key, got, digest, what):
             np.testing.assert_array_equal(a, g["%s%d" % (key, p)], err_msg="%s: %s plane %d" % (what, key, p))
 
 
-def check(case, out, what):
-    """Assert `out` (run_gpu / run_oracle) equals the reference outputs of `case`, stage by stage."""
+def check(case, out, what, planes_only=False):
+    """Assert `out` (run_gpu / run_oracle / FrameSlot.collect) equals the reference outputs of `case`, stage by stage.
+    planes_only (or a result that says so itself: a step whose decisions a later step on the same states has
+    overwritten): the deblocked, CDEF and LR planes alone."""
     c = pc.CASES[case]
     g = pc.load(case)
     digest = c["digest"]
     assert pc.input_digest(out["src"], out["rec"], out["mi"]) == str(g["input_sha"]), \
         "%s: input generator differs from the fixture's" % case
+    if planes_only or out.get("planes_only"):
+        for key in ("dlf", "cdef", "lr"):
+            _planes_equal(g, key, out[key], digest, what + " " + case)
+        return
     # DLF
     assert tuple(int(x) for x in out["lf"]) == tuple(int(x) for x in g["lf_levels"]), (what, case, out["lf"],
                                                                                       g["lf_levels"])

@@ -135,6 +135,53 @@ def test_search_golden(g, ctx):
         st.close()
 
 
+def test_overflow_after_a_search_filters_nothing(g, ctx):
+    """One state, three frames.  A frame whose golden enables CCSO on every plane is searched with the result left on
+    the device; then the rdmult overflow (rdmult * clamp(q, 1, 63) >= INT_MAX: svtgpu_ccso_search_frame returns 1 and
+    searches nothing -- the fixture's own overflow case is 64x64, another size, so it is the same frame with such an
+    rdmult); the apply with params = NULL must then leave every plane as it was, as the reference's ccso_frame does
+    with ccso_enable = 0, and not filter it with the first frame's search.  A third, ordinary search and apply of
+    other content on the same state equals the oracle.  (Without the clear before `return 1` in ccso.hip the second
+    step filters with the first search's tables: the parent commit fails here.)"""
+    import torch
+    c = next(c for c in xc.search_cases(g) if c["bd"] == 8 and all(p.enable for p in c["params"]))
+    w, h, bd = c["w"], c["h"], c["bd"]
+    st = svtgpu.CcsoState(ctx, w, h)
+    ext, _ = ext_dev(st, c["pre"])
+    d_org, d_rec = [dev(a) for a in c["org"]], [dev(a) for a in c["rec"]]
+    org_p, rec_p = [t.data_ptr() for t in d_org], [t.data_ptr() for t in d_rec]
+    assert st.search_frame(ext.data_ptr(), org_p, rec_p, bd, c["rdmult"], c["q"], read=False) == 0
+    over = (2 ** 31 - 1) // min(max(c["q"], 1), 63) + 1
+    assert over * min(max(c["q"], 1), 63) >= 2 ** 31 - 1 and over < 2 ** 31
+    assert st.search_frame(ext.data_ptr(), org_p, rec_p, bd, over, c["q"], read=False) == 1
+    for p in range(3):
+        ph, pw = c["out"][p].shape
+        plane = c["rec"][p][:ph, :pw].astype(np.uint8)
+        assert not np.array_equal(c["out"][p], plane)  # the first search's result would change the plane
+        d8 = dev(plane)
+        st.apply(ext.data_ptr(), p, 8, d8.data_ptr(), 8, pw)
+        np.testing.assert_array_equal(host(d8, np.uint8), plane, err_msg="plane %d filtered after the overflow" % p)
+    org, rec, pre = xc.content(w, h, bd, seed=5)
+    ext2, ext_h = ext_dev(st, pre)
+    d_org, d_rec = [dev(a) for a in org], [dev(a) for a in rec]
+    rc, prms, flags, ff = st.search_frame(ext2.data_ptr(), [t.data_ptr() for t in d_org],
+                                          [t.data_ptr() for t in d_rec], bd, c["rdmult"], c["q"])
+    torch.cuda.synchronize()
+    orc, oprms, oflags, off = oracle.ccso_search_frame(ext_h, org, rec, bd, c["rdmult"], c["q"])
+    assert (rc, ff) == (orc, off) == (0, 1)
+    for p in range(3):
+        assert prms[p].fields() == oprms[p].fields(), p
+        np.testing.assert_array_equal(prms[p].lut(), oprms[p].lut())
+        np.testing.assert_array_equal(flags[p], oflags[p])
+        ph, pw = (h >> 1, w >> 1) if p else (h, w)
+        plane = rec[p][:ph, :pw].astype(np.uint8)
+        d8 = dev(plane)
+        st.apply(ext2.data_ptr(), p, bd, d8.data_ptr(), 8, pw)
+        want = oracle.ccso_apply_plane(ext_h, bd, p, plane, oprms[p], oflags[p])
+        np.testing.assert_array_equal(host(d8, np.uint8), want, err_msg="plane %d" % p)
+    st.close()
+
+
 @pytest.mark.parametrize("w,h,bd,rdmult,q", [(1280, 720, 8, 1500, 80), (640, 360, 10, 900, 120),
                                              (1000, 504, 8, 50000, 40)])
 def test_search_and_apply_vs_oracle(ctx, w, h, bd, rdmult, q):

@@ -20,6 +20,10 @@
 //                         ep's filter planes read once into registers, the projection moments, the seed (the 2x2
 //                         double solve, as the reference) and finer_search_pixel_proj_error's descent, stepped by a
 //                         control wave between passes over the resident pixels
+//   wiener_res_small_kernel  the same descent on 256 lanes for one-part units whose window fits 38 KB of LDS (a
+//                         128 x 128 chroma unit): four workgroups per CU instead of one; units are routed by size
+//   sgr_res_small_kernel  the same body (sgr_res_body.h) sized for one-part units of <= SRS_KMAX chunks per lane (a
+//                         128 x 128 chroma unit): three workgroups per CU instead of two; units are routed by size
 //   sgr_best_kernel, sgr_sse_kernel
 //                         best ep per unit (strict <) and the SSE of its clipped output
 // The host does what is sequential in the reference and cheap: the RD pass over the units (rest_finish_search).  A
@@ -1011,22 +1015,24 @@ __host__ __device__ inline void set_wiener_taps(int16_t *t, const int *v) { // s
 // ---------------------------------------------------------------------------------------------
 constexpr int WR_NT = 1024, WR_RMAX = 32, WR_MAX_ROUNDS = 4096;
 constexpr int WR_LDS_CAP = 152 * 1024; // largest CDEF window kept in LDS (bytes); larger units read global memory
+constexpr int WRS_LDS_CAP = 38 * 1024; // ... of the small instance: four windows and the static words in a CU's 160 KB
 
 // geometry of a unit in the lane layout: column-pair slots per segment (a multiple of 64), segments, rows per segment
 struct WrGeo {
     int cpw, nseg, R;
 };
-__host__ __device__ inline WrGeo wr_geo(int w, int h) {
+__host__ __device__ inline WrGeo wr_geo(int w, int h, int nt = WR_NT) { // nt: the instance's lanes
     WrGeo g;
     g.cpw  = (((w + 1) >> 1) + 63) & ~63;
-    g.nseg = WR_NT / g.cpw;
+    g.nseg = nt / g.cpw;
     g.R    = (h + g.nseg - 1) / g.nseg;
     return g;
 }
 __host__ __device__ inline int wr_window_bytes(int w, int h) { return (h + 6) * ((w + 10) >> 1) * 4; }
 // LDS mode: the window in LDS and the source rows in registers; else both are read from global memory per candidate
-__host__ __device__ inline bool wr_lds_mode(int w, int h, int lds_cap) {
-    return wr_window_bytes(w, h) <= lds_cap && wr_geo(w, h).R <= WR_RMAX;
+__host__ __device__ inline bool wr_lds_mode(int w, int h, int lds_cap, int nt = WR_NT, int rmax = WR_RMAX) {
+    const WrGeo g = wr_geo(w, h, nt);
+    return wr_window_bytes(w, h) <= lds_cap && g.nseg > 0 && g.R <= rmax;
 }
 // A workgroup's share of a unit: rows [y0, y1) of unit `unit`.  A unit too large for one CU's LDS and registers (the
 // frame's bottom unit row: 256 x 376 at 4K) is cut into `nparts` row parts on as many workgroups; each evaluates every
@@ -1088,7 +1094,8 @@ __device__ __forceinline__ S uniform(const S &v) {
     return r;
 }
 
-template <typename T, bool LDSW>
+// NT, RMAX: the instance's lanes per workgroup and its cap on the rows of a segment (the unrolled row loop)
+template <typename T, bool LDSW, int NT, int RMAX>
 __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, const uint32_t *win, int ws, int ux,
                        int uy, int w, int h, const WrItem &it, unsigned long long *xch, int *s_mode, int16_t *s_taps,
                        unsigned long long *s_part, int32_t *status, unsigned long long &npx, unsigned long long *stat,
@@ -1096,27 +1103,27 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
     // diagnostics (SVTGPU_WR_STATS): thread 0's pass time (candidate start to the first barrier), its control step
     // and the whole descent, in 100 MHz ticks, kept in LDS ({run start, pass, control, mark}: no registers)
     __shared__ unsigned long long s_wt[6];
-    __shared__ uint32_t           s_wp[WR_NT / 64]; // each wave's pass time of the current candidate
+    __shared__ uint32_t           s_wp[NT / 64]; // each wave's pass time of the current candidate
     if (stat && threadIdx.x == 0)
         s_wt[0] = s_wt[3] = __builtin_amdgcn_s_memrealtime(), s_wt[1] = s_wt[2] = s_wt[4] = s_wt[5] = 0;
-    const WrGeo g  = wr_geo(w, h);
+    const WrGeo g  = wr_geo(w, h, NT);
     // a wave holds 64 column pairs of one row segment (cpw is a multiple of 64): the segment's values are wave-uniform,
     // which readfirstlane tells the compiler -- the row loop then branches on scalars instead of masking lanes
     const int   cp = threadIdx.x % g.cpw, sg = __builtin_amdgcn_readfirstlane((int)threadIdx.x / g.cpw), x = 2 * cp;
     const int   seg0 = sg * g.R, nrows = __builtin_amdgcn_readfirstlane(sg < g.nseg ? max(0, min(g.R, h - seg0)) : 0);
     const int   xc = min(x, (w - 1) & ~1), hw = h + 6; // an addressable column for lanes right of the unit
     const uint32_t dmask = x >= w ? 0u : x + 1 >= w ? 0xFFFFu : 0xFFFFFFFFu;
-    // the lane's source pixels, one (x, x+1) pair per row: registers (LDS mode, <= WR_RMAX rows), else global memory
+    // the lane's source pixels, one (x, x+1) pair per row: registers (LDS mode, <= RMAX rows), else global memory
     const T   *sbase = (const T *)P.src + (size_t)(uy + seg0) * P.sstride + ux + xc;
     const bool s1    = xc + 1 < w; // an odd unit width: the lane's second column is outside the unit
     auto       load_src = [&](int k) -> uint32_t {
         const T *q = sbase + (size_t)k * P.sstride;
         return (uint32_t)q[0] | ((uint32_t)(s1 ? q[1] : 0) << 16);
     };
-    uint32_t sv[LDSW ? WR_RMAX : 1];
+    uint32_t sv[LDSW ? RMAX : 1];
     if constexpr (LDSW) {
 #pragma unroll
-        for (int k = 0; k < WR_RMAX; k++)
+        for (int k = 0; k < RMAX; k++)
             if (k < nrows) sv[k] = load_src(k);
     }
     const WienerRound rr  = wiener_round(P.bd);
@@ -1176,7 +1183,7 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
         }
         if constexpr (LDSW) { // unrolled: the source pairs are addressed by constants
 #pragma unroll
-            for (int j = 0; j < WR_RMAX / 2 + 3; j++) {
+            for (int j = 0; j < RMAX / 2 + 3; j++) {
                 if (j < je) { // uniform per wave (one segment per wave)
 #pragma unroll
                     for (int k = 0; k < 5; k++) pa[k] = na[k], pb[k] = nb[k];
@@ -1210,7 +1217,7 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
     // ~1.1 of the ~9 us per candidate).  SVTGPU_WR_CLASSIC=1 keeps thread 0's step (the row-part units always do:
     // their SSE exchange runs on one thread)
     if (it.nparts == 1 && !classic) {
-        __shared__ unsigned long long s_part2[2][WR_NT / 64];
+        __shared__ unsigned long long s_part2[2][NT / 64];
         Descent Dw   = uniform(D);
         bool    live = __builtin_amdgcn_readfirstlane(*s_mode) != 0;
         while (live) {
@@ -1227,7 +1234,7 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
             __syncthreads();
             unsigned long long err = 0;
 #pragma unroll
-            for (int k = 0; k < WR_NT / 64; k++) err += s_part2[rounds & 1][k];
+            for (int k = 0; k < NT / 64; k++) err += s_part2[rounds & 1][k];
             npx += (unsigned long long)w * h;
             ++rounds;
             const bool ok = rounds <= WR_MAX_ROUNDS; // a descent always ends: an internal failure, reported by the host
@@ -1254,7 +1261,7 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
         __syncthreads();
         if (stat && threadIdx.x == 0) {
             uint32_t mx = 0, mn = ~0u;
-            for (int q = 0; q < WR_NT / 64; q++) mx = max(mx, s_wp[q]), mn = min(mn, s_wp[q]);
+            for (int q = 0; q < NT / 64; q++) mx = max(mx, s_wp[q]), mn = min(mn, s_wp[q]);
             s_wt[4] += mx, s_wt[5] += mn;
             s_wt[3] = __builtin_amdgcn_s_memrealtime();
         }
@@ -1263,7 +1270,7 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
             // pixel waves on this SIMD while it runs
             __builtin_amdgcn_s_setprio(3);
             unsigned long long err = 0;
-            for (int k = 0; k < WR_NT / 64; k++) err += s_part[k];
+            for (int k = 0; k < NT / 64; k++) err += s_part[k];
             npx += (unsigned long long)w * h;
             ++rounds;
             bool ok = rounds <= WR_MAX_ROUNDS; // a descent always ends: an internal failure, reported by the host
@@ -1310,18 +1317,23 @@ __device__ void wr_run(const SearchArgs &A, const PlaneArgs &P, Descent &D, cons
         atomicAdd(stat + 4, s_wt[1]), atomicAdd(stat + 5, (unsigned long long)w * h);
         atomicAdd(stat + 6, (unsigned long long)(it.nparts > 1)), atomicAdd(stat + 7, s_wt[4]);
         atomicAdd(stat + 8, s_wt[5]);
+        if (it.nparts == 1 && wr_window_bytes(w, h) <= WRS_LDS_CAP) // the small-size units apart, wherever they run
+            atomicAdd(stat + 9, 1ull), atomicAdd(stat + 10, (unsigned long long)rounds),
+                atomicAdd(stat + 11, __builtin_amdgcn_s_memrealtime() - s_wt[0]);
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(WR_NT) void wiener_res_kernel(const SearchArgs A, Descent *ds, const WrItem *items,
-                                                           int lds_cap, unsigned long long *xch, int32_t *status,
-                                                           unsigned long long *pc, unsigned long long *stat,
-                                                           unsigned long long *tk, int classic) {
+// The body of the resident Wiener kernels.  NT, RMAX: the instance's lanes and its cap on the rows of a lane's segment.
+// SMALL: an instance of one-part units whose window is in LDS, on the self-stepping path only (the planner sends it
+// nothing else; anything else sets status bit 4)
+template <typename T, int NT, int RMAX, bool SMALL>
+__device__ __forceinline__ void wr_res_body(const SearchArgs &A, Descent *ds, const WrItem *items, int lds_cap,
+                                            unsigned long long *xch, int32_t *status, unsigned long long *pc,
+                                            unsigned long long *stat, unsigned long long *tk, int classic) {
     PROF_BEGIN(tk);
     extern __shared__ uint32_t wr_win[]; // the part's CDEF window (LDS mode)
     __shared__ uint64_t           s_draw[sizeof(Descent) / 8];
-    __shared__ unsigned long long s_part[WR_NT / 64];
+    __shared__ unsigned long long s_part[NT / 64];
     __shared__ int16_t            s_taps[16];
     __shared__ int                s_mode;
     Descent         &D  = *(Descent *)s_draw;
@@ -1331,7 +1343,11 @@ __global__ __launch_bounds__(WR_NT) void wiener_res_kernel(const SearchArgs A, D
     const PlaneArgs &P  = A.pl[A.tiles[A.tile0[u]].plane];
     const int        ux = ur.h_start, uy = ur.v_start + it.y0, w = ur.h_end - ur.h_start, h = it.y1 - it.y0;
     const int        ws = (w + 10) >> 1;
-    const bool       lds = wr_lds_mode(w, h, lds_cap);
+    const bool       lds = wr_lds_mode(w, h, lds_cap, NT, RMAX);
+    if (SMALL && (!lds || it.nparts != 1)) { // never index past the window or the source registers
+        if (threadIdx.x == 0) atomicOr(status, 4);
+        return;
+    }
     if (threadIdx.x == 0) {
         D      = ds[u];
         s_mode = 0;
@@ -1344,7 +1360,7 @@ __global__ __launch_bounds__(WR_NT) void wiener_res_kernel(const SearchArgs A, D
     }
     if (lds) { // stage the edge-clamped window: rows uy-3 .., columns ux-4 .. (pairs)
         const T *d = (const T *)P.dgd;
-        for (int i = threadIdx.x; i < (h + 6) * ws; i += WR_NT) {
+        for (int i = threadIdx.x; i < (h + 6) * ws; i += NT) {
             const int r = i / ws, c = 2 * (i - r * ws);
             const int fy = min(max(uy - 3 + r, 0), P.H - 1), f0 = min(max(ux - 4 + c, 0), P.W - 1),
                       f1 = min(max(ux - 3 + c, 0), P.W - 1);
@@ -1354,11 +1370,37 @@ __global__ __launch_bounds__(WR_NT) void wiener_res_kernel(const SearchArgs A, D
     }
     __syncthreads();
     unsigned long long npx = 0;
-    if (lds) wr_run<T, true>(A, P, D, wr_win, ws, ux, uy, w, h, it, xch, &s_mode, s_taps, s_part, status, npx, stat, classic != 0);
-    else wr_run<T, false>(A, P, D, wr_win, ws, ux, uy, w, h, it, xch, &s_mode, s_taps, s_part, status, npx, stat, classic != 0);
+    if (SMALL || lds)
+        wr_run<T, true, NT, RMAX>(A, P, D, wr_win, ws, ux, uy, w, h, it, xch, &s_mode, s_taps, s_part, status, npx, stat,
+                                  !SMALL && classic != 0);
+    else if constexpr (!SMALL)
+        wr_run<T, false, NT, RMAX>(A, P, D, wr_win, ws, ux, uy, w, h, it, xch, &s_mode, s_taps, s_part, status, npx, stat,
+                                   classic != 0);
     if (threadIdx.x == 0 && it.part == 0) ds[u] = D;
     if (pc && threadIdx.x == 0 && npx) atomicAdd(pc + (blockIdx.x & (PROF_SP - 1)), npx);
     PROF_END(tk);
+}
+
+// the big instance: every unit, one 1024-lane workgroup per CU (the luma window: up to WR_LDS_CAP of LDS)
+template <typename T>
+__global__ __launch_bounds__(WR_NT) void wiener_res_kernel(const SearchArgs A, Descent *ds, const WrItem *items,
+                                                           int lds_cap, unsigned long long *xch, int32_t *status,
+                                                           unsigned long long *pc, unsigned long long *stat,
+                                                           unsigned long long *tk, int classic) {
+    wr_res_body<T, WR_NT, WR_RMAX, false>(A, ds, items, lds_cap, xch, status, pc, stat, tk, classic);
+}
+
+// The small instance: one-part units whose window fits a share of the CU's LDS (a 128 x 128 chroma unit: 37 KB) on NT
+// lanes with RMAX rows per segment -- several workgroups per CU where the big instance holds the whole CU for each.
+// Built as WRS_NT = 256 lanes x WRS_RMAX = 32 rows: four per CU (109 VGPRs at 4 waves per SIMD, 4 x 37 KB).  512 lanes
+// x 16 rows (77 VGPRs, per candidate 4.14 against 4.69 us) lost at four frames in flight: 3808-3817 against 3818-3832
+// Mpixels/s
+constexpr int WRS_NT = 256, WRS_RMAX = 32;
+template <typename T, int NT, int RMAX>
+__global__ __launch_bounds__(NT) void wiener_res_small_kernel(const SearchArgs A, Descent *ds, const WrItem *items,
+                                                              int lds_cap, int32_t *status, unsigned long long *pc,
+                                                              unsigned long long *stat, unsigned long long *tk) {
+    wr_res_body<T, NT, RMAX, true>(A, ds, items, lds_cap, nullptr, status, pc, stat, tk, 0);
 }
 
 // svt_decode_xq (EbRestoration.c:634-646): xq of the ep's absent filter is 0
@@ -1570,7 +1612,8 @@ __global__ void sgr_best_kernel(const Descent *ds, const SearchArgs A, int nplan
 //     outcomes on its path to the root (the per-round path's sgr_tree, one node per lane); lane 0 seeds the descent
 //     from the moments (sgr_seed: the reference's double arithmetic).  Two workgroup barriers per pass, nothing in
 //     global memory, and the pixel waves' registers are never live in the control code;
-//   * units larger than SR_MAX_PX (the frame's bottom luma unit row, 256 x 376 at 4K) are cut into row parts on
+//   * units larger than SR_MAX_PX (34 048 samples: at 4K every 256 x 256 luma unit, two parts, and the bottom luma
+//     unit row, 256 x 376, three) are cut into row parts on
 //     workgroups adjacent in their XCD's dispatch order; their moments and candidate errors meet through uncached
 //     memory each pass (tagged 64-bit words, double-buffered by pass parity, bounded waits), every part taking the
 //     same steps.
@@ -1593,7 +1636,22 @@ constexpr int SR_NT = SVTGPU_SR_NT, SR_PW = SR_NT / 64 - 1, SR_PL = SR_PW * 64, 
 constexpr int SR_LB = 4; // chunks whose loads are in flight together in the load phase
 constexpr int SR_MAX_PX = SR_PL * SR_KMAX * 4;
 constexpr int SR_MAX_PASSES = 4096, SR_MAX_PARTS = 8;
-constexpr int SR_LDS = SR_KMAX * SR_PL * 8; // the (x - src) pairs of the part
+constexpr int sr_lds_bytes(int kmax) { return kmax * SR_PL * 8; } // the (x - src) pairs of the part
+constexpr int SR_LDS = sr_lds_bytes(SR_KMAX);
+// the small instance (sgr_res_small_kernel): one-part items of <= SRS_KMAX chunks per lane, SRS_WGS workgroups per CU
+#ifndef SVTGPU_SRS_KMAX
+#define SVTGPU_SRS_KMAX 10 // a 128 x 128 unit: 4096 chunks over 448 pixel lanes
+#endif
+#ifndef SVTGPU_SRS_WGS
+#define SVTGPU_SRS_WGS 3 // 6 waves per SIMD: 80 VGPRs (at 4, 64 VGPRs, the load phase spilled 54-79 registers)
+#endif
+#ifndef SVTGPU_SRS_LB
+#define SVTGPU_SRS_LB 1 // its load phase's group of chunks in flight (divides SR_LB: sr_pass reads whole groups of SR_LB)
+#endif
+constexpr int SRS_KMAX = SVTGPU_SRS_KMAX, SRS_WGS = SVTGPU_SRS_WGS, SRS_LDS = sr_lds_bytes(SRS_KMAX);
+constexpr int SRS_LB = SVTGPU_SRS_LB;
+static_assert(SR_LB % SRS_LB == 0, "the zero fill up to a multiple of SR_LB goes by load groups");
+static_assert(SRS_KMAX <= SR_KMAX && SRS_WGS * (SRS_LDS + 2048) <= 160 * 1024, "SRS_WGS workgroups share a CU's LDS");
 struct SrItem {
     int32_t pair, y0, y1, part, nparts, first; // rows [y0, y1) of the pair's unit; part q at grid position first + 8 q
 };
@@ -1715,11 +1773,11 @@ __device__ __forceinline__ void sr_tree_publish(const Descent &d, bool live, int
 // The (x - src) pairs are read from LDS four chunks at a time: one LDS latency per group of four chunks instead of
 // one per chunk (the load phase leaves zeros in the chunks from K up to the next multiple of four, so a group never
 // needs a per-chunk guard).  Issuing the next group's reads before the current group spills the load phase's registers.
-template <int NV>
-__device__ __forceinline__ void sr_pass(const uint32_t (&g)[SR_KMAX][4], const uint32_t *dx, int pl, int K, int nv,
+template <int NV, int KMAX> // KMAX: the instance's chunk capacity per lane (deduced from g)
+__device__ __forceinline__ void sr_pass(const uint32_t (&g)[KMAX][4], const uint32_t *dx, int pl, int K, int nv,
                                         const uint32_t *s_xq, unsigned long long (*s_red)[SG_NC]) {
     static_assert(SR_LB == 4, "the load phase zero-fills whole groups of four chunks");
-    constexpr int GS = NV == 1 ? 4 : 1, NG = (SR_KMAX + GS - 1) / GS;
+    constexpr int GS = NV == 1 ? 4 : 1, NG = (KMAX + GS - 1) / GS;
     uint32_t xq[NV], acc[NV];
 #pragma unroll
     // the candidates stay in VGPRs: v_dot2_i32_i16 (VOP3) then takes the rounding constant from an SGPR, with no
@@ -1732,11 +1790,11 @@ __device__ __forceinline__ void sr_pass(const uint32_t (&g)[SR_KMAX][4], const u
             uint2 cur[GS];
 #pragma unroll
             for (int j = 0; j < GS; j++)
-                if (kb + j < SR_KMAX) cur[j] = make_uint2(dx[(kb + j) * SR_PL + pl], dx[(SR_KMAX + kb + j) * SR_PL + pl]);
+                if (kb + j < KMAX) cur[j] = make_uint2(dx[(kb + j) * SR_PL + pl], dx[(KMAX + kb + j) * SR_PL + pl]);
 #pragma unroll
             for (int j = 0; j < GS; j++) {
                 const int kk = kb + j;
-                if (kk >= SR_KMAX) break;
+                if (kk >= KMAX) break;
                 const uint2 dw = cur[j];
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
@@ -1767,457 +1825,30 @@ __global__ __launch_bounds__(SR_NT, 4) void sgr_res_kernel(const SearchArgs A, i
                                                         const SeedCfg cfg, int nodes_arg, Descent *ds,
                                                         unsigned long long *xch, unsigned xmode, int32_t *status,
                                                         unsigned long long *stat, unsigned long long *tk) {
-    PROF_BEGIN(tk);
-    // one node per pass in the default kernel: a compile-time constant there, so the per-lane tree builder (a
-    // divergent Descent copy per lane) is not compiled in and the descent keeps to registers
-    const int nodes = TREE ? nodes_arg : 1;
-    // [half][chunk k][pixel lane]: (x - src) of pixels 0, 1 (half 0) and 2, 3 (half 1), int16 pairs -- two planes of
-    // lane-linear words, the layout the direct global -> LDS loads (SVTGPU_SR_GLDS) write
-    extern __shared__ uint32_t sr_dx[];
-    // wave partials: the moments, then each pass's errors; two buffers by pass parity (the one-barrier path of
-    // one-part items reads a pass's partials while the next pass writes the other buffer)
-    __shared__ unsigned long long s_red2[2][SR_PW][SG_NC];
-    unsigned long long (*const s_red)[SG_NC] = s_red2[0];
-    // one-barrier path: the seeded descent every wave steps itself (raw storage: Descent has member initializers)
-    __shared__ __attribute__((aligned(8))) unsigned char s_desc_raw[sizeof(Descent)];
-    Descent &s_desc = *reinterpret_cast<Descent *>(s_desc_raw);
-    __shared__ unsigned long long s_etot[2]; // self-stepping row parts: each pass's error summed over the parts
-    __shared__ int                s_xok[2];  // ... and whether the exchange succeeded
-    __shared__ uint32_t           s_xq[SG_NC];         // the pending tree's candidates (xq pairs), compacted
-    __shared__ uint32_t           s_mask;              // its nodes
-    __shared__ int                s_nv;                // its candidate count (0: the descent has ended)
-    const SrItem it = items[blockIdx.x];
-    if (it.pair < 0) return; // an empty slot of the XCD-ordered grid (uniform)
-    int p = 0;
-    while (p + 1 < nplanes && it.pair >= A.pl[p + 1].pair_base) p++;
-    const PlaneArgs &P  = A.pl[p];
-    const int        ul = (it.pair - P.pair_base) / P.ne, k = it.pair - P.pair_base - ul * P.ne, ep = P.eps[k];
-    const URect      ur = A.units[P.unit_base + ul];
-    const int        uw = ur.h_end - ur.h_start, cw = (uw + 3) >> 2, nch = cw * (it.y1 - it.y0), K = (nch + SR_PL - 1) / SR_PL;
-    if (K > SR_KMAX || nch <= 0) { // the host plans parts of <= SR_MAX_PX pixels; never index past the registers
-        if (threadIdx.x == 0) atomicOr(status, 4);
-        return;
-    }
-    // the wave's role from a scalar (readfirstlane) condition: the compiler then treats each role's code as uniform
-    // control flow -- with `threadIdx.x < SR_PL` it could not prove the branch wave-uniform and compiled the control
-    // wave's descent steps as exec-masked vector code with scratch traffic
-    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) < SR_PW) {
-        // ================= pixel waves =================
-        const int      pl = threadIdx.x, r0 = c_sgr_r[ep][0], r1 = c_sgr_r[ep][1];
-        const T       *d = (const T *)P.dgd, *s = (const T *)P.src;
-        const size_t   pn = (size_t)P.fstride * P.H;
-        // an ep without one of the filters reads a plane that holds no data: its g half is zeroed
-        const int16_t *f0 = P.flt + (size_t)k * 2 * pn, *f1 = P.flt + (size_t)P.f1e[k] * 2 * pn + pn;
-        const uint32_t gmask = (r0 ? 0x0000FFFFu : 0u) | (r1 ? 0xFFFF0000u : 0u);
-        // ---- load the part: g in registers, (x - src) in LDS, the moments on the way ----
-        // Chunk kk of this lane is chunk c = pl + kk * SR_PL of the part (row-major over 4-sample columns); its
-        // (row, column) advance by a fixed step from one kk to the next (no division per chunk).  Chunks past the part
-        // read the part's last chunk (addresses stay inside) and contribute zeros.
-        const int      dr = SR_PL / cw, dc = SR_PL - dr * cw, lastc = nch - 1, lrow = lastc / cw, lcol = lastc - lrow * cw;
-        int            crow = pl / cw, ccol = pl - crow * cw; // chunk 0 of this lane
-        auto           chunk_at = [&](int kk, int &row, int &col) {   // (row, col) of chunk kk, clamped into the part
-            row = crow, col = ccol;
-            if (pl + kk * SR_PL >= nch) row = lrow, col = lcol;
-        };
-        auto           advance = [&]() {
-            crow += dr, ccol += dc;
-            if (ccol >= cw) ccol -= cw, crow++;
-        };
-        // 1. the ep's two filter planes of every chunk, straight into g (raw int16 pairs: flt0 of pixels 0, 1 | 2, 3
-        //    then flt1 of them): every HBM read of the part in flight at once, one memory round trip per item
-        uint32_t g[SR_KMAX][4];
-#pragma unroll
-        for (int kk = 0; kk < SR_KMAX; kk++) {
-            g[kk][0] = g[kk][1] = g[kk][2] = g[kk][3] = 0u;
-            if (kk < K) { // uniform
-                int row, col;
-                chunk_at(kk, row, col);
-                const size_t fo = (size_t)(ur.v_start + it.y0 + row) * P.fstride + ur.h_start + 4 * col;
-                // an ep without one of the filters (eps 10-15) reads only the other plane (r0 / r1 uniform)
-                const uint2  a0 = r0 ? *(const uint2 *)(f0 + fo) : make_uint2(0u, 0u);
-                const uint2  a1 = r1 ? *(const uint2 *)(f1 + fo) : make_uint2(0u, 0u);
-                g[kk][0] = a0.x, g[kk][1] = a0.y, g[kk][2] = a1.x, g[kk][3] = a1.y;
-                advance();
-            }
-        }
-        // 2. dx = dgd - src (the plane unit_sums_kernel writes; the eps of a unit read it through one L2) in groups of
-        //    SR_LB chunks: the moments, and the (x - src) pairs to LDS.  g (1.) already holds flt - (dgd << 4), so a
-        //    chunk needs two registers here instead of four for the CDEF output and the source: half the round trips
-        crow = pl / cw, ccol = pl - crow * cw;
-        unsigned long long M0 = 0, M1 = 0, M2 = 0, M3 = 0, M4 = 0; // M2..M4 hold signed sums mod 2^64
-#if SVTGPU_SR_GLDS
-        // every chunk's dx straight into its LDS words with direct global -> LDS loads (no registers: one round trip
-        // for the part), then each lane reads its own words back, masks them and forms the moments
-        {
-            uint32_t *lw = sr_dx + (pl & ~63); // the wave's lane-linear base: lane l of the wave lands at lw[l + ...]
-#pragma unroll
-            for (int kk = 0; kk < SR_KMAX; kk++) {
-                if (kk >= K) break; // uniform
-                int row, col;
-                chunk_at(kk, row, col);
-                const int16_t *src = P.dxp + (size_t)(ur.v_start + it.y0 + row) * P.fstride + ur.h_start + 4 * col;
-                __builtin_amdgcn_global_load_lds((const void *)src,
-                                                 (__attribute__((address_space(3))) void *)(lw + kk * SR_PL), 4, 0, 0);
-                __builtin_amdgcn_global_load_lds((const void *)(src + 2),
-                                                 (__attribute__((address_space(3))) void *)(lw + (SR_KMAX + kk) * SR_PL),
-                                                 4, 0, 0);
-                advance();
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        crow = pl / cw, ccol = pl - crow * cw;
-#pragma unroll
-        for (int kk = 0; kk < SR_KMAX; kk++) {
-            if (kk >= K) { // uniform: zeros up to the next multiple of SR_LB (sr_pass reads whole groups)
-                if (kk < ((K + SR_LB - 1) & ~(SR_LB - 1))) sr_dx[kk * SR_PL + pl] = sr_dx[(SR_KMAX + kk) * SR_PL + pl] = 0u;
-                continue;
-            }
-            int row, col;
-            chunk_at(kk, row, col);
-            const int nin = pl + kk * SR_PL < nch ? min(4, uw - 4 * col) : 0;
-            advance();
-            const uint32_t mlo = nin >= 2 ? ~0u : nin == 1 ? 0xFFFFu : 0u;
-            const uint32_t mhi = nin >= 4 ? ~0u : nin == 3 ? 0xFFFFu : 0u;
-            g[kk][0] &= mlo, g[kk][2] &= mlo, g[kk][1] &= mhi, g[kk][3] &= mhi;
-            const uint2 x2 = make_uint2(sr_dx[kk * SR_PL + pl] & mlo, sr_dx[(SR_KMAX + kk) * SR_PL + pl] & mhi);
-            if (nin < 4) sr_dx[kk * SR_PL + pl] = x2.x, sr_dx[(SR_KMAX + kk) * SR_PL + pl] = x2.y;
-            const int      dxq[4] = {(int)(int16_t)(x2.x & 0xFFFF), (int)x2.x >> 16, (int)(int16_t)(x2.y & 0xFFFF),
-                                     (int)x2.y >> 16};
-            const uint32_t fw[4] = {__builtin_amdgcn_perm(g[kk][2], g[kk][0], 0x05040100u),
-                                    __builtin_amdgcn_perm(g[kk][2], g[kk][0], 0x07060302u),
-                                    __builtin_amdgcn_perm(g[kk][3], g[kk][1], 0x05040100u),
-                                    __builtin_amdgcn_perm(g[kk][3], g[kk][1], 0x07060302u)};
-            uint32_t m0 = 0, m1 = 0;
-            int      m3 = 0, m4 = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint32_t gq = fw[q] & gmask;
-                const int      g1 = (int)(int16_t)(gq & 0xFFFF), g2 = (int)gq >> 16, ss = -(dxq[q] << 4);
-                m0 += (uint32_t)(g1 * g1), m1 += (uint32_t)(g2 * g2);
-                m3 += g1 * ss, m4 += g2 * ss;
-                M2 += (unsigned long long)(long long)(g1 * g2);
-                g[kk][q] = gq;
-            }
-            M0 += m0, M1 += m1, M3 += (unsigned long long)(long long)m3, M4 += (unsigned long long)(long long)m4;
-        }
-#else
-        constexpr int LB2 = SR_LB;
-#pragma unroll
-        for (int kb = 0; kb < SR_KMAX; kb += LB2) {
-            if (kb >= K) { // uniform: zeros up to the next multiple of SR_LB (sr_pass reads whole groups)
-                if (kb < ((K + SR_LB - 1) & ~(SR_LB - 1)))
-#pragma unroll
-                    for (int j = 0; j < LB2; j++)
-                        if (kb + j < SR_KMAX) sr_dx[(kb + j) * SR_PL + pl] = sr_dx[(SR_KMAX + kb + j) * SR_PL + pl] = 0u;
-                continue;
-            }
-            uint2 xv[LB2];
-            int   nin[LB2]; // the chunk's pixels inside the part: 4, fewer in the last column of a crop width that is
-                            // not a multiple of 4, none past the part
-#pragma unroll
-            for (int j = 0; j < LB2; j++) { // the group's loads in flight together
-                xv[j] = make_uint2(0u, 0u), nin[j] = 0;
-                if (kb + j >= SR_KMAX) continue;
-                int row, col;
-                chunk_at(kb + j, row, col);
-                nin[j]      = pl + (kb + j) * SR_PL < nch ? min(4, uw - 4 * col) : 0;
-                const int y = ur.v_start + it.y0 + row, x = ur.h_start + 4 * col;
-                xv[j]       = *(const uint2 *)(P.dxp + (size_t)y * P.fstride + x);
-                advance();
-            }
-#pragma unroll
-            for (int j = 0; j < LB2; j++) {
-                const int kk = kb + j;
-                if (kk >= SR_KMAX) break;
-                // pixels outside the part read as zeros everywhere: g = 0 and (x - src) = 0 add nothing to any sum
-                const uint32_t mlo = nin[j] >= 2 ? ~0u : nin[j] == 1 ? 0xFFFFu : 0u;
-                const uint32_t mhi = nin[j] >= 4 ? ~0u : nin[j] == 3 ? 0xFFFFu : 0u;
-                g[kk][0] &= mlo, g[kk][2] &= mlo, g[kk][1] &= mhi, g[kk][3] &= mhi;
-                const uint2    x2 = make_uint2(xv[j].x & mlo, xv[j].y & mhi);
-                const int      dxq[4] = {(int)(int16_t)(x2.x & 0xFFFF), (int)x2.x >> 16, (int)(int16_t)(x2.y & 0xFFFF),
-                                         (int)x2.y >> 16};
-                const uint32_t fw[4] = {__builtin_amdgcn_perm(g[kk][2], g[kk][0], 0x05040100u),
-                                        __builtin_amdgcn_perm(g[kk][2], g[kk][0], 0x07060302u),
-                                        __builtin_amdgcn_perm(g[kk][3], g[kk][1], 0x05040100u),
-                                        __builtin_amdgcn_perm(g[kk][3], g[kk][1], 0x07060302u)};
-                uint32_t m0 = 0, m1 = 0; // <= 4 g^2 < 2^32
-                int      m3 = 0, m4 = 0; // |4 g s| < 2^31
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t gq = fw[q] & gmask; // (flt0 - u, flt1 - u); an ep's absent filter reads as 0
-                    const int      g1 = (int)(int16_t)(gq & 0xFFFF), g2 = (int)gq >> 16, ss = -(dxq[q] << 4);
-                    m0 += (uint32_t)(g1 * g1), m1 += (uint32_t)(g2 * g2);
-                    m3 += g1 * ss, m4 += g2 * ss;
-                    M2 += (unsigned long long)(long long)(g1 * g2);
-                    g[kk][q] = gq;
-                }
-                M0 += m0, M1 += m1, M3 += (unsigned long long)(long long)m3, M4 += (unsigned long long)(long long)m4;
-                sr_dx[kk * SR_PL + pl] = x2.x, sr_dx[(SR_KMAX + kk) * SR_PL + pl] = x2.y;
-            }
-        }
-#endif
-        {
-            const unsigned long long t[5] = {wave_sum_u64_limbs(M0), wave_sum_u64_limbs(M1), wave_sum_u64_limbs(M2),
-                                             wave_sum_u64_limbs(M3), wave_sum_u64_limbs(M4)};
-            if ((pl & 63) == WAVE_LAST)
-#pragma unroll
-                for (int q = 0; q < 5; q++) s_red[pl >> 6][q] = t[q];
-        }
-        __syncthreads(); // B1: the moments are in s_red
-        __syncthreads(); // B2: the first tree is in s_xq
-        // diagnostics (stat): pixel wave 0's pass time (B2/B4 release to its arrival at B3) and its wait from B3 to the
-        // B4 release
-        unsigned long long tpass = 0, twait = 0, tmark = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-        if (!TREE && it.nparts == 1 && !(xmode & 0x200)) {
-            // One barrier per pass, and no wave waits on another's descent step: every wave (pixel and control) holds
-            // the seeded descent in its own scalar registers and steps it itself from the pass's wave partials --
-            // report + next once per pass, the same decisions everywhere (the errors are the same LDS words).  Before
-            // this the control wave stepped the descent and built both children of every candidate (three steps per
-            // pass, serial) while the pixel waves waited at the barrier: 13 us of descent per item, 8 of them control
-            Descent  Dw   = uniform(s_desc);
-            bool     live = __builtin_amdgcn_readfirstlane(s_nv) != 0;
-            uint32_t xq   = 0;
-            {
-                int32_t x[2];
-                decode_xq(Dw, x);
-                xq = __builtin_amdgcn_readfirstlane(pack2(x[0], x[1]));
-            }
-            for (int pass = 1; live; pass++) {
-                const uint32_t xl[1] = {xq};
-                sr_pass<1>(g, sr_dx, pl, K, 1, xl, s_red2[pass & 1]);
-                if (stat) {
-                    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-                    tpass += t - tmark, tmark = t;
-                }
-                __syncthreads(); // B3: the pass's wave partials are in LDS
-                unsigned long long e0 = 0;
-#pragma unroll
-                for (int w = 0; w < SR_PW; w++) e0 += s_red2[pass & 1][w][0];
-                Dw.report(readlane64((long long)e0, 0));
-                live = Dw.next() && pass <= SR_MAX_PASSES;
-                if (live) {
-                    int32_t x[2];
-                    decode_xq(Dw, x);
-                    xq = __builtin_amdgcn_readfirstlane(pack2(x[0], x[1]));
-                }
-                if (stat) {
-                    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-                    twait += t - tmark, tmark = t;
-                }
-            }
-        } else if (!TREE && !(xmode & 0x200)) {
-            // Row parts, self-stepping: the control wave sums this part's wave partials, exchanges the sum with the
-            // other parts and leaves the frame-unit total in LDS (B4); then every wave steps its own copy of the
-            // descent -- no children built, no wave waits on another's step
-            Descent  Dw   = uniform(s_desc);
-            bool     live = __builtin_amdgcn_readfirstlane(s_nv) != 0;
-            uint32_t xq   = 0;
-            {
-                int32_t x[2];
-                decode_xq(Dw, x);
-                xq = __builtin_amdgcn_readfirstlane(pack2(x[0], x[1]));
-            }
-            for (int pass = 1; live; pass++) {
-                const uint32_t xl[1] = {xq};
-                sr_pass<1>(g, sr_dx, pl, K, 1, xl, s_red);
-                if (stat) {
-                    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-                    tpass += t - tmark, tmark = t;
-                }
-                __syncthreads(); // B3: the pass's wave partials are in s_red
-                __syncthreads(); // B4: the parts' total is in s_etot
-                const bool okx = __builtin_amdgcn_readfirstlane(s_xok[pass & 1]) != 0;
-                if (okx) {
-                    Dw.report(readlane64((long long)s_etot[pass & 1], 0));
-                    live = Dw.next() && pass <= SR_MAX_PASSES;
-                } else
-                    live = false;
-                if (live) {
-                    int32_t x[2];
-                    decode_xq(Dw, x);
-                    xq = __builtin_amdgcn_readfirstlane(pack2(x[0], x[1]));
-                }
-                if (stat) {
-                    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-                    twait += t - tmark, tmark = t;
-                }
-            }
-        } else
-        for (;;) {
-            const int nv = __builtin_amdgcn_readfirstlane(s_nv);
-            if (nv == 0) break;
-            if constexpr (!TREE) {
-                sr_pass<1>(g, sr_dx, pl, K, 1, s_xq, s_red);
-            } else {
-                switch (nv) {
-                case 1: sr_pass<1>(g, sr_dx, pl, K, nv, s_xq, s_red); break;
-                case 2: sr_pass<2>(g, sr_dx, pl, K, nv, s_xq, s_red); break;
-                case 3: sr_pass<3>(g, sr_dx, pl, K, nv, s_xq, s_red); break;
-                case 4: sr_pass<4>(g, sr_dx, pl, K, nv, s_xq, s_red); break;
-                default: sr_pass<SG_NC>(g, sr_dx, pl, K, nv, s_xq, s_red); break;
-                }
-            }
-            if (stat) {
-                const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-                tpass += t - tmark, tmark = t;
-            }
-            __syncthreads(); // B3: the pass's errors are in s_red
-            __syncthreads(); // B4: the next tree (or the end) is in s_xq / s_nv
-            if (stat) {
-                const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-                twait += t - tmark, tmark = t;
-            }
-        }
-        if (stat && pl == 0) atomicAdd(stat + 7, tpass), atomicAdd(stat + 8, twait);
-    } else {
-        // ================= control wave =================
-        // stat (SVTGPU_SR_STATS diagnostics, else null): items, passes, candidate-pixels, load / descent / control
-        // ticks (100 MHz), pixels.  The control steps are the item's serial critical path: this wave issues ahead of
-        // the other workgroup's pixel waves on its SIMD (it waits at the barriers otherwise)
-        __builtin_amdgcn_s_setprio(3);
-        const int                lane = threadIdx.x & 63;
-        const unsigned long long t0   = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-        unsigned long long       tctl = 0, ncp = 0, tpre = 0;
-        __syncthreads(); // B1
-        const unsigned long long t1 = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-        long long v  = 0; // lane q < 5: moment q over the workgroup (and the other row parts)
-        bool      ok = true;
-        if (lane < 5) {
-            unsigned long long t = 0;
-            for (int w = 0; w < SR_PW; w++) t += s_red[w][lane];
-            v = (long long)t;
-            if (it.nparts > 1) ok = sr_exchange_lane(xch, it, 0, lane, v, status, xmode);
-        }
-        ok = __ballot(!ok) == 0;
-        long long mv[5];
-#pragma unroll
-        for (int q = 0; q < 5; q++) mv[q] = readlane64(v, q);
-        // the descent is wave-uniform from here on: kept in scalar registers, stepped by the scalar unit
-        Descent D = uniform(sgr_seed(A, p, it.pair, (const int64_t *)mv, cfg));
-        D.next(); // the seed itself is the first candidate
-        sr_tree_publish(D, ok, nodes, s_xq, &s_mask, &s_nv);
-        if (!TREE && it.nparts == 1 && !(xmode & 0x200)) {
-            // the self-stepping path (see the pixel waves): the seeded descent to LDS for every wave, then the same
-            // report + next per pass as everyone else
-            if (lane == 0) s_desc = D;
-            __syncthreads(); // B2
-            bool live = ok;
-            int  pass = 1;
-            for (; live; pass++) {
-                __syncthreads(); // B3
-                const unsigned long long tb = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-                ncp += (unsigned long long)nch * 4;
-                unsigned long long e0 = 0;
-#pragma unroll
-                for (int w = 0; w < SR_PW; w++) e0 += s_red2[pass & 1][w][0];
-                D.report(readlane64((long long)e0, 0));
-                live = D.next() && pass <= SR_MAX_PASSES;
-                if (pass > SR_MAX_PASSES && lane == 0) atomicOr(status, 1);
-                if (stat) tctl += __builtin_amdgcn_s_memrealtime() - tb;
-            }
-            if (stat && lane == 0) atomicAdd(stat + 1, (unsigned long long)(pass - 1));
-        } else if (!TREE && nodes == 1 && !(xmode & 0x200)) {
-            // self-stepping row parts (see the pixel waves): the exchange between B3 and B4, the step after B4
-            if (lane == 0) s_desc = D;
-            __syncthreads(); // B2
-            bool live = ok;
-            int  pass = 1;
-            for (; live; pass++) {
-                __syncthreads(); // B3
-                const unsigned long long tb = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-                ncp += (unsigned long long)nch * 4;
-                if (lane == 0) {
-                    unsigned long long t = 0;
-                    for (int w = 0; w < SR_PW; w++) t += s_red[w][0];
-                    long long e   = (long long)t;
-                    const bool ex = sr_exchange_lane(xch, it, pass, 0, e, status, xmode);
-                    s_etot[pass & 1] = (unsigned long long)e, s_xok[pass & 1] = ex;
-                }
-                __syncthreads(); // B4
-                const bool okx = __builtin_amdgcn_readfirstlane(s_xok[pass & 1]) != 0;
-                if (okx) {
-                    D.report(readlane64((long long)s_etot[pass & 1], 0));
-                    live = D.next() && pass <= SR_MAX_PASSES;
-                    if (pass > SR_MAX_PASSES && lane == 0) atomicOr(status, 1);
-                } else
-                    live = false;
-                if (stat) tctl += __builtin_amdgcn_s_memrealtime() - tb;
-            }
-            if (stat && lane == 0) atomicAdd(stat + 1, (unsigned long long)(pass - 1));
-        } else {
-        __syncthreads(); // B2
-        for (int pass = 1;; pass++) {
-            const int nv = __builtin_amdgcn_readfirstlane(s_nv);
-            if (nv == 0) break;
-            const uint32_t mask = __builtin_amdgcn_readfirstlane(s_mask);
-            uint32_t       xw = 0, xb = 0;
-            bool           okw = false, okb = false;
-            const unsigned long long tc0 = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-            if (nodes == 1) sr_children(D, xw, okw, xb, okb); // during the pass
-            if (stat) tpre += __builtin_amdgcn_s_memrealtime() - tc0;
-            __syncthreads(); // B3
-            const unsigned long long tb = stat ? __builtin_amdgcn_s_memrealtime() : 0;
-            ncp += (unsigned long long)nv * nch * 4;
-            long long e = 0; // lane c < nv: compacted candidate c's error
-            ok = true;
-            if (lane < nv) {
-                unsigned long long t = 0;
-                for (int w = 0; w < SR_PW; w++) t += s_red[w][lane];
-                e = (long long)t;
-                if (it.nparts > 1) ok = sr_exchange_lane(xch, it, pass, lane, e, status, xmode);
-            }
-            ok = __ballot(!ok) == 0;
-            if (pass > SR_MAX_PASSES) {
-                if (lane == 0) atomicOr(status, 1);
-                ok = false;
-            }
-            if (nodes == 1) { // the outcome picks a prepared child; the descent itself steps after the barrier
-                const long long e0    = readlane64(e, 0);
-                const bool      worse = !D.init && e0 > D.err;
-                if (lane == 0) {
-                    s_xq[0] = worse ? xw : xb;
-                    s_mask  = 1;
-                    s_nv    = ok && (worse ? okw : okb) ? 1 : 0;
-                }
-                if (stat) tctl += __builtin_amdgcn_s_memrealtime() - tb;
-                __syncthreads(); // B4
-                if (stat && lane == 0 && s_nv == 0) atomicAdd(stat + 1, (unsigned long long)pass);
-                if (ok) { // the same state change as the choice above, with the error value kept
-                    D.report(e0);
-                    D.next();
-                }
-                continue;
-            }
-            if (ok) { // the same steps in every lane (the errors made uniform: scalar code)
-                long long ev[SG_NC];
-#pragma unroll
-                for (int c = 0; c < SG_NC; c++) ev[c] = c < nv ? readlane64(e, c) : 0;
-                sgr_replay(D, mask, [&](int node) {
-                    const int i = __popc(mask & ((1u << node) - 1));
-                    long long r = ev[0];
-#pragma unroll
-                    for (int c = 1; c < SG_NC; c++) r = i == c ? ev[c] : r;
-                    return (int64_t)r;
-                });
-            }
-            sr_tree_publish(D, ok && !D.done, nodes, s_xq, &s_mask, &s_nv);
-            if (stat) tctl += __builtin_amdgcn_s_memrealtime() - tb;
-            __syncthreads(); // B4
-            if (stat && lane == 0 && s_nv == 0) atomicAdd(stat + 1, (unsigned long long)pass);
-        }
-        }
-        if (lane == 0 && it.part == 0) ds[it.pair] = D;
-        if (stat && lane == 0) {
-            const unsigned long long te = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(stat + 0, 1ull), atomicAdd(stat + 2, ncp), atomicAdd(stat + 3, t1 - t0);
-            atomicAdd(stat + 4, te - t1), atomicAdd(stat + 5, tctl);
-            atomicAdd(stat + 6, (unsigned long long)nch * 4), atomicAdd(stat + 9, tpre);
-            if (it.nparts > 1) // the row-part items apart: count, load, descent, control ticks
-                atomicAdd(stat + 10, 1ull), atomicAdd(stat + 11, t1 - t0), atomicAdd(stat + 12, te - t1),
-                    atomicAdd(stat + 13, tctl);
-        }
-    }
-    PROF_END(tk);
+    // the big instance: every item up to SR_KMAX chunks per lane, row parts and the TREE variants included -- two
+    // workgroups per CU (76 VGPRs of g in a 128-VGPR budget, 68 KB of LDS)
+    // sgr_res_body.h reads, besides T and TREE: A, nplanes, items, cfg, nodes_arg, ds, xch, xmode, status, stat, tk
+    // (the parameters) and KMAX, ONE
+    constexpr int  KMAX = SR_KMAX;
+    constexpr bool ONE  = false;
+#include "sgr_res_body.h"
+}
+
+// The small instance: one-part items of at most SRS_KMAX chunks per lane (a 128 x 128 chroma unit: K = 10) on the
+// default one-barrier path -- 40 VGPRs of g and 35 KB of LDS, SRS_WGS workgroups per CU: the items are latency chains
+// (load round trips, then ~7 passes of pass + barrier + step), so more of them resident per CU is what keeps its
+// SIMDs issuing while each waits
+template <typename T>
+__global__ __launch_bounds__(SR_NT, SRS_WGS * (SR_NT / 64) / 4) void sgr_res_small_kernel(
+    const SearchArgs A, int nplanes, const SrItem *items, const SeedCfg cfg, Descent *ds, int32_t *status,
+    unsigned long long *stat, unsigned long long *tk) {
+    // the names sgr_res_body.h reads that are no parameter here (see sgr_res_kernel): constants, so that the row-part
+    // exchange, the tree and the two-barrier paths fold away
+    constexpr int       KMAX = SRS_KMAX, nodes_arg = 1;
+    constexpr bool      ONE = true, TREE = false;
+    constexpr unsigned  xmode = 0;
+    unsigned long long *const xch = nullptr;
+#include "sgr_res_body.h"
 }
 
 struct Carver {
@@ -2837,6 +2468,17 @@ int wr_lds_cap() {
     return v;
 }
 
+// lanes of the small Wiener instance (wiener_res_small_kernel); 0: every unit on the big instance, which
+// SVTGPU_WR_CLASSIC=1 (thread 0's step: not in the small instance) and SVTGPU_WR_SMALL=0 (A/B, and the per-item
+// clocks of the small-size units there) ask for
+int wr_small_nt() {
+    static const int v = [] {
+        const char *c = std::getenv("SVTGPU_WR_CLASSIC"), *e = std::getenv("SVTGPU_WR_SMALL");
+        return (c && std::atoi(c) != 0) || (e && !std::strcmp(e, "0")) ? 0 : WRS_NT;
+    }();
+    return v;
+}
+
 // largest row part of the resident self-guided search (pixels); SVTGPU_SR_PART_PX lowers it (tests of the parted path)
 int sr_part_px() {
     static const int v = [] {
@@ -2856,6 +2498,26 @@ int sr_tree_nodes() {
         const char *e = std::getenv("SVTGPU_SR_TREE");
         const int   n = e ? std::atoi(e) : 1;
         return n == 3 || n == 7 ? n : 1;
+    }();
+    return v;
+}
+
+// SVTGPU_SR_1B=0 (A/B): every item on the two-barrier path, the control wave stepping the descent alone (round 3's form)
+bool sr_two_barriers() {
+    static const bool v = [] {
+        const char *e = std::getenv("SVTGPU_SR_1B");
+        return e && !std::strcmp(e, "0");
+    }();
+    return v;
+}
+
+// whether small one-part items run on sgr_res_small_kernel: the default path only (one candidate per pass, one
+// barrier); SVTGPU_SR_SMALL=0 keeps every item on the big instance (A/B, and the per-item clocks of the small-size
+// items there)
+bool sr_small_enabled() {
+    static const bool v = [] {
+        const char *e = std::getenv("SVTGPU_SR_SMALL");
+        return !(e && !std::strcmp(e, "0")) && sr_tree_nodes() == 1 && !sr_two_barriers();
     }();
     return v;
 }
@@ -3059,12 +2721,17 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
     // The resident Wiener kernel takes every unit up to 384 columns wide (unit sizes <= 256): a unit is cut into the
     // fewest row parts that fit one CU's LDS and registers each (global-memory mode when no cut up to WR_MAX_PARTS
     // does); workgroups start with the largest parts (the longest chains), the parts of a unit adjacent.
+    // Each unit is routed by its own size: a one-part unit whose window and rows fit the small instance
+    // (wiener_res_small_kernel: several workgroups per CU) goes there, every other unit to the big one; wr_items holds
+    // the big instance's items, then the small one's, each largest first, and each launch's LDS is its own items' maximum
     std::vector<WrItem> wr_items;
     bool                wr_parted = false;
-    int                 wr_lds = 0;
+    int                 wr_lds = 0, wrs_lds = 0, n_wrb = 0;
+    const int           wrs_nt = wr_small_nt(), wrs_rmax = WRS_RMAX;
     {
         std::vector<int> ord(n_wn);
         std::vector<int> np(n_wn, 1);
+        std::vector<char> small(n_wn, 0);
         for (int u = 0; u < n_wn; u++) {
             const URect &r = units[u];
             const int    w = r.h_end - r.h_start, h = r.v_end - r.v_start;
@@ -3074,16 +2741,22 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
             np[u] = wr_lds_mode(w, (h + k - 1) / k, wr_lds_cap()) ? k : 1;
             if (np[u] > 1) wr_parted = true;
             const int hp = (h + np[u] - 1) / np[u];
-            if (wr_lds_mode(w, hp, wr_lds_cap())) wr_lds = std::max(wr_lds, wr_window_bytes(w, hp));
+            small[u]     = wrs_nt && np[u] == 1 && wr_lds_mode(w, h, std::min(WRS_LDS_CAP, wr_lds_cap()), wrs_nt, wrs_rmax);
+            if (small[u]) wrs_lds = std::max(wrs_lds, wr_window_bytes(w, h));
+            else if (wr_lds_mode(w, hp, wr_lds_cap())) wr_lds = std::max(wr_lds, wr_window_bytes(w, hp));
         }
         auto part_area = [&](int u) {
             return (units[u].h_end - units[u].h_start) * ((units[u].v_end - units[u].v_start + np[u] - 1) / np[u]);
         };
         std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return part_area(a) > part_area(b); });
-        for (int u : ord) {
-            const int h = units[u].v_end - units[u].v_start, first = (int)wr_items.size();
-            for (int k = 0; k < np[u]; k++)
-                wr_items.push_back({u, h * k / np[u], h * (k + 1) / np[u], k, np[u], first});
+        for (int cls = 0; cls < 2; cls++) {
+            for (int u : ord) {
+                if (small[u] != cls) continue;
+                const int h = units[u].v_end - units[u].v_start, first = (int)wr_items.size();
+                for (int k = 0; k < np[u]; k++)
+                    wr_items.push_back({u, h * k / np[u], h * (k + 1) / np[u], k, np[u], first});
+            }
+            if (cls == 0) n_wrb = (int)wr_items.size();
         }
     }
     const int n_wr = (int)wr_items.size();
@@ -3093,11 +2766,16 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
     // read its CDEF and source samples through one L2, and the parts of an item sit next to each other in their XCD's
     // in-order dispatch, so a waiting part's partners are always dispatched after it (never behind other waiting
     // parts).  Units are dealt largest first to the lane with the least work; empty slots (pair -1) pad the lanes.
+    // Each unit is routed by its own size: a one-part unit of at most SRS_KMAX chunks per lane goes to the small
+    // instance (sgr_res_small_kernel: more workgroups per CU), every other unit to the big one.  Each instance's grid
+    // has the 8-lane layout within itself; sr_items holds the big grid, then the small one (first: a position in the
+    // item's own grid -- the exchange words are the big instance's alone).
     std::vector<SrItem>  sr_items;
     bool                 sr_parted = false;
+    int                  n_srb = 0; // the big instance's grid; the small one's is the rest of sr_items
     if (npairs) {
-        std::vector<std::vector<SrItem>> lanes(8);
-        std::vector<long long>           load(8, 0);
+        std::vector<std::vector<SrItem>> lanes[2] = {std::vector<std::vector<SrItem>>(8), std::vector<std::vector<SrItem>>(8)};
+        std::vector<long long>           load[2] = {std::vector<long long>(8, 0), std::vector<long long>(8, 0)};
         std::vector<int>                 ord;
         for (int p = 0; p < nplanes; p++)
             if (pp[p].sg)
@@ -3112,24 +2790,29 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
             const int        maxrows = std::max(1, sr_part_px() / 4 / std::max(cw, 1)), np = (h + maxrows - 1) / maxrows;
             if (np > SR_MAX_PARTS) return SVTGPU_ERR_UNSUPPORTED; // a unit wider than 1024 x 4 samples per row part
             sr_parted |= np > 1;
-            const int lane = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+            const int cls  = sr_small_enabled() && np == 1 && (cw * h + SR_PL - 1) / SR_PL <= SRS_KMAX;
+            const int lane = (int)(std::min_element(load[cls].begin(), load[cls].end()) - load[cls].begin());
             for (int k = 0; k < q.ne; k++) {
-                const int first = (int)lanes[lane].size(); // lane-local; made global below
+                const int first = (int)lanes[cls][lane].size(); // lane-local; made global below
                 for (int part = 0; part < np; part++)
-                    lanes[lane].push_back({q.pair_base + (u - q.unit_base) * q.ne + k, h * part / np, h * (part + 1) / np,
-                                           part, np, first});
+                    lanes[cls][lane].push_back({q.pair_base + (u - q.unit_base) * q.ne + k, h * part / np,
+                                                h * (part + 1) / np, part, np, first});
             }
-            load[lane] += area(u) * q.ne;
+            load[cls][lane] += area(u) * q.ne;
         }
-        size_t len = 0;
-        for (auto &l : lanes) len = std::max(len, l.size());
-        sr_items.assign(8 * len, SrItem{-1, 0, 0, 0, 1, 0});
-        for (int r = 0; r < 8; r++)
-            for (size_t m = 0; m < lanes[r].size(); m++) {
-                SrItem it = lanes[r][m];
-                it.first  = 8 * it.first + r; // parts of an item: positions first, first + 8, ...
-                sr_items[8 * m + r] = it;
-            }
+        for (int cls = 0; cls < 2; cls++) {
+            size_t len = 0;
+            for (auto &l : lanes[cls]) len = std::max(len, l.size());
+            const size_t base = sr_items.size();
+            sr_items.resize(base + 8 * len, SrItem{-1, 0, 0, 0, 1, 0});
+            for (int r = 0; r < 8; r++)
+                for (size_t m = 0; m < lanes[cls][r].size(); m++) {
+                    SrItem it = lanes[cls][r][m];
+                    it.first  = 8 * it.first + r; // parts of an item: positions first, first + 8, ...
+                    sr_items[base + 8 * m + r] = it;
+                }
+            if (cls == 0) n_srb = (int)sr_items.size();
+        }
     }
     const int n_sr = (int)sr_items.size();
     // ---- device scratch and pinned staging ----
@@ -3283,23 +2966,20 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
         }
         sr_xmode = 0x100u | (s->sx_epoch & 0xFFu);
     }
-    static const bool sr_two_barriers = [] { // SVTGPU_SR_1B=0 (A/B): every item on the two-barrier path, the control
-        const char *e = std::getenv("SVTGPU_SR_1B"); // wave stepping the descent alone (round 3's form)
-        return e && !std::strcmp(e, "0");
-    }();
-    if (sr_two_barriers) sr_xmode |= 0x200u;
+    if (sr_two_barriers()) sr_xmode |= 0x200u;
     static const bool wr_classic = [] { // SVTGPU_WR_CLASSIC=1 (A/B): the round-4 Wiener step (thread 0, two barriers)
         const char *e = std::getenv("SVTGPU_WR_CLASSIC");
         return e && std::atoi(e) != 0;
     }();
     static const bool   wr_stats = std::getenv("SVTGPU_WR_STATS") != nullptr; // per-search diagnostics to stderr
     static unsigned long long *wr_stat = nullptr;
-    if (wr_stats && !wr_stat) HIP_TRY(hipMalloc(&wr_stat, 128));
-    if (wr_stat) HIP_TRY(hipMemsetAsync(wr_stat, 0, 128, st));
+    if (wr_stats && !wr_stat) HIP_TRY(hipMalloc(&wr_stat, 256)); // 16 words per instance: the big one's, the small one's
+    if (wr_stat) HIP_TRY(hipMemsetAsync(wr_stat, 0, 256, st));
     static const bool   sr_stats = std::getenv("SVTGPU_SR_STATS") != nullptr; // per-search diagnostics to stderr
     static unsigned long long *sr_stat = nullptr;
-    if (sr_stats && !sr_stat) HIP_TRY(hipMalloc(&sr_stat, 128));
-    if (sr_stat) HIP_TRY(hipMemsetAsync(sr_stat, 0, 128, st));
+    constexpr int SR_NSTAT = 32; // words per instance: the big one's, then the small one's
+    if (sr_stats && !sr_stat) HIP_TRY(hipMalloc(&sr_stat, 2 * 8 * SR_NSTAT));
+    if (sr_stat) HIP_TRY(hipMemsetAsync(sr_stat, 0, 2 * 8 * SR_NSTAT, st));
     run(0, st, [&](unsigned long long *tk) {
         hipLaunchKernelGGL(unit_sums_kernel<T>, dim3(nt_all), dim3(256), 0, st, A, (unsigned long long *)dp(o_sum),
                            (unsigned long long *)dp(o_sse), tk);
@@ -3353,22 +3033,46 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
     mark(1);
     // ---- phase 3: descent rounds on the device ----
     if (n_wn) { // the whole Wiener descent of every unit, resident on one CU each (or a few, for the largest)
-        run(2, sw, [&](unsigned long long *tk) {
-            hipLaunchKernelGGL(wiener_res_kernel<T>, dim3(n_wr), dim3(WR_NT), wr_lds, sw, A, (Descent *)dp(o_wds),
-                               (const WrItem *)dp(o_witem), wr_lds, (unsigned long long *)(qa ? qa + q_wrx : nullptr),
-                               (int32_t *)dp(o_wstat), pc, wr_stat, tk, (int)wr_classic);
-        });
+        // the two instances back to back on the Wiener stream, each only if it has items, the big one (the long chains)
+        // first; both under the trial class
+        if (n_wrb)
+            run(2, sw, [&](unsigned long long *tk) {
+                hipLaunchKernelGGL(wiener_res_kernel<T>, dim3(n_wrb), dim3(WR_NT), wr_lds, sw, A, (Descent *)dp(o_wds),
+                                   (const WrItem *)dp(o_witem), wr_lds, (unsigned long long *)(qa ? qa + q_wrx : nullptr),
+                                   (int32_t *)dp(o_wstat), pc, wr_stat, tk, (int)wr_classic);
+            });
+        if (n_wr > n_wrb)
+            run(2, sw, [&](unsigned long long *tk) {
+                hipLaunchKernelGGL((wiener_res_small_kernel<T, WRS_NT, WRS_RMAX>), dim3(n_wr - n_wrb), dim3(wrs_nt), wrs_lds, sw, A, (Descent *)dp(o_wds),
+                                   (const WrItem *)dp(o_witem) + n_wrb, wrs_lds, (int32_t *)dp(o_wstat), pc,
+                                   wr_stat ? wr_stat + 16 : nullptr, tk);
+            });
         HIP_TRY(hipGetLastError());
     }
     if (n_sr) { // the whole self-guided search of every (unit, ep), resident on one CU each (or a few)
-        run(3, st, [&](unsigned long long *tk) {
-            const int nodes = sr_tree_nodes();
-            auto kern = nodes == 1 ? sgr_res_kernel<T, false> : sgr_res_kernel<T, true>;
-            hipLaunchKernelGGL(kern, dim3(n_sr), dim3(SR_NT), SR_LDS, st, A, sg_planes,
-                               (const SrItem *)dp(o_sritem), cfg, nodes, (Descent *)dp(o_sds),
-                               (unsigned long long *)(sr_parted ? (sr_l2 ? (uint8_t *)s->d_sxarena : qa + q_srx) : nullptr),
-                               sr_xmode, (int32_t *)dp(o_sstat), sr_stat, tk);
-        });
+        // the two instances back to back on this stream, each only if it has items (both under the projection class);
+        // the big instance first: its items are the long chains (small first measured the same: 3717-3723 against
+        // 3718-3732 Mpixels/s)
+        auto big = [&] {
+            if (n_srb)
+                run(3, st, [&](unsigned long long *tk) {
+                    const int nodes = sr_tree_nodes();
+                    auto kern = nodes == 1 ? sgr_res_kernel<T, false> : sgr_res_kernel<T, true>;
+                    hipLaunchKernelGGL(kern, dim3(n_srb), dim3(SR_NT), SR_LDS, st, A, sg_planes,
+                                       (const SrItem *)dp(o_sritem), cfg, nodes, (Descent *)dp(o_sds),
+                                       (unsigned long long *)(sr_parted ? (sr_l2 ? (uint8_t *)s->d_sxarena : qa + q_srx) : nullptr),
+                                       sr_xmode, (int32_t *)dp(o_sstat), sr_stat, tk);
+                });
+        };
+        auto small = [&] {
+            if (n_sr > n_srb)
+                run(3, st, [&](unsigned long long *tk) {
+                    hipLaunchKernelGGL(sgr_res_small_kernel<T>, dim3(n_sr - n_srb), dim3(SR_NT), SRS_LDS, st, A, sg_planes,
+                                       (const SrItem *)dp(o_sritem) + n_srb, cfg, (Descent *)dp(o_sds),
+                                       (int32_t *)dp(o_sstat), sr_stat ? sr_stat + SR_NSTAT : nullptr, tk);
+                });
+        };
+        big(), small();
         HIP_TRY(hipGetLastError());
     }
     mark(2);
@@ -3489,19 +3193,33 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
                                   __FILE__, __LINE__);
         return SVTGPU_ERR_HIP;
     }
-    if (n_wr && wr_stat) {
+    for (int inst = 0; inst < 2 && n_wr && wr_stat; inst++) { // the big instance, then the small one
+        if (inst == 0 ? n_wrb == 0 : n_wr == n_wrb) continue;
         unsigned long long v[16];
-        HIP_TRY(hipMemcpy(v, wr_stat, 128, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v, wr_stat + 16 * inst, 128, hipMemcpyDeviceToHost));
         const double n = (double)std::max(1ull, v[0]), r = (double)std::max(1ull, v[1]);
+        if (inst) std::fprintf(stderr, "wiener_res small instance (%d lanes):\n", wrs_nt);
+        else std::fprintf(stderr, "wiener_res big instance (%d lanes):\n", WR_NT);
+        if (v[9])
+            std::fprintf(stderr, "wiener_res: small-size items (one part, window <= %d B) %llu: %.1f candidates/item, "
+                         "%.2f us per candidate\n", WRS_LDS_CAP, v[9], v[10] / (double)v[9],
+                         v[11] / (double)std::max(1ull, v[10]) * 0.01);
         std::fprintf(stderr, "wiener_res: %llu items (%llu parted), %.1f candidates/item, %.0f px/item, per candidate: "
                      "%.2f us (thread 0: pass %.2f us, control %.2f us; wave passes: slowest %.2f us, fastest %.2f "
                      "us)\n", v[0], v[6], v[1] / n, v[5] / n, v[2] / r * 0.01, v[4] / r * 0.01, v[3] / r * 0.01,
                      v[7] / r * 0.01, v[8] / r * 0.01);
     }
-    if (n_sr && sr_stat) {
-        unsigned long long v[16];
-        HIP_TRY(hipMemcpy(v, sr_stat, 128, hipMemcpyDeviceToHost));
+    for (int inst = 0; inst < 2 && n_sr && sr_stat; inst++) { // the big instance, then the small one
+        if (inst == 0 ? n_srb == 0 : n_sr == n_srb) continue;
+        unsigned long long v[32];
+        HIP_TRY(hipMemcpy(v, sr_stat + 32 * inst, sizeof v, hipMemcpyDeviceToHost));
         const double n = (double)std::max(1ull, v[0]);
+        std::fprintf(stderr, "sgr_res %s instance (<= %d chunks/lane, %d workgroups/CU):\n", inst ? "small" : "big",
+                     inst ? SRS_KMAX : SR_KMAX, inst ? SRS_WGS : 2);
+        if (v[16])
+            std::fprintf(stderr, "sgr_res: small-size items (one part, <= %d chunks/lane) %llu: load %.2f us, descent "
+                         "%.2f us (control %.2f us)\n", SRS_KMAX, v[16], v[17] / (double)v[16] * 0.01,
+                         v[18] / (double)v[16] * 0.01, v[19] / (double)v[16] * 0.01);
         std::fprintf(stderr, "sgr_res: %llu items, %.2f passes/item, %.2f candidates/pass, %.0f px/item, ticks/item "
                      "load %.2f us, descent %.2f us (control %.2f us; pixel wave 0: passes %.2f us, waits B3-B4 %.2f "
                      "us; control wave before B3 %.2f us)\n", v[0], v[1] / n,

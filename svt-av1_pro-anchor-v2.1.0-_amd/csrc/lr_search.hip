@@ -39,16 +39,10 @@
 #include <vector>
 
 #include "lr_common.h"
-
+#include "lr_plan.h"
 
 namespace {
 
-struct Tile {
-    int32_t plane, unit, x0, y0, w, h; // unit: global index over the searched planes
-};
-struct URect {
-    int32_t h_start, h_end, v_start, v_end;
-};
 constexpr int PRJ_MIN0 = -96, PRJ_MAX0 = 31, PRJ_MIN1 = -32, PRJ_MAX1 = 95;
 const int     kHostSgrR[16][2] = {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1},
                               {2, 1}, {2, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 1}, {2, 0}, {2, 0}};
@@ -1013,37 +1007,6 @@ __host__ __device__ inline void set_wiener_taps(int16_t *t, const int *v) { // s
 // The candidate count per unit is bounded (WR_MAX_ROUNDS; a descent always ends far earlier): on overflow the
 // descent stops and *status is set, which search_frame reports as SVTGPU_ERR_HIP.
 // ---------------------------------------------------------------------------------------------
-constexpr int WR_NT = 1024, WR_RMAX = 32, WR_MAX_ROUNDS = 4096;
-constexpr int WR_LDS_CAP = 152 * 1024; // largest CDEF window kept in LDS (bytes); larger units read global memory
-constexpr int WRS_LDS_CAP = 38 * 1024; // ... of the small instance: four windows and the static words in a CU's 160 KB
-
-// geometry of a unit in the lane layout: column-pair slots per segment (a multiple of 64), segments, rows per segment
-struct WrGeo {
-    int cpw, nseg, R;
-};
-__host__ __device__ inline WrGeo wr_geo(int w, int h, int nt = WR_NT) { // nt: the instance's lanes
-    WrGeo g;
-    g.cpw  = (((w + 1) >> 1) + 63) & ~63;
-    g.nseg = nt / g.cpw;
-    g.R    = (h + g.nseg - 1) / g.nseg;
-    return g;
-}
-__host__ __device__ inline int wr_window_bytes(int w, int h) { return (h + 6) * ((w + 10) >> 1) * 4; }
-// LDS mode: the window in LDS and the source rows in registers; else both are read from global memory per candidate
-__host__ __device__ inline bool wr_lds_mode(int w, int h, int lds_cap, int nt = WR_NT, int rmax = WR_RMAX) {
-    const WrGeo g = wr_geo(w, h, nt);
-    return wr_window_bytes(w, h) <= lds_cap && g.nseg > 0 && g.R <= rmax;
-}
-// A workgroup's share of a unit: rows [y0, y1) of unit `unit`.  A unit too large for one CU's LDS and registers (the
-// frame's bottom unit row: 256 x 376 at 4K) is cut into `nparts` row parts on as many workgroups; each evaluates every
-// candidate over its rows, the parts' SSEs meet through words in uncached memory (xch[2 * (first + part) + parity]:
-// {round << 48 | partial SSE}, double-buffered by round parity), and every part takes the same descent step.  The
-// parts of a unit are adjacent in the launch order and there are far fewer parted workgroups than CUs, so a waiting
-// part's partner is always dispatched; the wait is bounded all the same (status bit 2).
-struct WrItem {
-    int32_t unit, y0, y1, part, nparts, first; // first: the item index of part 0 (exchange slots)
-};
-constexpr int WR_MAX_PARTS = 4;
 
 // the 5 packed sample pairs of window row r (unit rows -3.., columns x-4 .. x+5) for output columns x, x+1
 template <typename T, bool LDSW>
@@ -1395,7 +1358,6 @@ __global__ __launch_bounds__(WR_NT) void wiener_res_kernel(const SearchArgs A, D
 // Built as WRS_NT = 256 lanes x WRS_RMAX = 32 rows: four per CU (109 VGPRs at 4 waves per SIMD, 4 x 37 KB).  512 lanes
 // x 16 rows (77 VGPRs, per candidate 4.14 against 4.69 us) lost at four frames in flight: 3808-3817 against 3818-3832
 // Mpixels/s
-constexpr int WRS_NT = 256, WRS_RMAX = 32;
 template <typename T, int NT, int RMAX>
 __global__ __launch_bounds__(NT) void wiener_res_small_kernel(const SearchArgs A, Descent *ds, const WrItem *items,
                                                               int lds_cap, int32_t *status, unsigned long long *pc,
@@ -1626,35 +1588,6 @@ __global__ void sgr_best_kernel(const Descent *ds, const SearchArgs A, int nplan
 #ifndef SVTGPU_SR_GLDS
 #define SVTGPU_SR_GLDS 0 // 1: the load phase's dx chunks by direct global -> LDS loads (A/B)
 #endif
-#ifndef SVTGPU_SR_NT
-#define SVTGPU_SR_NT 512
-#endif
-#ifndef SVTGPU_SR_KMAX
-#define SVTGPU_SR_KMAX 19 // resident 4-pixel chunks per pixel lane: parts of <= 34048 pixels (256 x 133 luma)
-#endif
-constexpr int SR_NT = SVTGPU_SR_NT, SR_PW = SR_NT / 64 - 1, SR_PL = SR_PW * 64, SR_KMAX = SVTGPU_SR_KMAX;
-constexpr int SR_LB = 4; // chunks whose loads are in flight together in the load phase
-constexpr int SR_MAX_PX = SR_PL * SR_KMAX * 4;
-constexpr int SR_MAX_PASSES = 4096, SR_MAX_PARTS = 8;
-constexpr int sr_lds_bytes(int kmax) { return kmax * SR_PL * 8; } // the (x - src) pairs of the part
-constexpr int SR_LDS = sr_lds_bytes(SR_KMAX);
-// the small instance (sgr_res_small_kernel): one-part items of <= SRS_KMAX chunks per lane, SRS_WGS workgroups per CU
-#ifndef SVTGPU_SRS_KMAX
-#define SVTGPU_SRS_KMAX 10 // a 128 x 128 unit: 4096 chunks over 448 pixel lanes
-#endif
-#ifndef SVTGPU_SRS_WGS
-#define SVTGPU_SRS_WGS 3 // 6 waves per SIMD: 80 VGPRs (at 4, 64 VGPRs, the load phase spilled 54-79 registers)
-#endif
-#ifndef SVTGPU_SRS_LB
-#define SVTGPU_SRS_LB 1 // its load phase's group of chunks in flight (divides SR_LB: sr_pass reads whole groups of SR_LB)
-#endif
-constexpr int SRS_KMAX = SVTGPU_SRS_KMAX, SRS_WGS = SVTGPU_SRS_WGS, SRS_LDS = sr_lds_bytes(SRS_KMAX);
-constexpr int SRS_LB = SVTGPU_SRS_LB;
-static_assert(SR_LB % SRS_LB == 0, "the zero fill up to a multiple of SR_LB goes by load groups");
-static_assert(SRS_KMAX <= SR_KMAX && SRS_WGS * (SRS_LDS + 2048) <= 160 * 1024, "SRS_WGS workgroups share a CU's LDS");
-struct SrItem {
-    int32_t pair, y0, y1, part, nparts, first; // rows [y0, y1) of the pair's unit; part q at grid position first + 8 q
-};
 constexpr unsigned long long SR_LOW = (1ull << 48) - 1;
 
 // one lane's value of exchange round r, summed over the row parts (this part's value published first).  Every value
@@ -1851,15 +1784,6 @@ __global__ __launch_bounds__(SR_NT, SRS_WGS * (SR_NT / 64) / 4) void sgr_res_sma
 #include "sgr_res_body.h"
 }
 
-struct Carver {
-    size_t off = 0;
-    size_t operator()(size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 // device-clock timing of the search's launches by kernel class (svtgpu_lr_profile).  Everything accumulates on the
 // device: after a search one small kernel folds its launches' slots into per-class tick totals (and re-arms the
 // slots), so a timed search adds no copies or host synchronization; the totals are read back only when asked for.
@@ -1969,18 +1893,6 @@ struct LrProfiler {
         return SVTGPU_OK;
     }
 };
-
-struct PlanePlan {
-    int                  n = 0, nt = 0, unit_base = 0, tile_base = 0, win = 7, nval = 0, ne = 0, pair_base = 0;
-    bool                 wn = false, sg = false;
-    size_t               part_off = 0, mh_off = 0; // element offsets (int64)
-    std::vector<int32_t> eps;
-};
-
-int plane_win(const SvtGpuLrSearchControls *c, int p) {
-    const int win_l = c->wn_filter_tap_lvl == 1 ? 7 : c->wn_filter_tap_lvl == 2 ? 5 : 3;
-    return p == 0 ? win_l : std::min(win_l, 5);
-}
 
 // RestUnitSearchInfo as rest_finish_search uses it (EbRestoration.h:349-360): best[] = best_rtype[WIENER - 1 ..
 // SWITCHABLE - 1]
@@ -2105,9 +2017,6 @@ void finish_frame_host(const SvtGpuLrSearchControls *c, int nplanes, const int32
 // The shared RestUnitSearchInfo array (finish_plane_shared) is modelled by reading luma's entries for a type a chroma
 // plane does not search.
 // ---------------------------------------------------------------------------------------------
-constexpr int FIN_K1 = 63; // r = 1 / 2 masks: bit k < 63 = the unit k + 1 back as the reference, bit 63 = the default
-constexpr int FIN_CH = 64; // the walks: units per chunk (a lane per unit; the switchable tables staged in LDS)
-constexpr int FIN_OUT = 8; // device result words: frame types [3], search status, sequence
 
 struct RecArgs {
     int32_t                   nplanes, n_all, wn[3], sg[3];
@@ -2459,69 +2368,6 @@ void launch_stats(int win, Fn &&f) {
     else f(std::integral_constant<int, 3>());
 }
 
-// largest Wiener window staged in LDS (SVTGPU_WR_LDS_CAP overrides: measurements of the global-memory path)
-int wr_lds_cap() {
-    static const int v = [] {
-        const char *e = std::getenv("SVTGPU_WR_LDS_CAP");
-        return e ? std::atoi(e) : WR_LDS_CAP;
-    }();
-    return v;
-}
-
-// lanes of the small Wiener instance (wiener_res_small_kernel); 0: every unit on the big instance, which
-// SVTGPU_WR_CLASSIC=1 (thread 0's step: not in the small instance) and SVTGPU_WR_SMALL=0 (A/B, and the per-item
-// clocks of the small-size units there) ask for
-int wr_small_nt() {
-    static const int v = [] {
-        const char *c = std::getenv("SVTGPU_WR_CLASSIC"), *e = std::getenv("SVTGPU_WR_SMALL");
-        return (c && std::atoi(c) != 0) || (e && !std::strcmp(e, "0")) ? 0 : WRS_NT;
-    }();
-    return v;
-}
-
-// largest row part of the resident self-guided search (pixels); SVTGPU_SR_PART_PX lowers it (tests of the parted path)
-int sr_part_px() {
-    static const int v = [] {
-        const char *e = std::getenv("SVTGPU_SR_PART_PX");
-        return e ? std::max(64, std::min(std::atoi(e), SR_MAX_PX)) : SR_MAX_PX;
-    }();
-    return v;
-}
-
-// candidates per pass of the resident self-guided search: a complete speculative tree of 1, 3 or 7 nodes
-// (SVTGPU_SR_TREE for A/B measurements).  One: the descent's own candidate sequence, 7.1 passes per (unit, ep) at 4K
-// against 3.9 (3 nodes) and 2.7 (7 nodes) -- the resident passes are cheap, and a larger tree's evaluated-but-unused
-// candidates cost the other frames' work at three frames in flight (2366 / 2321 Mpx/s for 1 / 3 nodes,
-// profiles/r03/srvar)
-int sr_tree_nodes() {
-    static const int v = [] {
-        const char *e = std::getenv("SVTGPU_SR_TREE");
-        const int   n = e ? std::atoi(e) : 1;
-        return n == 3 || n == 7 ? n : 1;
-    }();
-    return v;
-}
-
-// SVTGPU_SR_1B=0 (A/B): every item on the two-barrier path, the control wave stepping the descent alone (round 3's form)
-bool sr_two_barriers() {
-    static const bool v = [] {
-        const char *e = std::getenv("SVTGPU_SR_1B");
-        return e && !std::strcmp(e, "0");
-    }();
-    return v;
-}
-
-// whether small one-part items run on sgr_res_small_kernel: the default path only (one candidate per pass, one
-// barrier); SVTGPU_SR_SMALL=0 keeps every item on the big instance (A/B, and the per-item clocks of the small-size
-// items there)
-bool sr_small_enabled() {
-    static const bool v = [] {
-        const char *e = std::getenv("SVTGPU_SR_SMALL");
-        return !(e && !std::strcmp(e, "0")) && sr_tree_nodes() == 1 && !sr_two_barriers();
-    }();
-    return v;
-}
-
 // The statistics of one unit on the matrix cores (svt_av1_compute_stats(_highbd) for 8- and 10-bit samples: the
 // RTCD shim of lr_shims.hip): the unit, its source and a 3-sample border are staged as a small frame (the border
 // replicated past the reference's `half` samples, which no feature of a smaller window reads), cut into <= 64 x 64
@@ -2598,10 +2444,6 @@ int stats_unit_mfma(int win, const T *dgd, const T *src, int h_start, int h_end,
     return SVTGPU_OK;
 }
 
-// plane p's Wiener window for the controls
-
-// The search of the units in unit rows [rb[p], re[p]) of planes 0..nplanes-1.  frame_type != nullptr: the band
-// is the whole frame and the RD finish runs and sets the state's units.
 // waits for the last device finish queued on `st` (bounded when an exchange sits before it) and returns its frame
 // types, or the failure a resident descent reported (status words copied by lr_fin_walk_kernel)
 int lr_collect(SvtGpuLrState *s, hipStream_t st, int32_t *frame_type) {
@@ -2625,252 +2467,110 @@ int lr_collect(SvtGpuLrState *s, hipStream_t st, int32_t *frame_type) {
     return SVTGPU_OK;
 }
 
-// SVTGPU_LR_FINISH=host: rest_finish_search on the host after a read-back of the records (the round-5 form; A/B)
-bool lr_finish_on_host() {
-    static const bool h = [] {
-        const char *e = std::getenv("SVTGPU_LR_FINISH");
-        return e && !std::strcmp(e, "host");
-    }();
-    return h;
-}
-
-// fin == 0: the records come back to the host (search_out) and, for the whole frame (frame_type != nullptr), the RD
-// finish runs there.  fin == 1: the records and the RD finish stay on the device (a tiled picture all-reduces the
-// records on the device first), the state's units are written in stream order; frame_type != nullptr then waits for
-// the result and reads the frame types (and the records into search_out), nullptr returns at once (the asynchronous
-// search: svtgpu_lr_read_result collects it).
-template <typename T>
-int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *src, const SvtGpuLrSearchControls *c,
-                 int nplanes, const int32_t *rb, const int32_t *re, const int32_t *cb, const int32_t *ce,
-                 int32_t *frame_type, SvtGpuLrUnitSearch *const *search_out, hipStream_t st, int fin = 0) {
-    // SVTGPU_LR_TIMING=1 prints the host-side phase times (wall clock, including the waits) to stderr
-    static const bool timing = std::getenv("SVTGPU_LR_TIMING") != nullptr;
-    auto              clk    = [] { return std::chrono::steady_clock::now(); };
-    auto              t_last = clk();
-    double            t_ph[6] = {0, 0, 0, 0, 0, 0};
-    auto              mark   = [&](int i) {
-        const auto now = clk();
-        t_ph[i] += std::chrono::duration<double, std::milli>(now - t_last).count();
+// SVTGPU_LR_TIMING: the host-side wall time of the search by phase (including the waits)
+struct PhaseTimer {
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+    double                                ms[5]  = {0, 0, 0, 0, 0};
+    void mark(int i) {
+        const auto now = std::chrono::steady_clock::now();
+        ms[i] += std::chrono::duration<double, std::milli>(now - t_last).count();
         t_last = now;
-    };
-    // ---- plan: units (foreach_rest_unit_in_tile, EbRestoration.c:1257-1294), their <= 64x64 tiles, the eps ----
-    PlanePlan            pp[3];
-    std::vector<URect>   units;
-    std::vector<Tile>    tiles;
-    std::vector<int32_t> tile0, uloc; // uloc: plane-local index of every global unit
-    int                  npairs = 0, n_wn = 0, nt_wn = 0, n_sg = 0, nt_sg = 0, sg_planes = 0;
-    size_t               flt_elems = 0, part_elems = 0, mh_elems = 0;
-    for (int p = 0; p < nplanes; p++) {
-        PlanePlan &q = pp[p];
-        const int  W = lr_plane_w(s, p), H = lr_plane_h(s, p), usz = s->unit_size[p], ext = usz * 3 / 2, off = 8 >> (p > 0);
-        q.unit_base = (int)units.size(), q.tile_base = (int)tiles.size();
-        int urow = 0, uidx = 0;
-        for (int y0 = 0; y0 < H; urow++) {
-            const int uh = (H - y0 < ext) ? H - y0 : usz;
-            int       vs = std::max(0, y0 - off), ve = y0 + uh;
-            if (ve < H) ve -= off;
-            for (int x0 = 0, ucol = 0; x0 < W; uidx++, ucol++) {
-                const int uw = (W - x0 < ext) ? W - x0 : usz;
-                if (urow >= rb[p] && urow < re[p] && ucol >= cb[p] && ucol < ce[p]) {
-                    tile0.push_back((int)tiles.size());
-                    for (int y = vs; y < ve; y += 64)
-                        for (int x = x0; x < x0 + uw; x += 64)
-                            tiles.push_back({p, (int)units.size(), x, y, std::min(64, x0 + uw - x), std::min(64, ve - y)});
-                    units.push_back({x0, x0 + uw, vs, ve});
-                    uloc.push_back(uidx);
-                }
-                x0 += uw;
-            }
-            y0 += uh;
-        }
-        q.n = (int)units.size() - q.unit_base, q.nt = (int)tiles.size() - q.tile_base;
-        if (urow != s->vunits[p] || uidx != s->hunits[p] * s->vunits[p]) return SVTGPU_ERR_INVALID_ARG;
-        q.wn   = c->wn_enabled && (!p || c->wn_use_chroma);
-        q.win  = plane_win(c, p);
-        q.nval = (q.win * (q.win + 1) / 2 + 1) * 49;
-        if (c->sg_enabled && (!p || c->sg_use_chroma))
-            for (int e = c->sg_start_ep[p > 0]; e < c->sg_end_ep[p > 0]; e += std::max(1, c->sg_ep_inc[p > 0]))
-                q.eps.push_back(e);
-        q.ne = (int)q.eps.size(), q.sg = q.ne > 0;
-        q.pair_base = npairs;
-        npairs += q.n * q.ne;
-        if (q.wn) {
-            n_wn += q.n, nt_wn += q.nt;
-            q.part_off = part_elems, q.mh_off = mh_elems;
-            part_elems += (size_t)q.nt * q.nval, mh_elems += (size_t)q.n * q.nval;
-        }
-        if (q.sg) {
-            n_sg += q.n, nt_sg += q.nt, sg_planes++;
-            flt_elems += (size_t)(q.ne * 2 + 1) * ((W + 63) & ~63) * H; // the eps' g planes and the dx plane
-        }
     }
-    tile0.push_back((int)tiles.size());
-    for (const Tile &t : tiles) // 4-pixel chunks start on tile x offsets (unit columns: multiples of 32)
-        if (t.x0 & 3) return SVTGPU_ERR_UNSUPPORTED;
-    const int n_all = (int)units.size(), nt_all = (int)tiles.size();
-    if (n_all == 0) return SVTGPU_OK; // an empty band
-    // the records' layout: every plane's units back to back (the state's units, d_units[0]); dst[gu]: the record of
-    // searched unit gu
-    int32_t nrec = 0, rbase[3];
-    for (int p = 0; p < 3; p++) rbase[p] = nrec, nrec += s->hunits[p] * s->vunits[p];
-    std::vector<int32_t> dst(n_all);
-    for (int p = 0, gu = 0; p < nplanes; p++)
-        for (int u = 0; u < pp[p].n; u++, gu++) dst[gu] = rbase[p] + uloc[gu];
-    // the resident Wiener kernel takes every unit whose rows fit its registers (all units of the 4K / 1080p frames);
-    // its workgroups start with the largest units (the longest chains); windows up to WR_LDS_CAP live in LDS
-    // The resident Wiener kernel takes every unit up to 384 columns wide (unit sizes <= 256): a unit is cut into the
-    // fewest row parts that fit one CU's LDS and registers each (global-memory mode when no cut up to WR_MAX_PARTS
-    // does); workgroups start with the largest parts (the longest chains), the parts of a unit adjacent.
-    // Each unit is routed by its own size: a one-part unit whose window and rows fit the small instance
-    // (wiener_res_small_kernel: several workgroups per CU) goes there, every other unit to the big one; wr_items holds
-    // the big instance's items, then the small one's, each largest first, and each launch's LDS is its own items' maximum
-    std::vector<WrItem> wr_items;
-    bool                wr_parted = false;
-    int                 wr_lds = 0, wrs_lds = 0, n_wrb = 0;
-    const int           wrs_nt = wr_small_nt(), wrs_rmax = WRS_RMAX;
-    {
-        std::vector<int> ord(n_wn);
-        std::vector<int> np(n_wn, 1);
-        std::vector<char> small(n_wn, 0);
-        for (int u = 0; u < n_wn; u++) {
-            const URect &r = units[u];
-            const int    w = r.h_end - r.h_start, h = r.v_end - r.v_start;
-            ord[u]         = u;
-            int k = 1;
-            while (k < WR_MAX_PARTS && !wr_lds_mode(w, (h + k - 1) / k, wr_lds_cap())) k++;
-            np[u] = wr_lds_mode(w, (h + k - 1) / k, wr_lds_cap()) ? k : 1;
-            if (np[u] > 1) wr_parted = true;
-            const int hp = (h + np[u] - 1) / np[u];
-            small[u]     = wrs_nt && np[u] == 1 && wr_lds_mode(w, h, std::min(WRS_LDS_CAP, wr_lds_cap()), wrs_nt, wrs_rmax);
-            if (small[u]) wrs_lds = std::max(wrs_lds, wr_window_bytes(w, h));
-            else if (wr_lds_mode(w, hp, wr_lds_cap())) wr_lds = std::max(wr_lds, wr_window_bytes(w, hp));
-        }
-        auto part_area = [&](int u) {
-            return (units[u].h_end - units[u].h_start) * ((units[u].v_end - units[u].v_start + np[u] - 1) / np[u]);
-        };
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return part_area(a) > part_area(b); });
-        for (int cls = 0; cls < 2; cls++) {
-            for (int u : ord) {
-                if (small[u] != cls) continue;
-                const int h = units[u].v_end - units[u].v_start, first = (int)wr_items.size();
-                for (int k = 0; k < np[u]; k++)
-                    wr_items.push_back({u, h * k / np[u], h * (k + 1) / np[u], k, np[u], first});
-            }
-            if (cls == 0) n_wrb = (int)wr_items.size();
-        }
+};
+
+// what the phases of one search share: the state and the controls, the two streams, the kernels' arguments
+struct SearchCtx {
+    SvtGpuLrState                *s;
+    const SvtGpuLrSearchControls *c;
+    int                           nplanes;
+    hipStream_t                   st, sw = nullptr; // the caller's stream (the self-guided chain), the Wiener chain's
+    LrProfiler                   *prof = nullptr;
+    uint8_t                      *qa = nullptr; // the uncached exchange arena (null: no unit is cut into row parts)
+    unsigned                      sr_xmode = 0;
+    unsigned long long           *wr_stat = nullptr, *sr_stat = nullptr; // SVTGPU_WR_STATS / SVTGPU_SR_STATS words
+    SearchArgs                    A;
+    SeedCfg                       cfg;
+    PhaseTimer                    t;
+    void *dp(size_t o) const { return (uint8_t *)s->d_work + o; }
+    void *hp(size_t o) const { return (uint8_t *)s->h_pin + o; }
+    template <typename Fn>
+    void run(int cls, hipStream_t ls, Fn &&launch) const { // one launch of profiler class cls on stream ls
+        const int ev = prof ? prof->ev_begin(cls, ls) : -1;
+        launch(prof ? prof->slot(cls) : nullptr);
+        if (prof) prof->ev_end(ev, ls);
     }
-    const int n_wr = (int)wr_items.size();
-    // The resident self-guided search (sgr_res_kernel): one item per (unit row part, ep).  Workgroups are dealt
-    // round-robin over the 8 XCDs (block b on XCD b mod 8), so the grid is laid out as 8 lanes (positions r, r + 8, ...):
-    // a unit's items -- its eps, and the row parts of each -- go to one lane, consecutively.  The eps of a unit then
-    // read its CDEF and source samples through one L2, and the parts of an item sit next to each other in their XCD's
-    // in-order dispatch, so a waiting part's partners are always dispatched after it (never behind other waiting
-    // parts).  Units are dealt largest first to the lane with the least work; empty slots (pair -1) pad the lanes.
-    // Each unit is routed by its own size: a one-part unit of at most SRS_KMAX chunks per lane goes to the small
-    // instance (sgr_res_small_kernel: more workgroups per CU), every other unit to the big one.  Each instance's grid
-    // has the 8-lane layout within itself; sr_items holds the big grid, then the small one (first: a position in the
-    // item's own grid -- the exchange words are the big instance's alone).
-    std::vector<SrItem>  sr_items;
-    bool                 sr_parted = false;
-    int                  n_srb = 0; // the big instance's grid; the small one's is the rest of sr_items
-    if (npairs) {
-        std::vector<std::vector<SrItem>> lanes[2] = {std::vector<std::vector<SrItem>>(8), std::vector<std::vector<SrItem>>(8)};
-        std::vector<long long>           load[2] = {std::vector<long long>(8, 0), std::vector<long long>(8, 0)};
-        std::vector<int>                 ord;
-        for (int p = 0; p < nplanes; p++)
-            if (pp[p].sg)
-                for (int u = 0; u < pp[p].n; u++) ord.push_back(pp[p].unit_base + u);
-        auto area = [&](int u) { return (long long)(units[u].h_end - units[u].h_start) * (units[u].v_end - units[u].v_start); };
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return area(a) > area(b); });
-        for (int u : ord) {
-            int p = 0;
-            while (p + 1 < nplanes && u >= pp[p + 1].unit_base) p++;
-            const PlanePlan &q = pp[p];
-            const int        cw = (units[u].h_end - units[u].h_start + 3) >> 2, h = units[u].v_end - units[u].v_start;
-            const int        maxrows = std::max(1, sr_part_px() / 4 / std::max(cw, 1)), np = (h + maxrows - 1) / maxrows;
-            if (np > SR_MAX_PARTS) return SVTGPU_ERR_UNSUPPORTED; // a unit wider than 1024 x 4 samples per row part
-            sr_parted |= np > 1;
-            const int cls  = sr_small_enabled() && np == 1 && (cw * h + SR_PL - 1) / SR_PL <= SRS_KMAX;
-            const int lane = (int)(std::min_element(load[cls].begin(), load[cls].end()) - load[cls].begin());
-            for (int k = 0; k < q.ne; k++) {
-                const int first = (int)lanes[cls][lane].size(); // lane-local; made global below
-                for (int part = 0; part < np; part++)
-                    lanes[cls][lane].push_back({q.pair_base + (u - q.unit_base) * q.ne + k, h * part / np,
-                                                h * (part + 1) / np, part, np, first});
-            }
-            load[cls][lane] += area(u) * q.ne;
-        }
-        for (int cls = 0; cls < 2; cls++) {
-            size_t len = 0;
-            for (auto &l : lanes[cls]) len = std::max(len, l.size());
-            const size_t base = sr_items.size();
-            sr_items.resize(base + 8 * len, SrItem{-1, 0, 0, 0, 1, 0});
-            for (int r = 0; r < 8; r++)
-                for (size_t m = 0; m < lanes[cls][r].size(); m++) {
-                    SrItem it = lanes[cls][r][m];
-                    it.first  = 8 * it.first + r; // parts of an item: positions first, first + 8, ...
-                    sr_items[base + 8 * m + r] = it;
-                }
-            if (cls == 0) n_srb = (int)sr_items.size();
-        }
-    }
-    const int n_sr = (int)sr_items.size();
-    // ---- device scratch and pinned staging ----
-    // three contiguous spans keep the host traffic to one copy each: the plan (uploaded when it changes), the
-    // accumulators zeroed per search, the results read back (o_sse is the last zeroed and the first read)
-    Carver       dc;
-    const size_t o_tiles = dc(sizeof(Tile) * nt_all), o_units = dc(sizeof(URect) * n_all), o_t0 = dc(4 * (n_all + 1)),
-                 o_witem = dc(sizeof(WrItem) * (size_t)n_wr), o_sritem = dc(sizeof(SrItem) * (size_t)n_sr),
-                 o_dst = dc(4 * (size_t)n_all);
-    const size_t plan_span = dc.off;
-    // zeroed per search: the accumulators, the device finish's records (zero-padded: a tiled picture sums them) and
-    // paths (a pass that does not run reads as "none taken")
-    const size_t o_sum = dc(8 * n_all), o_rec = dc(sizeof(SvtGpuLrUnitSearch) * (size_t)nrec),
-                 o_path = dc(16 * (size_t)nrec), o_sse = dc(8 * n_all), o_sse2 = dc(8 * (size_t)n_sg), o_wstat = dc(8),
-                 o_sstat = dc(8);
-    const size_t zero_span = dc.off - o_sum;
-    const size_t o_wu = dc(sizeof(SvtGpuRestUnit) * n_wn), o_wds = dc(sizeof(Descent) * n_wn),
-                 o_best = dc(16 * (size_t)n_sg), o_braw = dc(8 * (size_t)n_sg);
-    const size_t res_span = dc.off - o_sse; // the (unit, ep) descents stay on the device: the best ep's come back
-    const size_t o_sds = dc(sizeof(Descent) * npairs);
-    const size_t o_part = dc(8 * part_elems), o_mh = dc(8 * mh_elems);
-    const size_t o_m1 = dc(8 * (size_t)nrec), o_m2 = dc(8 * (size_t)nrec), o_b1 = dc(64 * (size_t)nrec),
-                 o_b2 = dc(64 * (size_t)nrec), o_fout = dc(4 * FIN_OUT);
-    // the uncached arena: the SSE exchange words of the Wiener units cut into row parts (wiener_res_kernel)
-    Carver       qc;
-    const size_t q_wrx = qc(16 * (size_t)n_wr), q_srx = qc(128 * (size_t)n_sr);
-    Carver       hc; // host mirrors of the plan and result spans keep the device layout
-    const size_t h_plan = hc(plan_span), h_res = hc(res_span), h_cnt = hc(32), h_out = hc(sizeof(SvtGpuRestUnit) * n_all),
-                 h_rec = hc(sizeof(SvtGpuLrUnitSearch) * (size_t)nrec);
-    const size_t h_sse = h_res, h_sse2 = h_res + (o_sse2 - o_sse), h_wu = h_res + (o_wu - o_sse),
-                 h_wds = h_res + (o_wds - o_sse), h_best = h_res + (o_best - o_sse), h_braw = h_res + (o_braw - o_sse);
-    if (dc.off > s->work_bytes) {
+};
+constexpr int SR_NSTAT = 32; // SVTGPU_SR_STATS words per instance: the big one's, then the small one's
+
+// grows the state's buffers to the layout; the exchange arenas only when a unit is cut into row parts
+int ensure_buffers(SearchCtx &x, const LrPlan &plan, const LrLayout &L) {
+    SvtGpuLrState *s = x.s;
+    const LrKnobs &k = lr_knobs();
+    const int      n_sr = plan.n_sr();
+    if (L.work_bytes > s->work_bytes) {
         (void)hipFree(s->d_work);
         s->d_work = nullptr, s->work_bytes = 0;
-        HIP_TRY(hipMalloc(&s->d_work, dc.off));
-        s->work_bytes = dc.off;
+        HIP_TRY(hipMalloc(&s->d_work, L.work_bytes));
+        s->work_bytes = L.work_bytes;
         s->plan_bytes.clear(); // nothing uploaded into the new buffer yet
     }
     if (s->pin_free) HIP_TRY(hipEventSynchronize(s->pin_free)); // the previous search's upload has read h_pin
-    if (hc.off > s->pin_bytes) {
+    if (L.pin_bytes > s->pin_bytes) {
         if (s->h_pin) (void)hipHostFree(s->h_pin);
         s->h_pin = nullptr, s->pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(&s->h_pin, hc.off, hipHostMallocDefault));
-        s->pin_bytes = hc.off;
+        HIP_TRY(hipHostMalloc(&s->h_pin, L.pin_bytes, hipHostMallocDefault));
+        s->pin_bytes = L.pin_bytes;
     }
-    if (2 * flt_elems > s->flt_bytes) {
+    if (2 * plan.flt_elems > s->flt_bytes) {
         (void)hipFree(s->d_flt);
         s->d_flt = nullptr, s->flt_bytes = 0;
-        HIP_TRY(hipMalloc(&s->d_flt, 2 * flt_elems));
-        s->flt_bytes = 2 * flt_elems;
+        HIP_TRY(hipMalloc(&s->d_flt, 2 * plan.flt_elems));
+        s->flt_bytes = 2 * plan.flt_elems;
     }
-    uint8_t *wb = (uint8_t *)s->d_work, *hb = (uint8_t *)s->h_pin;
-    auto     dp = [&](size_t o) { return (void *)(wb + o); };
-    auto     hp = [&](size_t o) { return (void *)(hb + o); };
-    SearchArgs A;
+    if ((plan.n_wn && plan.wr_parted) || (n_sr && plan.sr_parted)) {
+        if (L.qarena_bytes > s->qarena_bytes) {
+            if (s->d_qarena) (void)hipFree(s->d_qarena);
+            s->d_qarena = nullptr, s->qarena_bytes = 0;
+            HIP_TRY(hipExtMallocWithFlags(&s->d_qarena, L.qarena_bytes, hipDeviceMallocUncached));
+            s->qarena_bytes = L.qarena_bytes;
+        }
+        x.qa = (uint8_t *)s->d_qarena;
+    }
+    if (n_sr && plan.sr_parted && k.sr_l2) {
+        const size_t need = 128 * (size_t)n_sr;
+        if (need > s->sxarena_bytes) {
+            if (s->d_sxarena) (void)hipFree(s->d_sxarena);
+            s->d_sxarena = nullptr, s->sxarena_bytes = 0;
+            HIP_TRY(hipMalloc(&s->d_sxarena, need));
+            HIP_TRY(hipMemsetAsync(s->d_sxarena, 0, need, x.st));
+            s->sxarena_bytes = need;
+        }
+        // the tag holds 8 epoch bits: when they wrap, clear the arena so no word left 256 searches ago passes for this
+        // one's (ADVICE r4).  Test-only mode: the words are visible to an item's parts only through one XCD's L2, which
+        // holds while workgroups are dealt round-robin over the 8 XCDs (SPX partition mode, positions first + 8 q);
+        // another placement makes the partner polls time out (status word -> SVTGPU_ERR_HIP), never a wrong sum
+        if ((++s->sx_epoch & 0xFFu) == 0) {
+            HIP_TRY(hipMemsetAsync(s->d_sxarena, 0, s->sxarena_bytes, x.st));
+            ++s->sx_epoch;
+        }
+        x.sr_xmode = 0x100u | (s->sx_epoch & 0xFFu);
+    }
+    if (k.sr_two_barriers) x.sr_xmode |= 0x200u;
+    static unsigned long long *wr_stat = nullptr, *sr_stat = nullptr;
+    if (k.wr_stats && !wr_stat) HIP_TRY(hipMalloc(&wr_stat, 256)); // 16 words per instance: the big one's, the small one's
+    if (k.sr_stats && !sr_stat) HIP_TRY(hipMalloc(&sr_stat, 2 * 8 * SR_NSTAT));
+    x.wr_stat = wr_stat, x.sr_stat = sr_stat;
+    return SVTGPU_OK;
+}
+
+// the kernels' arguments, and the state fields svtgpu_lr_read_sgr_planes reads back
+void fill_search_args(SearchCtx &x, const LrPlan &plan, const LrLayout &L, const SvtGpuFrame *rec, const SvtGpuFrame *src) {
+    SvtGpuLrState   *s  = x.s;
+    const PlanePlan *pp = plan.pp;
+    SearchArgs      &A  = x.A;
     std::memset(&A, 0, sizeof A);
     size_t flt_off = 0;
-    for (int p = 0; p < nplanes; p++) {
+    for (int p = 0; p < x.nplanes; p++) {
         PlaneArgs &P = A.pl[p];
         P.dgd = rec->plane[p], P.src = src->plane[p], P.dstride = rec->stride[p], P.sstride = src->stride[p];
         P.W = lr_plane_w(s, p), P.H = lr_plane_h(s, p), P.bd = rec->bit_depth, P.fstride = (P.W + 63) & ~63;
@@ -2893,312 +2593,266 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
         if (pp[p].sg) flt_off += (size_t)(pp[p].ne * 2 + 1) * P.fstride * P.H;
     }
     for (int p = 0; p < 3; p++) { // what svtgpu_lr_read_sgr_planes reads back
-        const bool sg = p < nplanes && pp[p].sg;
+        const bool sg = p < x.nplanes && pp[p].sg;
         s->sg_flt[p] = sg ? A.pl[p].flt : nullptr, s->sg_ne[p] = sg ? A.pl[p].ne : 0;
         s->sg_fstride[p] = A.pl[p].fstride, s->sg_w[p] = A.pl[p].W, s->sg_h[p] = A.pl[p].H;
         for (int k = 0; k < 16; k++) s->sg_eps[p][k] = A.pl[p].eps[k], s->sg_f1e[p][k] = A.pl[p].f1e[k];
     }
-    A.tiles = (const Tile *)dp(o_tiles), A.units = (const URect *)dp(o_units), A.tile0 = (const int32_t *)dp(o_t0);
-    auto *d_t0 = (int32_t *)dp(o_t0);
-    // ---- phase 1: sums, Wiener statistics, self-guided filters and moments ----
-    LrProfiler         *prof = (LrProfiler *)s->prof;
-    unsigned long long *pc   = prof ? prof->d_px : nullptr;
-    auto run = [&](int c, hipStream_t ls, auto &&launch) {
-        const int ev = prof ? prof->ev_begin(c, ls) : -1;
-        launch(prof ? prof->slot(c) : nullptr);
-        if (prof) prof->ev_end(ev, ls);
-    };
-    if (prof) prof->start();
-    {
-        uint8_t *pl = (uint8_t *)hp(h_plan);
-        std::memset(pl, 0, plan_span);
-        std::memcpy(pl + o_tiles, tiles.data(), sizeof(Tile) * nt_all);
-        std::memcpy(pl + o_units, units.data(), sizeof(URect) * n_all);
-        std::memcpy(pl + o_t0, tile0.data(), 4 * (n_all + 1));
-        std::memcpy(pl + o_witem, wr_items.data(), sizeof(WrItem) * (size_t)n_wr);
-        std::memcpy(pl + o_sritem, sr_items.data(), sizeof(SrItem) * (size_t)n_sr);
-        std::memcpy(pl + o_dst, dst.data(), 4 * (size_t)n_all);
-        if (s->plan_work != s->d_work || s->plan_bytes.size() != plan_span ||
-            std::memcmp(s->plan_bytes.data(), pl, plan_span)) { // a new plan: one upload
-            HIP_TRY(hipMemcpyAsync(dp(0), pl, plan_span, hipMemcpyHostToDevice, st));
-            svtgpu_count_xfer(0, plan_span);
-            s->plan_bytes.assign(pl, pl + plan_span);
-            s->plan_work = s->d_work;
-        }
+    A.tiles = (const Tile *)x.dp(L.o_tiles), A.units = (const URect *)x.dp(L.o_units), A.tile0 = (const int32_t *)x.dp(L.o_t0);
+    x.cfg.wn_use_refinement = x.c->wn_use_refinement, x.cfg.wn_max_one_step = x.c->wn_max_one_refinement_step;
+    x.cfg.sg_refine[0] = x.c->sg_refine[0], x.cfg.sg_refine[1] = x.c->sg_refine[1];
+}
+
+// the plan into its span of d_work (one upload, when it changed) and the zeroes of everything a search accumulates into
+int upload_plan_and_zero(SearchCtx &x, const LrPlan &plan, const LrLayout &L) {
+    SvtGpuLrState *s  = x.s;
+    const size_t   n_all = plan.n_all();
+    uint8_t       *pl = (uint8_t *)x.hp(L.h_plan);
+    std::memset(pl, 0, L.plan_span);
+    std::memcpy(pl + L.o_tiles, plan.tiles.data(), sizeof(Tile) * plan.tiles.size());
+    std::memcpy(pl + L.o_units, plan.units.data(), sizeof(URect) * n_all);
+    std::memcpy(pl + L.o_t0, plan.tile0.data(), 4 * (n_all + 1));
+    std::memcpy(pl + L.o_witem, plan.wr_items.data(), sizeof(WrItem) * plan.wr_items.size());
+    std::memcpy(pl + L.o_sritem, plan.sr_items.data(), sizeof(SrItem) * plan.sr_items.size());
+    std::memcpy(pl + L.o_dst, plan.dst.data(), 4 * n_all);
+    if (s->plan_work != s->d_work || s->plan_bytes.size() != L.plan_span ||
+        std::memcmp(s->plan_bytes.data(), pl, L.plan_span)) { // a new plan: one upload
+        HIP_TRY(hipMemcpyAsync(x.dp(0), pl, L.plan_span, hipMemcpyHostToDevice, x.st));
+        svtgpu_count_xfer(0, L.plan_span);
+        s->plan_bytes.assign(pl, pl + L.plan_span);
+        s->plan_work = s->d_work;
     }
     // Every accumulator, status word and exchange arena is zeroed here, before the first kernel: a memset queued
     // behind the filters would wait for a CU slot while the resident Wiener descent holds them (~140 us at 4K).
-    HIP_TRY(hipMemsetAsync(dp(o_sum), 0, zero_span, st));
-    uint8_t *qa = nullptr;
-    if ((n_wn && wr_parted) || (n_sr && sr_parted)) {
-        if (qc.off > s->qarena_bytes) {
-            if (s->d_qarena) (void)hipFree(s->d_qarena);
-            s->d_qarena = nullptr, s->qarena_bytes = 0;
-            HIP_TRY(hipExtMallocWithFlags(&s->d_qarena, qc.off, hipDeviceMallocUncached));
-            s->qarena_bytes = qc.off;
-        }
-        qa = (uint8_t *)s->d_qarena;
-        HIP_TRY(hipMemsetAsync(qa, 0, qc.off, st));
-    }
-    // the self-guided row parts' exchange words: uncached memory (default) or, with SVTGPU_SR_XCH=l2, cached memory that
-    // stays in the XCD's L2 (no memset: the search epoch tags the words)
-    static const bool sr_l2 = [] {
-        const char *e = std::getenv("SVTGPU_SR_XCH");
-        return e && !std::strcmp(e, "l2");
-    }();
-    unsigned sr_xmode = 0;
-    if (n_sr && sr_parted && sr_l2) {
-        const size_t need = 128 * (size_t)n_sr;
-        if (need > s->sxarena_bytes) {
-            if (s->d_sxarena) (void)hipFree(s->d_sxarena);
-            s->d_sxarena = nullptr, s->sxarena_bytes = 0;
-            HIP_TRY(hipMalloc(&s->d_sxarena, need));
-            HIP_TRY(hipMemsetAsync(s->d_sxarena, 0, need, st));
-            s->sxarena_bytes = need;
-        }
-        // the tag holds 8 epoch bits: when they wrap, clear the arena so no word left 256 searches ago passes for this
-        // one's (ADVICE r4).  Test-only mode: the words are visible to an item's parts only through one XCD's L2, which
-        // holds while workgroups are dealt round-robin over the 8 XCDs (SPX partition mode, positions first + 8 q);
-        // another placement makes the partner polls time out (status word -> SVTGPU_ERR_HIP), never a wrong sum
-        if ((++s->sx_epoch & 0xFFu) == 0) {
-            HIP_TRY(hipMemsetAsync(s->d_sxarena, 0, s->sxarena_bytes, st));
-            ++s->sx_epoch;
-        }
-        sr_xmode = 0x100u | (s->sx_epoch & 0xFFu);
-    }
-    if (sr_two_barriers()) sr_xmode |= 0x200u;
-    static const bool wr_classic = [] { // SVTGPU_WR_CLASSIC=1 (A/B): the round-4 Wiener step (thread 0, two barriers)
-        const char *e = std::getenv("SVTGPU_WR_CLASSIC");
-        return e && std::atoi(e) != 0;
-    }();
-    static const bool   wr_stats = std::getenv("SVTGPU_WR_STATS") != nullptr; // per-search diagnostics to stderr
-    static unsigned long long *wr_stat = nullptr;
-    if (wr_stats && !wr_stat) HIP_TRY(hipMalloc(&wr_stat, 256)); // 16 words per instance: the big one's, the small one's
-    if (wr_stat) HIP_TRY(hipMemsetAsync(wr_stat, 0, 256, st));
-    static const bool   sr_stats = std::getenv("SVTGPU_SR_STATS") != nullptr; // per-search diagnostics to stderr
-    static unsigned long long *sr_stat = nullptr;
-    constexpr int SR_NSTAT = 32; // words per instance: the big one's, then the small one's
-    if (sr_stats && !sr_stat) HIP_TRY(hipMalloc(&sr_stat, 2 * 8 * SR_NSTAT));
-    if (sr_stat) HIP_TRY(hipMemsetAsync(sr_stat, 0, 2 * 8 * SR_NSTAT, st));
-    run(0, st, [&](unsigned long long *tk) {
-        hipLaunchKernelGGL(unit_sums_kernel<T>, dim3(nt_all), dim3(256), 0, st, A, (unsigned long long *)dp(o_sum),
-                           (unsigned long long *)dp(o_sse), tk);
+    HIP_TRY(hipMemsetAsync(x.dp(L.o_sum), 0, L.zero_span, x.st));
+    if (x.qa) HIP_TRY(hipMemsetAsync(x.qa, 0, L.qarena_bytes, x.st));
+    if (x.wr_stat) HIP_TRY(hipMemsetAsync(x.wr_stat, 0, 256, x.st));
+    if (x.sr_stat) HIP_TRY(hipMemsetAsync(x.sr_stat, 0, 2 * 8 * SR_NSTAT, x.st));
+    return SVTGPU_OK;
+}
+
+// The unit sums on the caller's stream, then the Wiener chain (statistics, decomposition, trial rounds).  It and the
+// self-guided chain (filters, seeds, projection rounds) are independent until the RD finish: the Wiener chain runs on
+// a second stream, so its latency-bound rounds fill the gaps of the self-guided work and the other way round.
+template <typename T>
+int launch_wiener_chain(SearchCtx &x, const LrPlan &plan, const LrLayout &L) {
+    SvtGpuLrState     *s  = x.s;
+    const hipStream_t  st = x.st;
+    const SearchArgs  &A  = x.A;
+    x.run(0, st, [&](unsigned long long *tk) {
+        hipLaunchKernelGGL(unit_sums_kernel<T>, dim3(plan.nt_all()), dim3(256), 0, st, A, (unsigned long long *)x.dp(L.o_sum),
+                           (unsigned long long *)x.dp(L.o_sse), tk);
     });
     HIP_TRY(hipGetLastError());
-    // The Wiener chain (statistics, decomposition, trial rounds) and the self-guided chain (filters, seeds,
-    // projection rounds) are independent until the RD finish: the Wiener chain runs on a second stream, so its
-    // latency-bound rounds fill the gaps of the self-guided work and the other way round.
     // measurement (svtgpu_lr_profile bit 7): both chains on the caller's stream, so a kernel's duration is its own,
     // not its share of the CUs beside the other chain's kernels
-    const bool serial = prof && prof->serial;
+    const bool serial = x.prof && x.prof->serial;
     if (!s->wst && !serial)
         if (int rc = lr_make_wiener_stream(s)) return rc;
-    hipStream_t sw     = serial ? st : s->wst;
+    const hipStream_t sw = x.sw = serial ? st : s->wst;
     if (!serial) {
         HIP_TRY(hipEventRecord(s->ev_fork, st));
         HIP_TRY(hipStreamWaitEvent(sw, s->ev_fork, 0));
     }
-    for (int p = 0; p < nplanes; p++) {
-        const PlanePlan &q = pp[p];
+    // ---- phase 1: Wiener statistics ----
+    for (int p = 0; p < x.nplanes; p++) {
+        const PlanePlan &q = plan.pp[p];
         if (!q.wn) continue;
-        long long *part = (long long *)dp(o_part) + q.part_off, *mh = (long long *)dp(o_mh) + q.mh_off;
-        run(0, sw, [&](unsigned long long *tk) {
+        long long *part = (long long *)x.dp(L.o_part) + q.part_off, *mh = (long long *)x.dp(L.o_mh) + q.mh_off;
+        x.run(0, sw, [&](unsigned long long *tk) {
             launch_stats(q.win, [&](auto wc) {
                 hipLaunchKernelGGL((wiener_stats_kernel<T, decltype(wc)::value>), dim3(q.nt), dim3(256), 0, sw, A,
-                                   q.tile_base, (const unsigned long long *)dp(o_sum), part, tk);
+                                   q.tile_base, (const unsigned long long *)x.dp(L.o_sum), part, tk);
             });
         });
-        run(0, sw, [&](unsigned long long *tk) {
+        x.run(0, sw, [&](unsigned long long *tk) {
             hipLaunchKernelGGL(reduce_parts_kernel, dim3(q.n, (q.nval + 255) / 256), dim3(256), 0, sw, (const long long *)part,
-                               (const int32_t *)d_t0 + q.unit_base, q.tile_base, q.nval, mh, tk);
+                               (const int32_t *)x.dp(L.o_t0) + q.unit_base, q.tile_base, q.nval, mh, tk);
         });
         HIP_TRY(hipGetLastError());
     }
-    if (nt_sg) {
-        run(1, st, [&](unsigned long long *tk) { hipLaunchKernelGGL(sgr_flt_kernel<T>, dim3(nt_sg), dim3(SG_NT), 0, st, A, tk); });
-        HIP_TRY(hipGetLastError());
-    }
-    mark(0);
-    // ---- phase 2: descent seeds (Wiener decomposition per unit, projection solve per (unit, ep)) ----
-    SeedCfg cfg;
-    cfg.wn_use_refinement = c->wn_use_refinement, cfg.wn_max_one_step = c->wn_max_one_refinement_step;
-    cfg.sg_refine[0] = c->sg_refine[0], cfg.sg_refine[1] = c->sg_refine[1];
-    if (n_wn) {
-        run(4, sw, [&](unsigned long long *tk) {
-            hipLaunchKernelGGL(wiener_solve_kernel, dim3(n_wn), dim3(256), 0, sw, A, nplanes, (const int64_t *)dp(o_mh),
-                               cfg, (Descent *)dp(o_wds), (SvtGpuRestUnit *)dp(o_wu), tk);
+    x.t.mark(0);
+    if (plan.n_wn) {
+        // ---- phase 2: the descent seeds (the Wiener decomposition per unit) ----
+        x.run(4, sw, [&](unsigned long long *tk) {
+            hipLaunchKernelGGL(wiener_solve_kernel, dim3(plan.n_wn), dim3(256), 0, sw, A, x.nplanes, (const int64_t *)x.dp(L.o_mh),
+                               x.cfg, (Descent *)x.dp(L.o_wds), (SvtGpuRestUnit *)x.dp(L.o_wu), tk);
         });
         HIP_TRY(hipGetLastError());
-    }
-    mark(1);
-    // ---- phase 3: descent rounds on the device ----
-    if (n_wn) { // the whole Wiener descent of every unit, resident on one CU each (or a few, for the largest)
+        x.t.mark(1);
+        // ---- phase 3: the whole Wiener descent of every unit, resident on one CU each (or a few, for the largest) ----
         // the two instances back to back on the Wiener stream, each only if it has items, the big one (the long chains)
         // first; both under the trial class
+        const int           n_wr = plan.n_wr(), n_wrb = plan.n_wrb, wr_lds = plan.wr_lds, wrs_lds = plan.wrs_lds;
+        unsigned long long *pc = x.prof ? x.prof->d_px : nullptr, *wr_stat = x.wr_stat;
         if (n_wrb)
-            run(2, sw, [&](unsigned long long *tk) {
-                hipLaunchKernelGGL(wiener_res_kernel<T>, dim3(n_wrb), dim3(WR_NT), wr_lds, sw, A, (Descent *)dp(o_wds),
-                                   (const WrItem *)dp(o_witem), wr_lds, (unsigned long long *)(qa ? qa + q_wrx : nullptr),
-                                   (int32_t *)dp(o_wstat), pc, wr_stat, tk, (int)wr_classic);
+            x.run(2, sw, [&](unsigned long long *tk) {
+                hipLaunchKernelGGL(wiener_res_kernel<T>, dim3(n_wrb), dim3(WR_NT), wr_lds, sw, A, (Descent *)x.dp(L.o_wds),
+                                   (const WrItem *)x.dp(L.o_witem), wr_lds, (unsigned long long *)(x.qa ? x.qa + L.q_wrx : nullptr),
+                                   (int32_t *)x.dp(L.o_wstat), pc, wr_stat, tk, (int)lr_knobs().wr_classic);
             });
         if (n_wr > n_wrb)
-            run(2, sw, [&](unsigned long long *tk) {
-                hipLaunchKernelGGL((wiener_res_small_kernel<T, WRS_NT, WRS_RMAX>), dim3(n_wr - n_wrb), dim3(wrs_nt), wrs_lds, sw, A, (Descent *)dp(o_wds),
-                                   (const WrItem *)dp(o_witem) + n_wrb, wrs_lds, (int32_t *)dp(o_wstat), pc,
+            x.run(2, sw, [&](unsigned long long *tk) {
+                hipLaunchKernelGGL((wiener_res_small_kernel<T, WRS_NT, WRS_RMAX>), dim3(n_wr - n_wrb), dim3(lr_knobs().wr_small_nt), wrs_lds, sw, A, (Descent *)x.dp(L.o_wds),
+                                   (const WrItem *)x.dp(L.o_witem) + n_wrb, wrs_lds, (int32_t *)x.dp(L.o_wstat), pc,
                                    wr_stat ? wr_stat + 16 : nullptr, tk);
             });
         HIP_TRY(hipGetLastError());
+        x.t.mark(2);
     }
-    if (n_sr) { // the whole self-guided search of every (unit, ep), resident on one CU each (or a few)
+    if (!serial) HIP_TRY(hipEventRecord(s->ev_join, sw)); // search_frame joins it to the caller's stream
+    return SVTGPU_OK;
+}
+
+// the self-guided chain on the caller's stream: the filters of every searched ep, the resident search of every
+// (unit, ep), the best ep per unit and its clipped SSE
+template <typename T>
+int launch_sgr_chain(SearchCtx &x, const LrPlan &plan, const LrLayout &L) {
+    const hipStream_t st = x.st;
+    const SearchArgs &A  = x.A;
+    const LrKnobs    &k  = lr_knobs();
+    const int         n_sr = plan.n_sr(), n_srb = plan.n_srb, n_sg = plan.n_sg, nt_sg = plan.nt_sg, sg_planes = plan.sg_planes;
+    if (nt_sg) { // ---- phase 1: self-guided filters and moments ----
+        x.run(1, st, [&](unsigned long long *tk) { hipLaunchKernelGGL(sgr_flt_kernel<T>, dim3(nt_sg), dim3(SG_NT), 0, st, A, tk); });
+        HIP_TRY(hipGetLastError());
+    }
+    x.t.mark(0);
+    if (n_sr) { // ---- phase 3: the whole self-guided search of every (unit, ep), resident on one CU each (or a few) ----
         // the two instances back to back on this stream, each only if it has items (both under the projection class);
         // the big instance first: its items are the long chains (small first measured the same: 3717-3723 against
         // 3718-3732 Mpixels/s)
-        auto big = [&] {
-            if (n_srb)
-                run(3, st, [&](unsigned long long *tk) {
-                    const int nodes = sr_tree_nodes();
-                    auto kern = nodes == 1 ? sgr_res_kernel<T, false> : sgr_res_kernel<T, true>;
-                    hipLaunchKernelGGL(kern, dim3(n_srb), dim3(SR_NT), SR_LDS, st, A, sg_planes,
-                                       (const SrItem *)dp(o_sritem), cfg, nodes, (Descent *)dp(o_sds),
-                                       (unsigned long long *)(sr_parted ? (sr_l2 ? (uint8_t *)s->d_sxarena : qa + q_srx) : nullptr),
-                                       sr_xmode, (int32_t *)dp(o_sstat), sr_stat, tk);
-                });
-        };
-        auto small = [&] {
-            if (n_sr > n_srb)
-                run(3, st, [&](unsigned long long *tk) {
-                    hipLaunchKernelGGL(sgr_res_small_kernel<T>, dim3(n_sr - n_srb), dim3(SR_NT), SRS_LDS, st, A, sg_planes,
-                                       (const SrItem *)dp(o_sritem) + n_srb, cfg, (Descent *)dp(o_sds),
-                                       (int32_t *)dp(o_sstat), sr_stat ? sr_stat + SR_NSTAT : nullptr, tk);
-                });
-        };
-        big(), small();
+        if (n_srb)
+            x.run(3, st, [&](unsigned long long *tk) {
+                const int nodes = k.sr_tree_nodes;
+                auto kern = nodes == 1 ? sgr_res_kernel<T, false> : sgr_res_kernel<T, true>;
+                hipLaunchKernelGGL(kern, dim3(n_srb), dim3(SR_NT), SR_LDS, st, A, sg_planes,
+                                   (const SrItem *)x.dp(L.o_sritem), x.cfg, nodes, (Descent *)x.dp(L.o_sds),
+                                   (unsigned long long *)(plan.sr_parted ? (k.sr_l2 ? (uint8_t *)x.s->d_sxarena : x.qa + L.q_srx) : nullptr),
+                                   x.sr_xmode, (int32_t *)x.dp(L.o_sstat), x.sr_stat, tk);
+            });
+        if (n_sr > n_srb)
+            x.run(3, st, [&](unsigned long long *tk) {
+                hipLaunchKernelGGL(sgr_res_small_kernel<T>, dim3(n_sr - n_srb), dim3(SR_NT), SRS_LDS, st, A, sg_planes,
+                                   (const SrItem *)x.dp(L.o_sritem) + n_srb, x.cfg, (Descent *)x.dp(L.o_sds),
+                                   (int32_t *)x.dp(L.o_sstat), x.sr_stat ? x.sr_stat + SR_NSTAT : nullptr, tk);
+            });
         HIP_TRY(hipGetLastError());
     }
-    mark(2);
-    // ---- phase 4: best ep and its clipped SSE; read back the descents ----
-    if (n_sg) {
-        hipLaunchKernelGGL(sgr_best_kernel, dim3((n_sg + 255) / 256), dim3(256), 0, st, (const Descent *)dp(o_sds), A,
-                           sg_planes, n_sg, (int32_t *)dp(o_best), (int32_t *)dp(o_braw));
-        run(4, st, [&](unsigned long long *tk) {
-            hipLaunchKernelGGL(sgr_sse_kernel<T>, dim3(nt_sg), dim3(256), 0, st, A, (const int32_t *)dp(o_best),
-                               (unsigned long long *)dp(o_sse2), tk);
+    x.t.mark(2);
+    if (n_sg) { // ---- phase 4: best ep and its clipped SSE ----
+        hipLaunchKernelGGL(sgr_best_kernel, dim3((n_sg + 255) / 256), dim3(256), 0, st, (const Descent *)x.dp(L.o_sds), A,
+                           sg_planes, n_sg, (int32_t *)x.dp(L.o_best), (int32_t *)x.dp(L.o_braw));
+        x.run(4, st, [&](unsigned long long *tk) {
+            hipLaunchKernelGGL(sgr_sse_kernel<T>, dim3(nt_sg), dim3(256), 0, st, A, (const int32_t *)x.dp(L.o_best),
+                               (unsigned long long *)x.dp(L.o_sse2), tk);
         });
         HIP_TRY(hipGetLastError());
     }
-    if (!serial) {
-        HIP_TRY(hipEventRecord(s->ev_join, sw)); // the Wiener chain joins the caller's stream
-        HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));
+    return SVTGPU_OK;
+}
+
+// ---- phase 5 on the device: the records, [the gather,] rest_finish_search.  The state's units are written in stream
+// order; frame_type != nullptr waits for the result (lr_collect), nullptr returns at once ----
+int finish_on_device(SearchCtx &x, const LrPlan &plan, const LrLayout &L, int32_t *frame_type,
+                     SvtGpuLrUnitSearch *const *search_out) {
+    SvtGpuLrState                *s  = x.s;
+    const SvtGpuLrSearchControls *c  = x.c;
+    const hipStream_t             st = x.st;
+    const int                     nplanes = x.nplanes, n_all = plan.n_all(), nrec = plan.nrec;
+    if (!s->h_fout) {
+        HIP_TRY(hipHostMalloc((void **)&s->h_fout, 4 * FIN_OUT, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(s->h_fout, 0, 4 * FIN_OUT);
+        HIP_TRY(hipHostGetDevicePointer((void **)&s->h_fout_dev, s->h_fout, 0));
     }
-    if (prof)
-        if (int rc = prof->finish(st)) return rc; // fold the launch timings on the device, no read-back
-    if (fin) { // ---- phase 5 on the device: the records, [the gather,] rest_finish_search ----
-        if (!s->h_fout) {
-            HIP_TRY(hipHostMalloc((void **)&s->h_fout, 4 * FIN_OUT, hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset(s->h_fout, 0, 4 * FIN_OUT);
-            HIP_TRY(hipHostGetDevicePointer((void **)&s->h_fout_dev, s->h_fout, 0));
-        }
-        RecArgs R;
-        std::memset(&R, 0, sizeof R);
-        R.nplanes = nplanes, R.n_all = n_all;
-        for (int p = 0; p < nplanes; p++) R.wn[p] = pp[p].wn, R.sg[p] = pp[p].sg;
-        R.sse0 = (const unsigned long long *)dp(o_sse), R.sse2 = (const unsigned long long *)dp(o_sse2);
-        R.wu = (const SvtGpuRestUnit *)dp(o_wu), R.wds = (const Descent *)dp(o_wds);
-        R.best = (const int32_t *)dp(o_best), R.raw = (const int32_t *)dp(o_braw);
-        R.dst = (const int32_t *)dp(o_dst), R.rec = (SvtGpuLrUnitSearch *)dp(o_rec);
-        hipLaunchKernelGGL(lr_records_kernel, dim3((n_all + 255) / 256), dim3(256), 0, st, A, R);
+    RecArgs R;
+    std::memset(&R, 0, sizeof R);
+    R.nplanes = nplanes, R.n_all = n_all;
+    for (int p = 0; p < nplanes; p++) R.wn[p] = plan.pp[p].wn, R.sg[p] = plan.pp[p].sg;
+    R.sse0 = (const unsigned long long *)x.dp(L.o_sse), R.sse2 = (const unsigned long long *)x.dp(L.o_sse2);
+    R.wu = (const SvtGpuRestUnit *)x.dp(L.o_wu), R.wds = (const Descent *)x.dp(L.o_wds);
+    R.best = (const int32_t *)x.dp(L.o_best), R.raw = (const int32_t *)x.dp(L.o_braw);
+    R.dst = (const int32_t *)x.dp(L.o_dst), R.rec = (SvtGpuLrUnitSearch *)x.dp(L.o_rec);
+    hipLaunchKernelGGL(lr_records_kernel, dim3((n_all + 255) / 256), dim3(256), 0, st, x.A, R);
+    HIP_TRY(hipGetLastError());
+    // a picture tiled over GPUs: the zero-padded records summed over the ranks = the gather rest_finish_search reads
+    // (one contributor per unit), on the device: no host wait
+    static_assert(sizeof(SvtGpuLrUnitSearch) % 8 == 0, "records travel as uint64 words");
+    if (svtgpu_comm_tiled(s->comm))
+        if (int rc = svtgpu_comm_sum(s->comm, x.dp(L.o_rec), (size_t)nrec * sizeof(SvtGpuLrUnitSearch) / 8, true, st,
+                                     SVTGPU_XCH_LR))
+            return rc;
+    FinArgs F;
+    std::memset(&F, 0, sizeof F);
+    bool tables = false;
+    for (int p = 0; p < 3; p++) {
+        FinPlane &P = F.pl[p];
+        P.n = s->hunits[p] * s->vunits[p], P.base = plan.rbase[p];
+        for (int r = 0; r < 4; r++) P.run[r] = p < nplanes && finish_runs(c, p, P.n, r);
+        P.win1 = plane_win(c, p);
+        P.own1 = p == 0 || P.run[1], P.own2 = p == 0 || P.run[2];
+        tables |= P.run[1] || P.run[2] || P.run[3];
+    }
+    F.nplanes = nplanes, F.nrec = nrec, F.rdmult = c->rdmult;
+    for (int k = 0; k < 3; k++) F.sw[k] = c->switchable_restore_cost[k];
+    for (int k = 0; k < 2; k++) F.wn[k] = c->wiener_restore_cost[k], F.sg[k] = c->sgrproj_restore_cost[k];
+    F.rec = (const SvtGpuLrUnitSearch *)x.dp(L.o_rec);
+    F.m1 = (unsigned long long *)x.dp(L.o_m1), F.m2 = (unsigned long long *)x.dp(L.o_m2);
+    F.b1 = (uint8_t *)x.dp(L.o_b1), F.b2 = (uint8_t *)x.dp(L.o_b2);
+    F.path = (int32_t *)x.dp(L.o_path), F.units = s->d_units[0];
+    F.out = (int32_t *)x.dp(L.o_fout), F.out_host = s->h_fout_dev;
+    F.wstat = plan.n_wn ? (const int32_t *)x.dp(L.o_wstat) : nullptr, F.sstat = plan.n_sr() ? (const int32_t *)x.dp(L.o_sstat) : nullptr;
+    F.seq = ++s->fin_seq;
+    static unsigned long long *d_clk = nullptr;
+    if (lr_knobs().fin_clk && !d_clk) HIP_TRY(hipMalloc(&d_clk, 64));
+    F.clk = lr_knobs().fin_clk ? d_clk : nullptr;
+    F.wtab = lr_knobs().fin_win;
+    if (tables) {
+        hipLaunchKernelGGL(lr_fin_tables_kernel, dim3(F.pl[nplanes - 1].base + F.pl[nplanes - 1].n), dim3(64), 0,
+                           st, F);
         HIP_TRY(hipGetLastError());
-        // a picture tiled over GPUs: the zero-padded records summed over the ranks = the gather rest_finish_search reads
-        // (one contributor per unit), on the device: no host wait
-        static_assert(sizeof(SvtGpuLrUnitSearch) % 8 == 0, "records travel as uint64 words");
-        if (svtgpu_comm_tiled(s->comm))
-            if (int rc = svtgpu_comm_sum(s->comm, dp(o_rec), (size_t)nrec * sizeof(SvtGpuLrUnitSearch) / 8, true, st,
-                                         SVTGPU_XCH_LR))
-                return rc;
-        FinArgs F;
-        std::memset(&F, 0, sizeof F);
-        bool tables = false;
-        for (int p = 0; p < 3; p++) {
-            FinPlane &P = F.pl[p];
-            P.n = s->hunits[p] * s->vunits[p], P.base = rbase[p];
-            for (int r = 0; r < 4; r++) P.run[r] = p < nplanes && finish_runs(c, p, P.n, r);
-            P.win1 = plane_win(c, p);
-            P.own1 = p == 0 || P.run[1], P.own2 = p == 0 || P.run[2];
-            tables |= P.run[1] || P.run[2] || P.run[3];
-        }
-        F.nplanes = nplanes, F.nrec = nrec, F.rdmult = c->rdmult;
-        for (int k = 0; k < 3; k++) F.sw[k] = c->switchable_restore_cost[k];
-        for (int k = 0; k < 2; k++) F.wn[k] = c->wiener_restore_cost[k], F.sg[k] = c->sgrproj_restore_cost[k];
-        F.rec = (const SvtGpuLrUnitSearch *)dp(o_rec);
-        F.m1 = (unsigned long long *)dp(o_m1), F.m2 = (unsigned long long *)dp(o_m2);
-        F.b1 = (uint8_t *)dp(o_b1), F.b2 = (uint8_t *)dp(o_b2);
-        F.path = (int32_t *)dp(o_path), F.units = s->d_units[0];
-        F.out = (int32_t *)dp(o_fout), F.out_host = s->h_fout_dev;
-        F.wstat = n_wn ? (const int32_t *)dp(o_wstat) : nullptr, F.sstat = n_sr ? (const int32_t *)dp(o_sstat) : nullptr;
-        F.seq = ++s->fin_seq;
-        static const bool fin_clk = std::getenv("SVTGPU_LR_FIN_CLK") != nullptr;
-        static unsigned long long *d_clk = nullptr;
-        if (fin_clk && !d_clk) HIP_TRY(hipMalloc(&d_clk, 64));
-        F.clk = fin_clk ? d_clk : nullptr;
-        static const int fin_win = [] {
-            const char *e = std::getenv("SVTGPU_LR_FIN_WIN");
-            return e ? std::max(1, std::min(FIN_K1, std::atoi(e))) : FIN_K1;
-        }();
-        F.wtab = fin_win;
-        if (tables) {
-            hipLaunchKernelGGL(lr_fin_tables_kernel, dim3(F.pl[nplanes - 1].base + F.pl[nplanes - 1].n), dim3(64), 0,
-                               st, F);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(lr_fin_walk_kernel, dim3(1), dim3(FIN_NT), 0, st, F);
-        HIP_TRY(hipGetLastError());
-        if (search_out) { // the records, all planes' units
-            HIP_TRY(hipMemcpyAsync(hp(h_rec), dp(o_rec), sizeof(SvtGpuLrUnitSearch) * (size_t)nrec,
-                                   hipMemcpyDeviceToHost, st));
-            svtgpu_count_xfer(1, sizeof(SvtGpuLrUnitSearch) * (size_t)nrec);
-        }
-        if (!s->pin_free) HIP_TRY(hipEventCreateWithFlags(&s->pin_free, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(s->pin_free, st));
-        s->fin_pending = 1;
-        mark(3);
-        if (!frame_type) return SVTGPU_OK; // asynchronous: svtgpu_lr_read_result collects the frame types
-        if (int rc = lr_collect(s, st, frame_type)) return rc;
-        if (F.clk) {
-            unsigned long long v[8];
-            HIP_TRY(hipMemcpy(v, F.clk, 64, hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "lr_fin_walk us: r1/r2 walks %.1f, switchable walks %.1f (luma: %llu chunks, preparation "
-                                 "%.1f, steps %.1f), sums %.1f, types %.1f\n",
-                         (v[1] - v[0]) * 0.01, (v[2] - v[1]) * 0.01, v[7], v[5] * 0.01, v[6] * 0.01, (v[3] - v[2]) * 0.01,
-                         (v[4] - v[3]) * 0.01);
-        }
-        if (search_out) {
-            const SvtGpuLrUnitSearch *hr = (const SvtGpuLrUnitSearch *)hp(h_rec);
-            for (int p = 0; p < 3; p++)
-                if (search_out[p]) std::memcpy(search_out[p], hr + rbase[p], sizeof(SvtGpuLrUnitSearch) * F.pl[p].n);
-        }
-        mark(4);
-        if (timing)
-            std::fprintf(stderr, "lr_search ms: stats+flt %.3f  seeds %.3f  descents %.3f  device finish + wait %.3f\n",
-                         t_ph[0], t_ph[1], t_ph[2], t_ph[3] + t_ph[4]);
-        return SVTGPU_OK;
     }
-    Descent        *hw = (Descent *)hp(h_wds);
-    const int32_t  *hbest = (const int32_t *)hp(h_best), *hraw = (const int32_t *)hp(h_braw);
-    SvtGpuRestUnit *wu = (SvtGpuRestUnit *)hp(h_wu);
-    HIP_TRY(hipMemcpyAsync(hp(h_res), dp(o_sse), res_span, hipMemcpyDeviceToHost, st)); // every result, one copy
-    svtgpu_count_xfer(1, res_span);
-    if (int rc = svtgpu_comm_wait(s->comm, st)) return rc; // bounded when an exchange sits before it
-    if (n_wn && *(const int32_t *)hp(h_res + (o_wstat - o_sse))) { // status bits of wiener_res_kernel
-        svtgpu_set_last_hip_error(hipErrorUnknown, "LR Wiener descent: round bound or part exchange timed out",
-                                  __FILE__, __LINE__);
-        return SVTGPU_ERR_HIP;
+    hipLaunchKernelGGL(lr_fin_walk_kernel, dim3(1), dim3(FIN_NT), 0, st, F);
+    HIP_TRY(hipGetLastError());
+    if (search_out) { // the records, all planes' units
+        HIP_TRY(hipMemcpyAsync(x.hp(L.h_rec), x.dp(L.o_rec), sizeof(SvtGpuLrUnitSearch) * (size_t)nrec,
+                               hipMemcpyDeviceToHost, st));
+        svtgpu_count_xfer(1, sizeof(SvtGpuLrUnitSearch) * (size_t)nrec);
     }
+    if (!s->pin_free) HIP_TRY(hipEventCreateWithFlags(&s->pin_free, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(s->pin_free, st));
+    s->fin_pending = 1;
+    x.t.mark(3);
+    if (!frame_type) return SVTGPU_OK; // asynchronous: svtgpu_lr_read_result collects the frame types
+    if (int rc = lr_collect(s, st, frame_type)) return rc;
+    if (F.clk) {
+        unsigned long long v[8];
+        HIP_TRY(hipMemcpy(v, F.clk, 64, hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "lr_fin_walk us: r1/r2 walks %.1f, switchable walks %.1f (luma: %llu chunks, preparation "
+                             "%.1f, steps %.1f), sums %.1f, types %.1f\n",
+                     (v[1] - v[0]) * 0.01, (v[2] - v[1]) * 0.01, v[7], v[5] * 0.01, v[6] * 0.01, (v[3] - v[2]) * 0.01,
+                     (v[4] - v[3]) * 0.01);
+    }
+    if (search_out) {
+        const SvtGpuLrUnitSearch *hr = (const SvtGpuLrUnitSearch *)x.hp(L.h_rec);
+        for (int p = 0; p < 3; p++)
+            if (search_out[p]) std::memcpy(search_out[p], hr + plan.rbase[p], sizeof(SvtGpuLrUnitSearch) * F.pl[p].n);
+    }
+    x.t.mark(4);
+    if (lr_knobs().timing)
+        std::fprintf(stderr, "lr_search ms: stats+flt %.3f  seeds %.3f  descents %.3f  device finish + wait %.3f\n",
+                     x.t.ms[0], x.t.ms[1], x.t.ms[2], x.t.ms[3] + x.t.ms[4]);
+    return SVTGPU_OK;
+}
+
+// SVTGPU_WR_STATS: the per-item clocks and counts of the Wiener descent's two instances (16 words each)
+int print_wr_stats(const unsigned long long *wr_stat, const LrPlan &plan) {
+    const int n_wr = plan.n_wr(), n_wrb = plan.n_wrb;
     for (int inst = 0; inst < 2 && n_wr && wr_stat; inst++) { // the big instance, then the small one
         if (inst == 0 ? n_wrb == 0 : n_wr == n_wrb) continue;
         unsigned long long v[16];
         HIP_TRY(hipMemcpy(v, wr_stat + 16 * inst, 128, hipMemcpyDeviceToHost));
         const double n = (double)std::max(1ull, v[0]), r = (double)std::max(1ull, v[1]);
-        if (inst) std::fprintf(stderr, "wiener_res small instance (%d lanes):\n", wrs_nt);
+        if (inst) std::fprintf(stderr, "wiener_res small instance (%d lanes):\n", lr_knobs().wr_small_nt);
         else std::fprintf(stderr, "wiener_res big instance (%d lanes):\n", WR_NT);
         if (v[9])
             std::fprintf(stderr, "wiener_res: small-size items (one part, window <= %d B) %llu: %.1f candidates/item, "
@@ -3209,6 +2863,12 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
                      "us)\n", v[0], v[6], v[1] / n, v[5] / n, v[2] / r * 0.01, v[4] / r * 0.01, v[3] / r * 0.01,
                      v[7] / r * 0.01, v[8] / r * 0.01);
     }
+    return SVTGPU_OK;
+}
+
+// SVTGPU_SR_STATS: the same of the self-guided search's two instances (SR_NSTAT words each)
+int print_sr_stats(const unsigned long long *sr_stat, const LrPlan &plan) {
+    const int n_sr = plan.n_sr(), n_srb = plan.n_srb;
     for (int inst = 0; inst < 2 && n_sr && sr_stat; inst++) { // the big instance, then the small one
         if (inst == 0 ? n_srb == 0 : n_sr == n_srb) continue;
         unsigned long long v[32];
@@ -3231,15 +2891,58 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
                      v[12] / m * 0.01, v[13] / m * 0.01, v[0] - v[10], (v[3] - v[11]) / o * 0.01,
                      (v[4] - v[12]) / o * 0.01, (v[5] - v[13]) / o * 0.01);
     }
-    if (n_sr && *(const int32_t *)hp(h_res + (o_sstat - o_sse))) { // status bits of sgr_res_kernel
+    return SVTGPU_OK;
+}
+
+// the search's algorithmic bytes per profiler class (sample bytes bps, filter planes int16); the pixel-count parts at read
+void prof_static_bytes(LrProfiler *prof, const LrPlan &plan, const SearchArgs &A, int nplanes, double bps) {
+    const PlanePlan *pp = plan.pp;
+    double           all = 0, wn = 0, sgb = 0, sgp = 0, sgw = 0; // sgw: filter planes written (equal r = 1 shared)
+    for (int p = 0; p < nplanes; p++) {
+        double area = 0;
+        for (int i = pp[p].tile_base; i < pp[p].tile_base + pp[p].nt; i++) area += (double)plan.tiles[i].w * plan.tiles[i].h;
+        all += area;
+        if (pp[p].wn) wn += area;
+        if (pp[p].sg) sgb += area, sgp += area * pp[p].ne;
+        for (int k = 0; k < pp[p].ne; k++)
+            sgw += area * ((kHostSgrR[A.pl[p].eps[k]][0] > 0) + (kHostSgrR[A.pl[p].eps[k]][1] > 0 && A.pl[p].f1e[k] == k));
+    }
+    prof->bps = bps;
+    prof->static_bytes[0] += (all + wn) * 2 * bps; // unit sums, statistics: x and source
+    prof->static_bytes[1] += sgb * bps + sgw * 2;     // filters: x in, the int16 planes out (each once)
+    prof->static_bytes[3] += sgb * 2 * bps + sgp * 4; // resident search: x, source and every ep's planes, once
+    prof->static_bytes[4] += sgb * (4 + 2 * bps);     // the chosen ep's SSE
+}
+
+// ---- phase 5 on the host: every result read back in one copy, the per-unit records (search_out) and, for the whole
+// frame (frame_type != nullptr), the RD finish and the upload of the state's units ----
+int finish_on_host(SearchCtx &x, const LrPlan &plan, const LrLayout &L, int32_t *frame_type,
+                   SvtGpuLrUnitSearch *const *search_out) {
+    SvtGpuLrState    *s  = x.s;
+    const hipStream_t st = x.st;
+    const PlanePlan  *pp = plan.pp;
+    const int         nplanes = x.nplanes, n_all = plan.n_all();
+    Descent        *hw = (Descent *)x.hp(L.host(L.o_wds));
+    const int32_t  *hbest = (const int32_t *)x.hp(L.host(L.o_best)), *hraw = (const int32_t *)x.hp(L.host(L.o_braw));
+    SvtGpuRestUnit *wu = (SvtGpuRestUnit *)x.hp(L.host(L.o_wu));
+    HIP_TRY(hipMemcpyAsync(x.hp(L.h_res), x.dp(L.o_sse), L.res_span, hipMemcpyDeviceToHost, st)); // every result, one copy
+    svtgpu_count_xfer(1, L.res_span);
+    if (int rc = svtgpu_comm_wait(s->comm, st)) return rc; // bounded when an exchange sits before it
+    if (plan.n_wn && *(const int32_t *)x.hp(L.host(L.o_wstat))) { // status bits of wiener_res_kernel
+        svtgpu_set_last_hip_error(hipErrorUnknown, "LR Wiener descent: round bound or part exchange timed out",
+                                  __FILE__, __LINE__);
+        return SVTGPU_ERR_HIP;
+    }
+    if (int rc = print_wr_stats(x.wr_stat, plan)) return rc;
+    if (int rc = print_sr_stats(x.sr_stat, plan)) return rc;
+    if (plan.n_sr() && *(const int32_t *)x.hp(L.host(L.o_sstat))) { // status bits of sgr_res_kernel
         svtgpu_set_last_hip_error(hipErrorUnknown, "LR self-guided descent: pass bound, part plan or exchange failed",
                                   __FILE__, __LINE__);
         return SVTGPU_ERR_HIP;
     }
-    mark(3);
-    // ---- phase 5 (host): per-unit results and, for the whole frame, the RD finish ----
-    const uint64_t                 *sse0 = (const uint64_t *)hp(h_sse), *sse2 = (const uint64_t *)hp(h_sse2);
-    SvtGpuRestUnit                 *out  = (SvtGpuRestUnit *)hp(h_out);
+    x.t.mark(3);
+    const uint64_t                 *sse0 = (const uint64_t *)x.hp(L.host(L.o_sse)), *sse2 = (const uint64_t *)x.hp(L.host(L.o_sse2));
+    SvtGpuRestUnit                 *out  = (SvtGpuRestUnit *)x.hp(L.h_out);
     std::vector<SvtGpuLrUnitSearch> rs(n_all);
     for (int p = 0; p < nplanes; p++) {
         const PlanePlan &q = pp[p];
@@ -3262,45 +2965,86 @@ int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *sr
                 R.sgrproj.xqd[0] = hraw[2 * gu], R.sgrproj.xqd[1] = hraw[2 * gu + 1];
                 R.sse[2] = (int64_t)sse2[gu];
             }
-            if (search_out && search_out[p]) search_out[p][uloc[gu]] = R;
+            if (search_out && search_out[p]) search_out[p][plan.uloc[gu]] = R;
         }
     }
     if (frame_type) { // whole frame: units are in plane order, uloc[gu] == u
         std::vector<FinRusi> rusi((size_t)std::max(1, pp[0].n));
         std::memset(rusi.data(), 0, sizeof(FinRusi) * rusi.size());
         for (int p = 0; p < nplanes; p++)
-            finish_plane_shared(c, p, pp[p].win, rs.data() + pp[p].unit_base, pp[p].n, rusi.data(), &frame_type[p],
+            finish_plane_shared(x.c, p, pp[p].win, rs.data() + pp[p].unit_base, pp[p].n, rusi.data(), &frame_type[p],
                                 out + pp[p].unit_base);
-    }
-    if (frame_type) // d_units holds the planes back to back in the same order: one upload
+        // d_units holds the planes back to back in the same order: one upload
         HIP_TRY(hipMemcpyAsync(s->d_units[0], out, sizeof(SvtGpuRestUnit) * n_all, hipMemcpyHostToDevice, st));
-    if (frame_type) svtgpu_count_xfer(0, sizeof(SvtGpuRestUnit) * n_all);
-    if (prof) { // algorithmic bytes per class (sample bytes bps, filter planes int16); the pixel-count parts at read
-        const double bps = (double)sizeof(T);
-        double       all = 0, wn = 0, sgb = 0, sgp = 0, sgw = 0; // sgw: filter planes written (equal r = 1 shared)
-        for (int p = 0; p < nplanes; p++) {
-            double area = 0;
-            for (int i = pp[p].tile_base; i < pp[p].tile_base + pp[p].nt; i++) area += (double)tiles[i].w * tiles[i].h;
-            all += area;
-            if (pp[p].wn) wn += area;
-            if (pp[p].sg) sgb += area, sgp += area * pp[p].ne;
-            for (int k = 0; k < pp[p].ne; k++)
-                sgw += area * ((kHostSgrR[A.pl[p].eps[k]][0] > 0) + (kHostSgrR[A.pl[p].eps[k]][1] > 0 && A.pl[p].f1e[k] == k));
-        }
-        prof->bps = bps;
-        prof->static_bytes[0] += (all + wn) * 2 * bps; // unit sums, statistics: x and source
-        prof->static_bytes[1] += sgb * bps + sgw * 2;     // filters: x in, the int16 planes out (each once)
-        prof->static_bytes[3] += sgb * 2 * bps + sgp * 4; // resident search: x, source and every ep's planes, once
-        prof->static_bytes[4] += sgb * (4 + 2 * bps);     // the chosen ep's SSE
+        svtgpu_count_xfer(0, sizeof(SvtGpuRestUnit) * n_all);
     }
     // no wait for the units upload: the next search waits for this event before it rewrites the pinned staging
     if (!s->pin_free) HIP_TRY(hipEventCreateWithFlags(&s->pin_free, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(s->pin_free, st));
-    mark(4);
-    if (timing)
+    x.t.mark(4);
+    if (lr_knobs().timing)
         std::fprintf(stderr, "lr_search ms: stats+flt %.3f  seeds %.3f  descents %.3f  best %.3f  finish %.3f\n",
-                     t_ph[0], t_ph[1], t_ph[2], t_ph[3], t_ph[4]);
+                     x.t.ms[0], x.t.ms[1], x.t.ms[2], x.t.ms[3], x.t.ms[4]);
     return SVTGPU_OK;
+}
+
+// The search of the units of `band` in planes 0..nplanes-1: the plan, the buffers, the two chains, the finish.
+// fin == 0: the records come back to the host (search_out) and, for the whole frame (frame_type != nullptr), the RD
+// finish runs there.  fin == 1: the records and the RD finish stay on the device (a tiled picture all-reduces the
+// records on the device first), the state's units are written in stream order; frame_type != nullptr then waits for
+// the result and reads the frame types (and the records into search_out), nullptr returns at once (the asynchronous
+// search: svtgpu_lr_read_result collects it).
+template <typename T>
+int search_frame(SvtGpuLrState *s, const SvtGpuFrame *rec, const SvtGpuFrame *src, const SvtGpuLrSearchControls *c,
+                 int nplanes, const Band &band, int32_t *frame_type, SvtGpuLrUnitSearch *const *search_out,
+                 hipStream_t st, int fin) {
+    SearchCtx x; // its phase timer starts here
+    x.s = s, x.c = c, x.nplanes = nplanes, x.st = st, x.prof = (LrProfiler *)s->prof;
+    LrPlanIn in;
+    for (int p = 0; p < 3; p++) {
+        in.W[p] = lr_plane_w(s, p), in.H[p] = lr_plane_h(s, p), in.unit_size[p] = s->unit_size[p];
+        in.hunits[p] = s->hunits[p], in.vunits[p] = s->vunits[p];
+    }
+    in.band = band, in.nplanes = nplanes;
+    LrPlan plan;
+    if (int rc = lr_plan_build(plan, in, *c, lr_knobs())) return rc;
+    if (plan.units.empty()) return SVTGPU_OK; // an empty band
+    const LrLayout L = lr_layout(plan, sizeof(Descent));
+    if (int rc = ensure_buffers(x, plan, L)) return rc;
+    fill_search_args(x, plan, L, rec, src);
+    if (x.prof) x.prof->start();
+    if (int rc = upload_plan_and_zero(x, plan, L)) return rc;
+    if (int rc = launch_wiener_chain<T>(x, plan, L)) return rc;
+    if (int rc = launch_sgr_chain<T>(x, plan, L)) return rc;
+    if (x.sw != st) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0)); // the Wiener chain joins the caller's stream
+    if (x.prof)
+        if (int rc = x.prof->finish(st)) return rc; // fold the launch timings on the device, no read-back
+    if (fin) return finish_on_device(x, plan, L, frame_type, search_out);
+    if (int rc = finish_on_host(x, plan, L, frame_type, search_out)) return rc;
+    if (x.prof) prof_static_bytes(x.prof, plan, x.A, nplanes, (double)sizeof(T));
+    return SVTGPU_OK;
+}
+
+// the 8- / 16-bit dispatch of search_frame
+int run_search(SvtGpuLrState *s, const SvtGpuFrame *recon, const SvtGpuFrame *source, const SvtGpuLrSearchControls *ctrls,
+               int nplanes, const Band &band, int32_t *frame_type, SvtGpuLrUnitSearch *const *search_out, hipStream_t st,
+               int fin) {
+    return recon->bytes_per_sample == 2
+        ? search_frame<uint16_t>(s, recon, source, ctrls, nplanes, band, frame_type, search_out, st, fin)
+        : search_frame<uint8_t>(s, recon, source, ctrls, nplanes, band, frame_type, search_out, st, fin);
+}
+Band band_whole(const SvtGpuLrState *s) {
+    Band b;
+    for (int p = 0; p < 3; p++) b.rb[p] = b.cb[p] = 0, b.re[p] = s->vunits[p], b.ce[p] = s->hunits[p];
+    return b;
+}
+// the state's tile of a picture tiled over GPUs (svtgpu_lr_set_tile); the whole frame when it is not tiled
+Band band_of_tile(const SvtGpuLrState *s) {
+    if (!svtgpu_comm_tiled(s->comm)) return band_whole(s);
+    Band b;
+    for (int p = 0; p < 3; p++)
+        b.cb[p] = s->tile_units[p][0], b.rb[p] = s->tile_units[p][1], b.ce[p] = s->tile_units[p][2], b.re[p] = s->tile_units[p][3];
+    return b;
 }
 } // namespace
 
@@ -3346,11 +3090,7 @@ void lr_profiler_destroy(void *prof) { delete (LrProfiler *)prof; }
 int lr_make_wiener_stream(SvtGpuLrState *s) {
     int least = 0, greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    static const int wprio = [] { // SVTGPU_WN_PRIO=0: the Wiener chain at normal priority (A/B)
-        const char *e = std::getenv("SVTGPU_WN_PRIO");
-        return e ? std::atoi(e) : 1;
-    }();
-    HIP_TRY(hipStreamCreateWithPriority(&s->wst, hipStreamNonBlocking, wprio ? greatest : least));
+    HIP_TRY(hipStreamCreateWithPriority(&s->wst, hipStreamNonBlocking, lr_knobs().wn_prio ? greatest : least));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
     return SVTGPU_OK;
@@ -3410,23 +3150,10 @@ extern "C" int svtgpu_lr_search_frame(SvtGpuLrState *s, const SvtGpuFrame *recon
     hipStream_t st      = pick_stream(s->ctx, stream);
     const int   nplanes = searched_planes(ctrls);
     for (int p = 0; p < 3; p++) frame_type_out[p] = SVTGPU_RESTORE_NONE;
-    if (!lr_finish_on_host()) { // the records and the RD finish on the device; one wait at the end
-        int32_t rb[3], re[3], cb[3], ce[3];
-        for (int p = 0; p < 3; p++)
-            cb[p] = s->tile_units[p][0], rb[p] = s->tile_units[p][1], ce[p] = s->tile_units[p][2], re[p] = s->tile_units[p][3];
-        if (!svtgpu_comm_tiled(s->comm))
-            for (int p = 0; p < 3; p++) rb[p] = cb[p] = 0, re[p] = s->vunits[p], ce[p] = s->hunits[p];
-        return recon->bytes_per_sample == 2
-            ? search_frame<uint16_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, frame_type_out, search_out, st, 1)
-            : search_frame<uint8_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, frame_type_out, search_out, st, 1);
-    }
-    if (!svtgpu_comm_tiled(s->comm)) {
-        int32_t rb[3] = {0, 0, 0}, re[3] = {s->vunits[0], s->vunits[1], s->vunits[2]};
-        int32_t cb[3] = {0, 0, 0}, ce[3] = {s->hunits[0], s->hunits[1], s->hunits[2]};
-        return recon->bytes_per_sample == 2
-            ? search_frame<uint16_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, frame_type_out, search_out, st)
-            : search_frame<uint8_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, frame_type_out, search_out, st);
-    }
+    if (!lr_knobs().finish_on_host) // the records and the RD finish on the device; one wait at the end
+        return run_search(s, recon, source, ctrls, nplanes, band_of_tile(s), frame_type_out, search_out, st, 1);
+    if (!svtgpu_comm_tiled(s->comm))
+        return run_search(s, recon, source, ctrls, nplanes, band_whole(s), frame_type_out, search_out, st, 0);
     // a picture tiled over GPUs: this rank's units, the zero-padded records summed over the ranks (one contributor per
     // unit: the gather restoration_seg_search's segments leave for rest_finish_search), then the finish of every
     // plane on every rank (EbRestorationPick.c:1555-1634, sequential over the units), identical everywhere
@@ -3435,12 +3162,7 @@ extern "C" int svtgpu_lr_search_frame(SvtGpuLrState *s, const SvtGpuFrame *recon
     std::vector<SvtGpuLrUnitSearch> rec(nrec);
     std::memset(rec.data(), 0, sizeof(SvtGpuLrUnitSearch) * nrec);
     SvtGpuLrUnitSearch *outs[3] = {rec.data() + base[0], rec.data() + base[1], rec.data() + base[2]};
-    int32_t             rb[3], re[3], cb[3], ce[3];
-    for (int p = 0; p < 3; p++)
-        cb[p] = s->tile_units[p][0], rb[p] = s->tile_units[p][1], ce[p] = s->tile_units[p][2], re[p] = s->tile_units[p][3];
-    int rc = recon->bytes_per_sample == 2
-        ? search_frame<uint16_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, nullptr, outs, st)
-        : search_frame<uint8_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, nullptr, outs, st);
+    int rc = run_search(s, recon, source, ctrls, nplanes, band_of_tile(s), nullptr, outs, st, 0);
     if (rc) return rc;
     static_assert(sizeof(SvtGpuLrUnitSearch) % 8 == 0, "records travel as uint64 words");
     if ((rc = svtgpu_comm_sum(s->comm, rec.data(), nrec * sizeof(SvtGpuLrUnitSearch) / 8, false, st, SVTGPU_XCH_LR))) return rc;
@@ -3492,10 +3214,9 @@ extern "C" int svtgpu_lr_search_units(SvtGpuLrState *s, const SvtGpuFrame *recon
         if (row_begin[p] < 0 || row_end[p] > s->vunits[p] || row_begin[p] > row_end[p] || !search_out[p])
             return SVTGPU_ERR_INVALID_ARG;
     hipStream_t st = pick_stream(s->ctx, stream);
-    const int32_t cb[3] = {0, 0, 0}, ce[3] = {s->hunits[0], s->hunits[1], s->hunits[2]};
-    return recon->bytes_per_sample == 2
-        ? search_frame<uint16_t>(s, recon, source, ctrls, nplanes, row_begin, row_end, cb, ce, nullptr, search_out, st)
-        : search_frame<uint8_t>(s, recon, source, ctrls, nplanes, row_begin, row_end, cb, ce, nullptr, search_out, st);
+    Band band = band_whole(s); // every unit column of the rows asked for
+    for (int p = 0; p < nplanes; p++) band.rb[p] = row_begin[p], band.re[p] = row_end[p];
+    return run_search(s, recon, source, ctrls, nplanes, band, nullptr, search_out, st, 0);
 }
 
 extern "C" int svtgpu_lr_finish_plane(const SvtGpuLrSearchControls *ctrls, int32_t plane, int32_t nunits,
@@ -3544,21 +3265,14 @@ extern "C" int svtgpu_lr_search_frame_async(SvtGpuLrState *s, const SvtGpuFrame 
     if (int rc = check_search_args(s, recon, source, ctrls)) return rc;
     hipStream_t st      = pick_stream(s->ctx, stream);
     const int   nplanes = searched_planes(ctrls);
-    if (lr_finish_on_host()) { // the host finish waits anyway: the synchronous search, its frame types kept
+    if (lr_knobs().finish_on_host) { // the host finish waits anyway: the synchronous search, its frame types kept
         int32_t ft[3];
         if (int rc = svtgpu_lr_search_frame(s, recon, source, ctrls, ft, nullptr, stream)) return rc;
         for (int p = 0; p < 3; p++) s->last_ft[p] = ft[p];
         s->fin_pending = 0;
         return SVTGPU_OK;
     }
-    int32_t rb[3], re[3], cb[3], ce[3];
-    for (int p = 0; p < 3; p++)
-        cb[p] = s->tile_units[p][0], rb[p] = s->tile_units[p][1], ce[p] = s->tile_units[p][2], re[p] = s->tile_units[p][3];
-    if (!svtgpu_comm_tiled(s->comm))
-        for (int p = 0; p < 3; p++) rb[p] = cb[p] = 0, re[p] = s->vunits[p], ce[p] = s->hunits[p];
-    return recon->bytes_per_sample == 2
-        ? search_frame<uint16_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, nullptr, nullptr, st, 1)
-        : search_frame<uint8_t>(s, recon, source, ctrls, nplanes, rb, re, cb, ce, nullptr, nullptr, st, 1);
+    return run_search(s, recon, source, ctrls, nplanes, band_of_tile(s), nullptr, nullptr, st, 1);
 }
 
 extern "C" int svtgpu_lr_read_units(SvtGpuLrState *s, int32_t plane, SvtGpuRestUnit *units_out, void *stream) {

@@ -23,7 +23,7 @@
 /* With bd = 8 the highbd arithmetic equals the 8-bit int8 arithmetic of filter4/8/14.            */
 /* ------------------------------------------------------------------------------------------- */
 static int clamp_sc(int t, int bd) { /* signed_char_clamp(_high) (EbDeblockingCommon.c:26-35) */
-    const int lo = -128 << (bd - 8), hi = (128 << (bd - 8)) - 1;
+    const int lo = -(128 << (bd - 8)), hi = (128 << (bd - 8)) - 1;
     return CLAMP_(t, lo, hi);
 }
 
@@ -214,6 +214,19 @@ static void lf_info_init(LfInfo *L, const SvtGpuLfParams *p, int plane_start, in
     }
 }
 
+/* what lf_info_init fills for planes [plane_start, plane_end): lvl[3][8][2][8][2] ([plane][segment][dir][ref][mode];
+ * entries it does not write stay zero) and the thresholds mblim / lim / hev [64] */
+void oracle_dlf_level_tables(const SvtGpuLfParams *p, int plane_start, int plane_end, uint8_t *lvl, uint8_t *mblim,
+                             uint8_t *lim, uint8_t *hev) {
+    LfInfo L;
+    memset(&L, 0, sizeof L);
+    lf_info_init(&L, p, plane_start, plane_end);
+    memcpy(lvl, L.lvl, sizeof L.lvl);
+    memcpy(mblim, L.mblim, 64);
+    memcpy(lim, L.lim, 64);
+    memcpy(hev, L.hev, 64);
+}
+
 /* ------------------------------------------------------------------------------------------- */
 /* Frame driver                                                                                  */
 /* ------------------------------------------------------------------------------------------- */
@@ -370,16 +383,12 @@ static int64_t try_level(OracleFrame *recon, const OracleFrame *backup, const Or
     return e;
 }
 
-/* search_filter_level (:886-991) */
-static int search_level(OracleFrame *recon, OracleFrame *backup, const OracleFrame *src, const SvtGpuLfMi *mi,
-                        SvtGpuLfParams *p, const int last[4], int dlf_avg, int early_exit, int only4x4, int plane,
-                        int dir) {
-    int lvl = plane == 0 ? (dlf_avg ? last[0] : last[dir]) : last[plane + 1];
-    int mid = CLAMP_(lvl, 0, 63), step = mid < 16 ? 4 : mid / 4, direction = 0;
+/* search_filter_level (:886-991) from the start level on: err_fn(ctx, level) is try_filter_frame's error of a level */
+int oracle_dlf_search_level_fn(OracleDlfErrFn err_fn, void *ctx, int start, int early_exit, int only4x4) {
+    int mid = CLAMP_(start, 0, 63), step = mid < 16 ? 4 : mid / 4, direction = 0;
     int64_t ss_err[64];
     for (int i = 0; i < 64; i++) ss_err[i] = -1;
-    copy_plane(backup, recon, plane);
-    int64_t best_err = try_level(recon, backup, src, mi, p, mid, plane, dir);
+    int64_t best_err = err_fn(ctx, mid);
     int     best     = mid;
     ss_err[mid]      = best_err;
     int conv = 0;
@@ -390,7 +399,7 @@ static int search_level(OracleFrame *recon, OracleFrame *backup, const OracleFra
             bias >>= 1;
         if (direction <= 0 && lo != mid) {
             if (ss_err[lo] < 0)
-                ss_err[lo] = try_level(recon, backup, src, mi, p, lo, plane, dir);
+                ss_err[lo] = err_fn(ctx, lo);
             if (ss_err[lo] < best_err + bias) {
                 if (ss_err[lo] < best_err)
                     best_err = ss_err[lo];
@@ -399,7 +408,7 @@ static int search_level(OracleFrame *recon, OracleFrame *backup, const OracleFra
         }
         if (direction >= 0 && hi != mid) {
             if (ss_err[hi] < 0)
-                ss_err[hi] = try_level(recon, backup, src, mi, p, hi, plane, dir);
+                ss_err[hi] = err_fn(ctx, hi);
             if (ss_err[hi] < best_err - bias) {
                 best_err = ss_err[hi];
                 best     = hi;
@@ -418,6 +427,27 @@ static int search_level(OracleFrame *recon, OracleFrame *backup, const OracleFra
         }
     }
     return best;
+}
+
+typedef struct TryCtx {
+    OracleFrame       *recon, *backup;
+    const OracleFrame *src;
+    const SvtGpuLfMi  *mi;
+    SvtGpuLfParams    *p;
+    int                plane, dir;
+} TryCtx;
+static int64_t try_level_of(void *ctx, int lvl) {
+    const TryCtx *c = (const TryCtx *)ctx;
+    return try_level(c->recon, c->backup, c->src, c->mi, c->p, lvl, c->plane, c->dir);
+}
+
+static int search_level(OracleFrame *recon, OracleFrame *backup, const OracleFrame *src, const SvtGpuLfMi *mi,
+                        SvtGpuLfParams *p, const int last[4], int dlf_avg, int early_exit, int only4x4, int plane,
+                        int dir) {
+    const int lvl = plane == 0 ? (dlf_avg ? last[0] : last[dir]) : last[plane + 1];
+    TryCtx    c   = {recon, backup, src, mi, p, plane, dir};
+    copy_plane(backup, recon, plane);
+    return oracle_dlf_search_level_fn(try_level_of, &c, lvl, early_exit, only4x4);
 }
 
 /* svt_av1_pick_filter_level, FULL_IMAGE branch (:1146-1250) minus the reference-frame averaging

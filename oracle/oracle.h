@@ -74,6 +74,16 @@ int oracle_dlf_frame_crop(OracleFrame *f, const SvtGpuLfMi *mi, const SvtGpuLfPa
 int oracle_dlf_pick(OracleFrame *recon, const OracleFrame *src, const SvtGpuLfMi *mi, SvtGpuLfParams *p, int dlf_avg,
                     int dlf_avg_uv, int temporal_layer_index, int early_exit, int only4x4);
 
+/* the bisection of search_filter_level alone: err_fn(ctx, level) gives the error try_filter_frame measures at a level
+ * (called once per level); start = the level the search starts from; returns the picked level */
+typedef int64_t (*OracleDlfErrFn)(void *ctx, int level);
+int oracle_dlf_search_level_fn(OracleDlfErrFn err_fn, void *ctx, int start, int early_exit, int only4x4);
+/* the level tables svt_av1_loop_filter_frame_init fills for planes [plane_start, plane_end): lvl[3][8][2][8][2]
+ * ([plane][segment][dir][ref][mode]; entries it does not write are zero: a plane that is off, every plane after a luma
+ * that is off, and with mode_ref_delta_enabled reference 0's mode 1) and the thresholds mblim / lim / hev [64] */
+void oracle_dlf_level_tables(const SvtGpuLfParams *p, int plane_start, int plane_end, uint8_t *lvl, uint8_t *mblim,
+                             uint8_t *lim, uint8_t *hev);
+
 /* ---- mode-decision distortion (md_oracle.c) ---- */
 uint32_t oracle_sad(const uint8_t *a, int as, const uint8_t *b, int bs, int w, int h);
 uint32_t oracle_sad16(const uint16_t *a, int as, const uint16_t *b, int bs, int w, int h);

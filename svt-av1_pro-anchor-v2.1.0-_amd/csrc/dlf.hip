@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "svtgpu_internal.h"
+#include "dlf_levels.h"
 
 #ifndef DLF_EXP
 #define DLF_EXP 0 // development experiments (bit 0: no vertical pass, bit 1: no horizontal pass); 0 = real kernel
@@ -200,9 +201,6 @@ constexpr int TILE  = 64;
 constexpr int APRON = 12;
 constexpr int LW    = TILE + 2 * APRON; // 88 samples per LDS row
 constexpr int NTHR  = 256;
-constexpr int MAX_TRIALS = 2; // levels per trial launch (the bisection's lo and hi candidates)
-
-constexpr int MAX_JOBS   = 3; // planes per launch: the Y, U and V level searches run side by side
 
 // one plane of a launch
 struct DlfPlaneJob {
@@ -217,15 +215,6 @@ struct DlfPlaneJob {
     int32_t         ox, oy, ow, oh; // the region filtered / measured (a tile of a picture split over GPUs)
     int32_t         ntrial;
     uint8_t         lvl[MAX_TRIALS][2][128]; // [trial][dir][class] filter level
-};
-
-// a device-resident level search (svtgpu_dlf_pick with SVTGPU_DLF_DEVICE=1): the levels and level tables of the next
-// trial launch, written by dlf_search_step_kernel from the previous launch's SSEs (no host decision between trials)
-struct DlfDevPlan {
-    int32_t ntrial[MAX_JOBS];                   // levels of each job in the next trial launch (0: the job has none)
-    int32_t lv[MAX_JOBS][MAX_TRIALS];
-    uint8_t lvl[MAX_JOBS][MAX_TRIALS][2][128];  // [job][trial][dir][class]
-    int32_t done;                               // every search has finished
 };
 
 struct DlfTileArgs {
@@ -671,60 +660,6 @@ struct SvtGpuDlfState {
 
 namespace {
 
-// level tables: svt_av1_loop_filter_frame_init + svt_aom_update_sharpness (EbDeblockingCommon.c:76-139, 554-572)
-struct LevelTables {
-    uint8_t lvl[3][2][128]; // [plane][dir][segment*16 + ref*2 + mode_lf]
-    uint8_t mblim[64], lim[64], hev[64];
-};
-
-__host__ __device__ static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// the level per (segment, reference, mode) class of one plane and direction whose base level is lv
-// (svt_av1_loop_filter_frame_init, EbDeblockingFilter.c)
-// one (segment, reference, mode) class of it: cls = seg * 16 + ref * 2 + mode
-__host__ __device__ static inline uint8_t level_entry(const SvtGpuLfParams &p, int pl, int dir, int lv, int cls) {
-    const int feat[3][2] = {{1, 2}, {3, 3}, {4, 4}}; // SEG_LVL_ALT_LF_{Y_V, Y_H, U, V}
-    const int seg = cls >> 4, ref = (cls >> 1) & 7, mode = cls & 1;
-    int       ls  = lv;
-    if (p.segmentation_enabled && p.seg_feature_enabled[seg][feat[pl][dir]])
-        ls = clampi(ls + p.seg_feature_data[seg][feat[pl][dir]], 0, 63);
-    int v = ls;
-    if (p.mode_ref_delta_enabled) {
-        const int scale = 1 << (ls >> 5);
-        v = ls + p.ref_deltas[ref] * scale + (ref > 0 ? p.mode_deltas[mode] * scale : 0);
-        v = clampi(v, 0, 63);
-    }
-    return (uint8_t)v;
-}
-
-__host__ __device__ static void fill_level_table(const SvtGpuLfParams &p, int pl, int dir, int lv, uint8_t *out) {
-    for (int cls = 0; cls < 128; cls++) out[cls] = level_entry(p, pl, dir, lv, cls);
-}
-
-void build_level_tables(const SvtGpuLfParams &p, LevelTables &L) {
-    std::memset(&L, 0, sizeof L);
-    const int sh = p.sharpness_level;
-    for (int l = 0; l < 64; l++) {
-        int inside = l >> ((sh > 0) + (sh > 4));
-        if (sh > 0) inside = std::min(inside, 9 - sh);
-        inside     = std::max(inside, 1);
-        L.lim[l]   = (uint8_t)inside;
-        L.mblim[l] = (uint8_t)(2 * (l + 2) + inside);
-        L.hev[l]   = (uint8_t)(l >> 4);
-    }
-    const int base[3][2] = {{p.filter_level[0], p.filter_level[1]},
-                            {p.filter_level_u, p.filter_level_u},
-                            {p.filter_level_v, p.filter_level_v}};
-    for (int pl = 0; pl < 3; pl++)
-        for (int dir = 0; dir < 2; dir++) fill_level_table(p, pl, dir, base[pl][dir], L.lvl[pl][dir]);
-}
-
-// is the plane filtered at all with these levels (svt_aom_loop_filter_sb :575-582)
-__host__ __device__ bool plane_active(const SvtGpuLfParams &p, int plane) {
-    if (plane == 0) return p.filter_level[0] || p.filter_level[1];
-    return plane == 1 ? p.filter_level_u != 0 : p.filter_level_v != 0;
-}
-
 DlfPlaneJob plane_job(SvtGpuDlfState *s, const SvtGpuFrame *f, int plane, bool trial) {
     DlfPlaneJob j;
     std::memset(&j, 0, sizeof j);
@@ -746,7 +681,19 @@ DlfPlaneJob plane_job(SvtGpuDlfState *s, const SvtGpuFrame *f, int plane, bool t
     return j;
 }
 
-DlfTileArgs base_args(const SvtGpuFrame *f, const LevelTables &L) {
+// one plane of a trial launch: recon filtered at `ntrial` levels and measured against the source
+DlfPlaneJob trial_job(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *source, int plane, int ntrial) {
+    DlfPlaneJob j = plane_job(s, recon, plane, true);
+    j.src = recon->plane[plane], j.src_stride = recon->stride[plane];
+    j.ref = source->plane[plane], j.ref_stride = source->stride[plane];
+    j.ntrial = ntrial;
+    return j;
+}
+
+// a launch's arguments with no job yet: the bit depth and the per-level thresholds of p's sharpness
+DlfTileArgs base_args(const SvtGpuFrame *f, const SvtGpuLfParams &p) {
+    LevelThresholds L;
+    build_thresholds(p.sharpness_level, L);
     DlfTileArgs a;
     std::memset(&a, 0, sizeof a);
     a.bd = f->bit_depth;
@@ -756,19 +703,23 @@ DlfTileArgs base_args(const SvtGpuFrame *f, const LevelTables &L) {
     return a;
 }
 
+// launches the instance of a kernel template for the frame's sample size: k8 (uint8_t) or k16 (uint16_t)
+template <typename... P, typename... A>
+int launch_for_samples(int bps, void (*k8)(P...), void (*k16)(P...), int grid, hipStream_t st, const A &...args) {
+    hipLaunchKernelGGL(bps == 2 ? k16 : k8, dim3(grid), dim3(NTHR), 0, st, args...);
+    HIP_TRY(hipGetLastError());
+    return SVTGPU_OK;
+}
+
 int launch_tile(const DlfTileArgs &a0, int bps, bool trial, hipStream_t st) {
     int tiles = 0; // workgroups: one per tile (apply) or per (tile, trial)
     for (int j = 0; j < a0.njob; j++) tiles += a0.job[j].tiles * (trial ? a0.job[j].ntrial : 1);
     DlfTileArgs a = a0;
     a.wgclk       = svtgpu_wgclk_begin(tiles);
-    if (bps == 2) {
-        if (trial) hipLaunchKernelGGL((dlf_tile_kernel<uint16_t, true>), dim3(tiles), dim3(NTHR), 0, st, a);
-        else       hipLaunchKernelGGL((dlf_tile_kernel<uint16_t, false>), dim3(tiles), dim3(NTHR), 0, st, a);
-    } else {
-        if (trial) hipLaunchKernelGGL((dlf_tile_kernel<uint8_t, true>), dim3(tiles), dim3(NTHR), 0, st, a);
-        else       hipLaunchKernelGGL((dlf_tile_kernel<uint8_t, false>), dim3(tiles), dim3(NTHR), 0, st, a);
-    }
-    HIP_TRY(hipGetLastError());
+    if (int rc = trial ? launch_for_samples(bps, dlf_tile_kernel<uint8_t, true>, dlf_tile_kernel<uint16_t, true>, tiles, st, a)
+                       : launch_for_samples(bps, dlf_tile_kernel<uint8_t, false>, dlf_tile_kernel<uint16_t, false>, tiles, st,
+                                            a))
+        return rc;
     svtgpu_wgclk_end(trial ? "dlf_trial" : "dlf_apply", tiles, st);
     return SVTGPU_OK;
 }
@@ -776,144 +727,10 @@ int launch_tile(const DlfTileArgs &a0, int bps, bool trial, hipStream_t st) {
 bool frame_matches(const SvtGpuDlfState *s, const SvtGpuFrame *f) {
     return f && f->width == s->width && f->height == s->height && (f->bit_depth == 8 || f->bit_depth == 10);
 }
-
-__host__ __device__ void set_trial_level(SvtGpuLfParams &p, int plane, int dir, int lvl) { // try_filter_frame (:841-883)
-    if (plane == 0) {
-        if (dir != 1) p.filter_level[0] = lvl;
-        if (dir != 0) p.filter_level[1] = lvl;
-    } else if (plane == 1)
-        p.filter_level_u = lvl;
-    else
-        p.filter_level_v = lvl;
-}
-
-// search_filter_level (EbDeblockingFilter.c:886-991) as a resumable state machine: pending() names the levels the
-// next step needs (advancing over steps whose levels are already known), feed() records their SSE.  Independent
-// searches (U and V) then share launches.
-struct LevelSearch {
-    int     plane = 0, dir = 0, early_exit = 0, only4x4 = 0;
-    int     mid = 0, step = 0, direction = 0, conv = 0, best = 0;
-    int64_t best_err = 0, bias = 0, err[64];
-    int     phase = 0; // 0: the start level; 1: bisection steps; 2: done
-    int     lo = 0, hi = 0;
-    bool    try_lo = false, try_hi = false;
-    int     req[MAX_TRIALS], nreq = 0;
-
-    __host__ __device__ LevelSearch() {}
-    __host__ __device__ LevelSearch(const int last[4], int dlf_avg, int early_exit_, int only4x4_, int plane_, int dir_)
-        : plane(plane_), dir(dir_), early_exit(early_exit_), only4x4(only4x4_) {
-        const int start = plane == 0 ? (dlf_avg ? last[0] : last[dir]) : last[plane + 1];
-        mid  = clampi(start, 0, 63);
-        step = mid < 16 ? 4 : mid / 4;
-        best = mid;
-        for (int i = 0; i < 64; i++) err[i] = -1;
-        req[0] = mid, nreq = 1;
-    }
-    // the next bisection step's candidates (try lo / hi around mid), or done
-    __host__ __device__ void next_request() {
-        if (step <= 0) {
-            phase = 2, nreq = 0;
-            return;
-        }
-        hi   = mid + step < 63 ? mid + step : 63, lo = mid - step > 0 ? mid - step : 0;
-        bias = (best_err >> (15 - (mid / 8))) * step;
-        if (!only4x4) bias >>= 1;
-        try_lo = direction <= 0 && lo != mid, try_hi = direction >= 0 && hi != mid;
-        nreq   = 0;
-        if (try_lo) req[nreq++] = lo;
-        if (try_hi) req[nreq++] = hi;
-    }
-    __host__ __device__ void resolve() {
-        if (phase == 0) {
-            best_err = err[mid], best = mid, phase = 1;
-        } else {
-            if (try_lo && err[lo] < best_err + bias) {
-                if (err[lo] < best_err) best_err = err[lo];
-                best = lo;
-            }
-            if (try_hi && err[hi] < best_err - bias) {
-                best_err = err[hi];
-                best     = hi;
-            }
-            if (best == mid) {
-                conv++;
-                step      = conv == early_exit ? 0 : step / 2;
-                direction = 0;
-            } else {
-                direction = best < mid ? -1 : 1;
-                mid       = best;
-            }
-        }
-        next_request();
-    }
-    __host__ __device__ int pending(int *lv) {
-        while (phase != 2) {
-            int m = 0;
-            for (int k = 0; k < nreq; k++) {
-                bool dup = err[req[k]] >= 0;
-                for (int j = 0; j < m && !dup; j++) dup = lv[j] == req[k];
-                if (!dup) lv[m++] = req[k];
-            }
-            if (m) return m;
-            resolve();
-        }
-        return 0;
-    }
-    __host__ __device__ void feed(const int *lv, int m, const unsigned long long *sse) {
-        for (int k = 0; k < m; k++) err[lv[k]] = (int64_t)sse[k];
-    }
-};
-
-// The device-resident form of the searches (SVTGPU_DLF_DEVICE=1): the plane searches, the frame's parameters and the
-// next trial launch's plan live in HBM; after each trial launch one single-lane kernel feeds the SSEs to the searches
-// and writes the next plan, so the bisection advances with no host decision between trials.  The host enqueues a
-// chunk of (trial, step) pairs and reads the state back once per chunk; launches after the searches have finished
-// find an empty plan (every workgroup returns at once).
-struct DlfDevSearch {
-    LevelSearch    srch[MAX_JOBS];
-    int32_t        ns;
-    SvtGpuLfParams p;
-    DlfDevPlan     plan;
-    int32_t        rounds; // trial rounds taken (svtgpu_dlf_pick_async)
-};
-// what an asynchronous search leaves for the apply (device) and the caller (mapped host memory)
-struct DlfDevResult {
-    int32_t levels[4]; // filter_level[0], [1], _u, _v
-    int32_t rounds, seq, pad[2];
-    uint8_t lvl[3][2][128]; // the apply's level tables of the picked levels (zero for a plane that is not filtered)
-};
-
-// the next launch's levels per search (the bisection steps), then each (search, level)'s tables: that plane's only, as
-// run_searches builds them (try_filter_frame sets one plane's level; the other levels and the class deltas stay)
-__host__ __device__ void plan_levels(DlfDevSearch &S) {
-    S.plan.done = 1;
-    for (int i = 0; i < MAX_JOBS; i++) {
-        const int m = i < S.ns ? S.srch[i].pending(S.plan.lv[i]) : 0;
-        S.plan.ntrial[i] = m;
-        if (m) S.plan.done = 0;
-    }
-}
-// table entry e of [MAX_JOBS][MAX_TRIALS][2][128] (entries of levels the plan does not try are left as they are)
-__host__ __device__ inline void plan_table_entry(DlfDevSearch &S, int e) {
-    const int cls = e & 127, d = (e >> 7) & 1, k = (e >> 8) % MAX_TRIALS, i = (e >> 8) / MAX_TRIALS;
-    if (i >= S.ns || k >= S.plan.ntrial[i]) return;
-    const int plane = S.srch[i].plane, lvl = S.plan.lv[i][k];
-    int       l0 = S.p.filter_level[0], l1 = S.p.filter_level[1], lu = S.p.filter_level_u, lvv = S.p.filter_level_v;
-    if (plane == 0) { // set_trial_level
-        if (S.srch[i].dir != 1) l0 = lvl;
-        if (S.srch[i].dir != 0) l1 = lvl;
-    } else if (plane == 1)
-        lu = lvl;
-    else
-        lvv = lvl;
-    const bool on   = plane == 0 ? (l0 || l1) : plane == 1 ? lu != 0 : lvv != 0; // plane_active
-    const int  base = plane == 0 ? (d == 0 ? l0 : l1) : plane == 1 ? lu : lvv;
-    S.plan.lvl[i][k][d][cls] = on ? level_entry(S.p, plane, d, base, cls) : 0;
-}
-constexpr int PLAN_ENTRIES = MAX_JOBS * MAX_TRIALS * 2 * 128;
-void plan_next(DlfDevSearch &S) { // host
-    plan_levels(S);
-    for (int e = 0; e < PLAN_ENTRIES; e++) plan_table_entry(S, e);
+// what every filter and pick entry point asks: a state with edge records and two frames (or one, twice) of its size
+// and of one bit depth
+bool valid_call(const SvtGpuDlfState *s, const SvtGpuFrame *a, const SvtGpuFrame *b) {
+    return s && frame_matches(s, a) && frame_matches(s, b) && a->bit_depth == b->bit_depth && s->have_mi;
 }
 
 // one bisection decision per search from the last trial launch's sums (re-zeroed), then the next plan.  The state is
@@ -942,12 +759,7 @@ __device__ void dlf_step(DlfDevSearch *S, unsigned long long *sse, uint32_t *w, 
     __shared__ unsigned long long v[MAX_JOBS * MAX_TRIALS]; // the sums, one lane each (not a chain of atomics)
     if (tid < MAX_JOBS * MAX_TRIALS) v[tid] = atomic_sums ? atomicExch(&sse[tid], 0ull) : sse[tid];
     __syncthreads();
-    if (tid == 0) {
-        for (int i = 0; i < D.ns; i++)
-            if (D.plan.ntrial[i]) D.srch[i].feed(D.plan.lv[i], D.plan.ntrial[i], v + i * MAX_TRIALS);
-        plan_levels(D);
-        D.rounds++;
-    }
+    if (tid == 0) search_step(D, v);
     __syncthreads();
     for (int e = tid; e < PLAN_ENTRIES; e += nt) plan_table_entry(D, e); // the tables: one entry per lane and pass
     __syncthreads();
@@ -960,21 +772,14 @@ __global__ __launch_bounds__(64) void dlf_search_step_kernel(DlfDevSearch *S, un
     dlf_step(S, sse, w, false);
 }
 
-// svtgpu_dlf_pick_async, 1: the searches' start (LevelSearch's constructor: the start level) and the first plan,
-// from the caller's parameters -- no host staging
+// svtgpu_dlf_pick_async, 1: the searches' start and the first plan, from the caller's parameters -- no host staging
 __global__ __launch_bounds__(64) void dlf_search_init_kernel(DlfDevSearch *S, SvtGpuLfParams p, int ns, int dlf_avg,
                                                             int early_exit, int only4x4) {
     __shared__ __align__(16) uint32_t w[sizeof(DlfDevSearch) / 4];
     constexpr int NW = (int)(sizeof(DlfDevSearch) / 4);
     DlfDevSearch &D  = *(DlfDevSearch *)w;
     const int     tid = threadIdx.x;
-    if (tid == 0) {
-        const int last[4] = {p.filter_level[0], p.filter_level[1], p.filter_level_u, p.filter_level_v};
-        const int dirs[3] = {2, 0, 0};
-        for (int i = 0; i < MAX_JOBS; i++) D.srch[i] = LevelSearch(last, dlf_avg, early_exit, only4x4, i, dirs[i]);
-        D.ns = ns, D.p = p, D.rounds = 0;
-        plan_levels(D);
-    }
+    if (tid == 0) search_init(D, p, ns, dlf_avg, early_exit, only4x4);
     __syncthreads();
     for (int e = tid; e < PLAN_ENTRIES; e += 64) plan_table_entry(D, e);
     __syncthreads();
@@ -1044,23 +849,15 @@ __global__ __launch_bounds__(NTHR) void dlf_finish_kernel(const DlfTileArgs a0, 
         dlf_step(S, a.sse, (uint32_t *)L.t, true);
         __syncthreads();
     }
-    // the picked levels (svt_av1_pick_filter_level: luma both directions from the dir-2 search; chroma searched, or the
-    // start levels when dlf_avg_uv skips it) and their tables (build_level_tables / plane_active / luma_off)
+    // the picked levels and the apply's tables of them
     __shared__ int lv[4];
-    if (tid == 0) {
-        const DlfDevSearch &D = *S;
-        lv[0] = lv[1] = D.srch[0].best;
-        lv[2] = D.ns == 3 ? D.srch[1].best : D.p.filter_level_u;
-        lv[3] = D.ns == 3 ? D.srch[2].best : D.p.filter_level_v;
-    }
+    if (tid == 0) picked_levels(S->srch, S->ns, S->p, lv);
     __syncthreads();
     SvtGpuLfParams q = S->p;
-    q.filter_level[0] = lv[0], q.filter_level[1] = lv[1], q.filter_level_u = lv[2], q.filter_level_v = lv[3];
-    const bool luma_off = !plane_active(q, 0);
+    set_levels(q, lv[0], lv[1], lv[2], lv[3]);
     for (int e = tid; e < 3 * 2 * 128; e += NTHR) {
         const int pl = e >> 8, d = (e >> 7) & 1, cls = e & 127;
-        const int base = pl == 0 ? q.filter_level[d] : pl == 1 ? q.filter_level_u : q.filter_level_v;
-        res->lvl[pl][d][cls] = (!luma_off && plane_active(q, pl)) ? level_entry(q, pl, d, base, cls) : 0;
+        res->lvl[pl][d][cls] = apply_level_entry(q, pl, d, cls);
     }
     if (tid < 4) res->levels[tid] = lv[tid];
     if (tid == 0) {
@@ -1072,47 +869,29 @@ __global__ __launch_bounds__(NTHR) void dlf_finish_kernel(const DlfTileArgs a0, 
     }
 }
 
-// (trial, step) pairs per host read-back; 0: the host-driven search.  Default: the device search for a tile of a
-// picture spread over ranks (its trial launches are small, so the host round trips and the all-reduce waits between
-// them dominate: emulated 8-GPU rank 7.7-7.9 -> 8.1 Gpx/s), the host-driven one for a whole picture (its launches
-// sized per step beat the device plan's full-shape grid: 3053 vs 2949 Mpx/s).  SVTGPU_DLF_DEVICE=0|1|n overrides.
-int dlf_device_chunk(const SvtGpuDlfState *s) {
-    static const int k = [] {
-        const char *e = std::getenv("SVTGPU_DLF_DEVICE");
-        return e ? std::max(0, std::min(64, std::atoi(e) == 1 ? 6 : std::atoi(e))) : -1;
-    }();
-    return k >= 0 ? k : (svtgpu_comm_tiled(s->comm) ? 6 : 0);
+// the device-resident search's state and its pinned host copy, allocated at the first device search
+int ensure_device_search(SvtGpuDlfState *s) {
+    if (s->d_search) return SVTGPU_OK;
+    HIP_TRY(hipMalloc(&s->d_search, sizeof(DlfDevSearch)));
+    HIP_TRY(hipHostMalloc(&s->h_search, sizeof(DlfDevSearch), hipHostMallocDefault));
+    return SVTGPU_OK;
 }
 
-int run_searches_device_body(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *src,
-                             const SvtGpuLfParams &p, LevelSearch *const *srch, int ns, hipStream_t st, int chunk) {
-    if (!s->d_search) {
-        HIP_TRY(hipMalloc(&s->d_search, sizeof(DlfDevSearch)));
-        HIP_TRY(hipHostMalloc(&s->h_search, sizeof(DlfDevSearch), hipHostMallocDefault));
-    }
+// the device search in chunks of (trial, step) pairs, the state read back once per chunk
+int run_searches_device_body(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *src, DlfDevSearch &S,
+                             hipStream_t st, int chunk) {
+    if (int rc = ensure_device_search(s)) return rc;
     DlfDevSearch &H = *(DlfDevSearch *)s->h_search; // pinned: the caller's previous pick has read it back
     DlfDevSearch *D = (DlfDevSearch *)s->d_search;
-    for (int i = 0; i < ns; i++) H.srch[i] = *srch[i];
-    H.ns = ns;
-    H.p  = p;
+    H = S;
     plan_next(H);
     if (!H.plan.done) {
         HIP_TRY(hipMemcpyAsync(D, &H, sizeof H, hipMemcpyHostToDevice, st));
         svtgpu_count_xfer(0, sizeof H);
-        LevelTables L;
-        build_level_tables(p, L);
-        DlfTileArgs a = base_args(recon, L);
-        for (int i = 0; i < ns; i++) { // the grid covers MAX_TRIALS levels of every search; the plan says which run
-            const int    plane = srch[i]->plane;
-            DlfPlaneJob &J     = a.job[i];
-            J                  = plane_job(s, recon, plane, true);
-            J.src              = recon->plane[plane];
-            J.src_stride       = recon->stride[plane];
-            J.ref              = src->plane[plane];
-            J.ref_stride       = src->stride[plane];
-            J.ntrial           = MAX_TRIALS;
-        }
-        a.njob = ns;
+        DlfTileArgs a = base_args(recon, H.p);
+        // the grid covers MAX_TRIALS levels of every search; the plan says which run
+        for (int i = 0; i < H.ns; i++) a.job[i] = trial_job(s, recon, src, H.srch[i].plane, MAX_TRIALS);
+        a.njob = H.ns;
         a.sse  = s->d_sse;
         a.plan = &D->plan;
         for (int launches = 0;;) {
@@ -1135,60 +914,34 @@ int run_searches_device_body(SvtGpuDlfState *s, const SvtGpuFrame *recon, const 
             }
         }
     }
-    for (int i = 0; i < ns; i++) *srch[i] = H.srch[i];
+    S = H;
     return SVTGPU_OK;
 }
 
 // the device search; on any error exit the trial accumulators are zeroed again (the next pick assumes them zero)
-int run_searches_device(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *src, const SvtGpuLfParams &p,
-                        LevelSearch *const *srch, int ns, hipStream_t st, int chunk) {
-    const int rc = run_searches_device_body(s, recon, src, p, srch, ns, st, chunk);
+int run_searches_device(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *src, DlfDevSearch &S,
+                        hipStream_t st, int chunk) {
+    const int rc = run_searches_device_body(s, recon, src, S, st, chunk);
     if (rc) (void)hipMemsetAsync(s->d_sse, 0, sizeof(unsigned long long) * MAX_JOBS * MAX_TRIALS, st);
     return rc;
 }
 
 // run searches side by side: each launch evaluates the pending levels of every unfinished search (one plane job
 // each), the SSE of every (job, level) comes back through mapped pinned memory; recon is never modified
-int run_searches(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *src, const SvtGpuLfParams &p,
-                 LevelSearch *const *srch, int ns, hipStream_t st) {
+int run_searches(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *src, DlfDevSearch &S, hipStream_t st) {
     for (;;) {
-        DlfTileArgs a;
-        int         lv[MAX_JOBS][MAX_TRIALS], m[MAX_JOBS], who[MAX_JOBS];
-        bool        first = true;
-        for (int i = 0; i < ns; i++) {
-            const int mi = srch[i]->pending(lv[i]);
-            if (!mi) continue;
-            const int plane = srch[i]->plane;
-            LevelTables L;
-            if (first) {
-                build_level_tables(p, L);
-                a     = base_args(recon, L);
-                first = false;
-            }
+        plan_levels(S);
+        if (S.plan.done) return SVTGPU_OK;
+        DlfTileArgs a = base_args(recon, S.p);
+        int         who[MAX_JOBS];
+        for (int i = 0; i < S.ns; i++) {
+            const int m = S.plan.ntrial[i], plane = S.srch[i].plane;
+            if (!m) continue;
             DlfPlaneJob &J = a.job[a.njob];
-            J              = plane_job(s, recon, plane, true);
-            J.src          = recon->plane[plane];
-            J.src_stride   = recon->stride[plane];
-            J.ref          = src->plane[plane];
-            J.ref_stride   = src->stride[plane];
-            J.ntrial       = mi;
-            for (int k = 0; k < mi; k++) { // the trial's tables of this plane only (try_filter_frame's levels)
-                SvtGpuLfParams q = p;
-                set_trial_level(q, plane, srch[i]->dir, lv[i][k]);
-                const int  base[3][2] = {{q.filter_level[0], q.filter_level[1]},
-                                         {q.filter_level_u, q.filter_level_u},
-                                         {q.filter_level_v, q.filter_level_v}};
-                const bool on = plane_active(q, plane);
-                for (int dir = 0; dir < 2; dir++) {
-                    if (on) fill_level_table(q, plane, dir, base[plane][dir], J.lvl[k][dir]);
-                    else std::memset(J.lvl[k][dir], 0, 128);
-                }
-            }
-            m[a.njob]   = mi;
-            who[a.njob] = i;
-            a.njob++;
+            J              = trial_job(s, recon, src, plane, m);
+            for (int k = 0; k < m; k++) fill_trial_table(S.p, plane, S.srch[i].dir, S.plan.lv[i][k], J.lvl[k]);
+            who[a.njob++] = i;
         }
-        if (first) return SVTGPU_OK; // every search has finished
         a.sse    = s->d_sse;
         a.arrive = s->d_arrive;
         a.out    = s->h_sse_dev;
@@ -1198,20 +951,13 @@ int run_searches(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame 
         svtgpu_count_xfer(1, 8); // the sequence word
         unsigned long long sse[MAX_JOBS * MAX_TRIALS];
         std::memcpy(sse, s->h_sse, sizeof sse);
-        for (int j = 0; j < a.njob; j++) svtgpu_count_xfer(1, 8 * (size_t)m[j]); // the job's trial SSEs (mapped memory)
+        // the jobs' trial SSEs (mapped memory)
+        for (int j = 0; j < a.njob; j++) svtgpu_count_xfer(1, 8 * (size_t)a.job[j].ntrial);
         // a picture tiled over GPUs: every rank measured its tile; the frame's SSE is the sum over the ranks, and
         // every rank then takes the same bisection step
         if (int rc = svtgpu_comm_sum(s->comm, sse, MAX_JOBS * MAX_TRIALS, false, st, SVTGPU_XCH_DLF)) return rc;
-        for (int j = 0; j < a.njob; j++) srch[who[j]]->feed(lv[who[j]], m[j], sse + j * MAX_TRIALS);
+        for (int j = 0; j < a.njob; j++) S.srch[who[j]].feed(S.plan.lv[who[j]], a.job[j].ntrial, sse + j * MAX_TRIALS);
     }
-}
-
-bool valid_params(const SvtGpuLfParams *p) {
-    if (!p) return false;
-    const int lv[4] = {p->filter_level[0], p->filter_level[1], p->filter_level_u, p->filter_level_v};
-    for (int v : lv)
-        if (v < 0 || v > 63) return false;
-    return p->sharpness_level >= 0 && p->sharpness_level <= 7;
 }
 
 } // namespace
@@ -1288,12 +1034,18 @@ int edge_records(SvtGpuDlfState *s, hipStream_t st, unsigned long long *bad) {
     return SVTGPU_OK;
 }
 
-// a device-side check raised the flag: the grid handed over had records out of range (cleared when reported)
-bool take_bad_mi(SvtGpuDlfState *s) {
+// The verdict on a grid that came through svtgpu_dlf_set_mode_info_device, reported once, by the first call that has
+// the stream past its records kernel (wait: a bounded stream wait first, unless the caller has just waited): the
+// device-side checks raise the flag word for records out of range (cleared when reported)
+int collect_mi_verdict(SvtGpuDlfState *s, hipStream_t st, bool wait) {
+    if (!s->mi_on_device) return SVTGPU_OK;
+    s->mi_on_device = 0;
+    if (wait)
+        if (int rc = svtgpu_comm_wait(s->comm, st)) return rc;
     volatile unsigned long long *f = s->h_sse + MAX_JOBS * MAX_TRIALS + 1;
-    if (!*f) return false;
+    if (!*f) return SVTGPU_OK;
     *f = 0;
-    return true;
+    return SVTGPU_ERR_INVALID_ARG;
 }
 } // namespace
 
@@ -1371,21 +1123,13 @@ int dlf_frame_impl(SvtGpuDlfState *s, const SvtGpuFrame *in, SvtGpuFrame *out, c
     // through the tile kernel: a plane that is not filtered has all-zero tables, lists no edge and is copied)
     const bool dev = params == nullptr;
     if (dev) params = &s->dev_params;
-    if (s->mi_on_device && !dev) { // a device grid no pick has reported on (the FROM_Q levels): its verdict first
-        s->mi_on_device = 0;
-        if (int rc = svtgpu_comm_wait(s->comm, st)) return rc; // bounded when an exchange may sit before it
-        if (take_bad_mi(s)) return SVTGPU_ERR_INVALID_ARG;
-    }
-    LevelTables L;
-    build_level_tables(*params, L);
-    bool        luma_off = false;
-    DlfTileArgs a        = base_args(in, L);
-    size_t      sc_off   = 0; // bytes of scratch used by earlier planes
+    if (!dev) // a device grid no pick has reported on (the FROM_Q levels): its verdict first
+        if (int rc = collect_mi_verdict(s, st, true)) return rc;
+    DlfTileArgs a      = base_args(in, *params);
+    size_t      sc_off = 0; // bytes of scratch used by earlier planes
     for (int pl = ps; pl < pe; pl++) {
-        if (pl == 0 && !plane_active(*params, 0)) luma_off = true; // no plane is filtered (:575-577)
         const size_t bps = in->bytes_per_sample;
-        const bool   on  = dev || (!luma_off && plane_active(*params, pl));
-        if (!on) { // the output rectangle of the plane passes through
+        if (!dev && !plane_filtered(*params, pl, ps)) { // the output rectangle of the plane passes through
             const DlfPlaneJob R = plane_job(s, in, pl, false);
             if (in != out && R.ow > 0 && R.oh > 0) {
                 const size_t io = ((size_t)R.oy * in->stride[pl] + R.ox) * bps, oo = ((size_t)R.oy * out->stride[pl] + R.ox) * bps;
@@ -1413,29 +1157,32 @@ int dlf_frame_impl(SvtGpuDlfState *s, const SvtGpuFrame *in, SvtGpuFrame *out, c
         J.dst        = out->plane[pl];
         J.dst_stride = out->stride[pl];
         J.ntrial     = 1;
-        for (int dir = 0; dir < 2; dir++) std::memcpy(J.lvl[0][dir], L.lvl[pl][dir], 128);
+        if (dev) continue; // the tables the search left (below), not the job's own
+        fill_apply_table(*params, pl, ps, J.lvl[0]);
     }
     if (dev) a.dev_lvl = ((const DlfDevResult *)s->d_res)->lvl[0][0];
     if (a.njob) return launch_tile(a, (int)in->bytes_per_sample, false, st);
     return SVTGPU_OK;
 }
+
+// the filter entry points' conditions: valid_call, levels (NULL: an asynchronous pick's) and a plane range
+bool valid_filter_call(const SvtGpuDlfState *s, const SvtGpuFrame *in, const SvtGpuFrame *out,
+                       const SvtGpuLfParams *params, int32_t plane_start, int32_t plane_end) {
+    return valid_call(s, in, out) && (params ? valid_params(params) : s->dev_ready != 0) && plane_start >= 0 &&
+           plane_end <= 3 && plane_start <= plane_end;
+}
 } // namespace
 
 extern "C" int svtgpu_dlf_frame(SvtGpuDlfState *s, SvtGpuFrame *frame, const SvtGpuLfParams *params,
                                 int32_t plane_start, int32_t plane_end, void *stream) {
-    if (!s || !frame_matches(s, frame) || (params ? !valid_params(params) : !s->dev_ready) || plane_start < 0 || plane_end > 3 ||
-        plane_start > plane_end || !s->have_mi)
-        return SVTGPU_ERR_INVALID_ARG;
+    if (!valid_filter_call(s, frame, frame, params, plane_start, plane_end)) return SVTGPU_ERR_INVALID_ARG;
     return dlf_frame_impl(s, frame, frame, params, plane_start, plane_end, pick_stream(s->ctx, stream));
 }
 
 extern "C" int svtgpu_dlf_frame_to(SvtGpuDlfState *s, const SvtGpuFrame *in, SvtGpuFrame *out,
                                    const SvtGpuLfParams *params, int32_t plane_start, int32_t plane_end,
                                    void *stream) {
-    if (!s || !frame_matches(s, in) || !frame_matches(s, out) || in->bit_depth != out->bit_depth ||
-        (params ? !valid_params(params) : !s->dev_ready) || plane_start < 0 || plane_end > 3 || plane_start > plane_end ||
-        !s->have_mi)
-        return SVTGPU_ERR_INVALID_ARG;
+    if (!valid_filter_call(s, in, out, params, plane_start, plane_end)) return SVTGPU_ERR_INVALID_ARG;
     return dlf_frame_impl(s, in, out, params, plane_start, plane_end, pick_stream(s->ctx, stream));
 }
 
@@ -1443,139 +1190,134 @@ extern "C" int svtgpu_dlf_pick(SvtGpuDlfState *s, SvtGpuFrame *recon, const SvtG
                                SvtGpuLfParams *params, int32_t dlf_avg, int32_t dlf_avg_uv,
                                int32_t temporal_layer_index, int32_t early_exit_convergence,
                                int32_t tx_mode_only_4x4, void *stream) {
-    if (!s || !frame_matches(s, recon) || !frame_matches(s, source) || source->bit_depth != recon->bit_depth ||
-        !valid_params(params) || !s->have_mi)
-        return SVTGPU_ERR_INVALID_ARG;
+    if (!valid_call(s, recon, source) || !valid_params(params)) return SVTGPU_ERR_INVALID_ARG;
     // this pick's levels go to the caller only: an earlier svtgpu_dlf_pick_async's device levels are another frame's,
     // so the NULL-parameter filter and svtgpu_dlf_read_levels refuse until the next asynchronous pick
     s->dev_ready = 0, s->dev_pending = 0;
     hipStream_t    st = pick_stream(s->ctx, stream);
     SvtGpuLfParams p  = *params;
     p.sharpness_level = 0;
-    const int last[4] = {p.filter_level[0], p.filter_level[1], p.filter_level_u, p.filter_level_v};
-    int       rc;
     // The three searches are independent: a trial filters only its own plane with its own level (the luma levels
-    // gate only the luma plane, EbDeblockingFilter.c:571-577), so they share launches.  With dlf_avg_uv on a
-    // non-base layer the chroma levels stay (EbDeblockingFilter.c:1221-1229).
-    const bool  search_uv = !(dlf_avg_uv && temporal_layer_index > 0);
-    LevelSearch ys(last, dlf_avg, early_exit_convergence, tx_mode_only_4x4, 0, 2);
-    LevelSearch us(last, dlf_avg, early_exit_convergence, tx_mode_only_4x4, 1, 0);
-    LevelSearch vs(last, dlf_avg, early_exit_convergence, tx_mode_only_4x4, 2, 0);
-    LevelSearch *all[3] = {&ys, &us, &vs};
-    const int   chunk  = dlf_device_chunk(s);
+    // gate only the luma plane, EbDeblockingFilter.c:571-577), so they share launches.
+    DlfDevSearch S{};
+    search_init(S, p, searches_for(dlf_avg_uv, temporal_layer_index), dlf_avg, early_exit_convergence, tx_mode_only_4x4);
+    const int   chunk = dlf_knobs().chunk(svtgpu_comm_tiled(s->comm));
     hipStream_t hs;
+    int         rc;
     if ((rc = svtgpu_prio_enter(&s->prio, st, &hs))) return rc;
-    rc = chunk ? run_searches_device(s, recon, source, p, all, search_uv ? 3 : 1, hs, chunk)
-               : run_searches(s, recon, source, p, all, search_uv ? 3 : 1, hs);
+    rc = chunk ? run_searches_device(s, recon, source, S, hs, chunk) : run_searches(s, recon, source, S, hs);
     if (int rj = svtgpu_prio_leave(&s->prio, hs, st)) rc = rc ? rc : rj;
     if (rc) return rc;
-    if (s->mi_on_device) { // the grid was checked by the records kernel: its verdict, once the stream has passed it
-        s->mi_on_device = 0;
-        if (int rc = svtgpu_comm_wait(s->comm, st)) return rc;
-        if (take_bad_mi(s)) return SVTGPU_ERR_INVALID_ARG;
-    }
-    p.filter_level[0] = p.filter_level[1] = ys.best;
-    p.filter_level_u = search_uv ? us.best : last[2];
-    p.filter_level_v = search_uv ? vs.best : last[3];
-    *params          = p;
+    // a grid checked by the records kernel: its verdict, once the stream has passed it
+    if ((rc = collect_mi_verdict(s, st, true))) return rc;
+    int lv[4];
+    picked_levels(S.srch, S.ns, p, lv);
+    set_levels(p, lv[0], lv[1], lv[2], lv[3]);
+    *params = p;
     return SVTGPU_OK;
 }
+
+namespace {
+// svtgpu_dlf_pick_async's result: the apply's tables on the device, the caller's levels in mapped host memory
+int ensure_async_result(SvtGpuDlfState *s) {
+    if (s->d_res) return SVTGPU_OK;
+    HIP_TRY(hipMalloc(&s->d_res, sizeof(DlfDevResult)));
+    HIP_TRY(hipHostMalloc(&s->h_res, sizeof(DlfDevResult), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(s->h_res, 0, sizeof(DlfDevResult));
+    HIP_TRY(hipHostGetDevicePointer(&s->h_res_dev, s->h_res, 0));
+    return SVTGPU_OK;
+}
+
+// A picture tiled over GPUs (an all-reduce between a trial round and its step): the synchronous search (host
+// read-backs per chunk); its levels and their tables become the asynchronous result
+int async_tiled_fallback(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *source, SvtGpuLfParams p,
+                         int32_t dlf_avg, int32_t dlf_avg_uv, int32_t temporal_layer_index,
+                         int32_t early_exit_convergence, int32_t tx_mode_only_4x4, void *stream) {
+    if (int rc = svtgpu_dlf_pick(s, const_cast<SvtGpuFrame *>(recon), source, &p, dlf_avg, dlf_avg_uv,
+                                 temporal_layer_index, early_exit_convergence, tx_mode_only_4x4, stream))
+        return rc;
+    DlfDevResult r;
+    std::memset(&r, 0, sizeof r);
+    for (int pl = 0; pl < 3; pl++) fill_apply_table(p, pl, 0, r.lvl[pl]);
+    r.levels[0] = p.filter_level[0], r.levels[1] = p.filter_level[1], r.levels[2] = p.filter_level_u;
+    r.levels[3] = p.filter_level_v, r.seq = ++s->dev_seq;
+    std::memcpy(s->h_res, &r, sizeof r);
+    HIP_TRY(hipMemcpyAsync(s->d_res, s->h_res, sizeof r, hipMemcpyHostToDevice, pick_stream(s->ctx, stream)));
+    s->dev_params = p, s->dev_ready = 1, s->dev_pending = 1;
+    return SVTGPU_OK;
+}
+
+// The rounds to enqueue: SVTGPU_DLF_ROUNDS, else two more than the latest search that has completed took (read from
+// mapped memory without waiting -- whichever search that is: the caller's thread may run ahead of the device -- else
+// the last hint)
+int async_size_rounds(SvtGpuDlfState *s) {
+    const volatile DlfDevResult *hr = (const volatile DlfDevResult *)s->h_res;
+    if (hr->seq != s->dev_seen) s->dev_seen = hr->seq, s->dev_rounds = std::max(4, std::min(16, hr->rounds + 2));
+    return s->dev_rounds_last = dlf_knobs().rounds ? dlf_knobs().rounds : s->dev_rounds;
+}
+
+// the searches' start on the device and the first plan in plans[0]
+int async_init(SvtGpuDlfState *s, const SvtGpuLfParams &p, int ns, int32_t dlf_avg, int32_t early_exit_convergence,
+               int32_t tx_mode_only_4x4, hipStream_t st) {
+    if (int rc = ensure_device_search(s)) return rc;
+    if (!s->d_plans) HIP_TRY(hipMalloc(&s->d_plans, 2 * sizeof(DlfDevPlan)));
+    DlfDevSearch *D = (DlfDevSearch *)s->d_search;
+    hipLaunchKernelGGL(dlf_search_init_kernel, dim3(1), dim3(64), 0, st, D, p, ns, dlf_avg, early_exit_convergence,
+                       tx_mode_only_4x4);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->d_plans, &D->plan, sizeof(DlfDevPlan), hipMemcpyDeviceToDevice, st));
+    return SVTGPU_OK;
+}
+
+// `rounds` trial rounds of the device plan, each stepping itself: trial launch k reads plans[k & 1] and its step writes
+// the other; the grid covers MAX_TRIALS levels of every search
+int async_rounds(SvtGpuDlfState *s, DlfTileArgs &a, int bps, int rounds, hipStream_t st) {
+    DlfDevPlan *plans = (DlfDevPlan *)s->d_plans;
+    int         items = 0;
+    for (int i = 0; i < a.njob; i++) items += a.job[i].tiles * MAX_TRIALS;
+    const int grid = std::max(1, items);
+    for (int k = 0; k < rounds; k++) {
+        a.plan = &plans[k & 1], a.next_plan = &plans[(k + 1) & 1];
+        if (int rc = launch_for_samples(bps, dlf_trial_dev_kernel<uint8_t>, dlf_trial_dev_kernel<uint16_t>, grid, st, a,
+                                        (DlfDevSearch *)s->d_search, 1))
+            return rc;
+    }
+    return SVTGPU_OK;
+}
+
+// the finisher: one workgroup stepping the search's own copy of the plan, then the result
+int async_finish(SvtGpuDlfState *s, DlfTileArgs &a, int bps, hipStream_t st) {
+    DlfDevSearch *D = (DlfDevSearch *)s->d_search;
+    a.plan = &D->plan, a.next_plan = nullptr;
+    return launch_for_samples(bps, dlf_finish_kernel<uint8_t>, dlf_finish_kernel<uint16_t>, 1, st, a, D,
+                              (DlfDevResult *)s->d_res, (DlfDevResult *)s->h_res_dev, ++s->dev_seq);
+}
+} // namespace
 
 // The level search with no host wait: the start (dlf_search_init_kernel), a number of device trial rounds sized from the
 // previous search's count, each stepping itself (dlf_trial_dev_kernel), then dlf_finish_kernel, which completes a search
 // still open and writes the apply's tables and the caller's levels -- all in stream order.  A picture tiled over GPUs
-// (an all-reduce between a trial round and its step) runs the synchronous search here and keeps its levels.
+// runs the synchronous search here and keeps its levels.
 extern "C" int svtgpu_dlf_pick_async(SvtGpuDlfState *s, const SvtGpuFrame *recon, const SvtGpuFrame *source,
                                      const SvtGpuLfParams *params, int32_t dlf_avg, int32_t dlf_avg_uv,
                                      int32_t temporal_layer_index, int32_t early_exit_convergence,
                                      int32_t tx_mode_only_4x4, void *stream) {
-    if (!s || !frame_matches(s, recon) || !frame_matches(s, source) || source->bit_depth != recon->bit_depth ||
-        !valid_params(params) || !s->have_mi)
-        return SVTGPU_ERR_INVALID_ARG;
+    if (!valid_call(s, recon, source) || !valid_params(params)) return SVTGPU_ERR_INVALID_ARG;
     hipStream_t st = pick_stream(s->ctx, stream);
-    if (!s->d_res) {
-        HIP_TRY(hipMalloc(&s->d_res, sizeof(DlfDevResult)));
-        HIP_TRY(hipHostMalloc(&s->h_res, sizeof(DlfDevResult), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(s->h_res, 0, sizeof(DlfDevResult));
-        HIP_TRY(hipHostGetDevicePointer(&s->h_res_dev, s->h_res, 0));
-    }
-    if (svtgpu_comm_tiled(s->comm)) { // the tiled search (host read-backs per chunk); its levels become the result
-        SvtGpuLfParams p = *params;
-        if (int rc = svtgpu_dlf_pick(s, const_cast<SvtGpuFrame *>(recon), source, &p, dlf_avg, dlf_avg_uv, temporal_layer_index,
-                                     early_exit_convergence, tx_mode_only_4x4, stream))
-            return rc;
-        DlfDevResult r;
-        std::memset(&r, 0, sizeof r);
-        LevelTables L;
-        build_level_tables(p, L);
-        const bool luma_off = !plane_active(p, 0);
-        for (int pl = 0; pl < 3; pl++)
-            if (!luma_off && plane_active(p, pl)) std::memcpy(r.lvl[pl], L.lvl[pl], sizeof r.lvl[pl]);
-        r.levels[0] = p.filter_level[0], r.levels[1] = p.filter_level[1], r.levels[2] = p.filter_level_u;
-        r.levels[3] = p.filter_level_v, r.seq = ++s->dev_seq;
-        std::memcpy(s->h_res, &r, sizeof r);
-        HIP_TRY(hipMemcpyAsync(s->d_res, s->h_res, sizeof r, hipMemcpyHostToDevice, st));
-        s->dev_params = p, s->dev_ready = 1, s->dev_pending = 1;
-        return SVTGPU_OK;
-    }
-    if (!s->d_search) {
-        HIP_TRY(hipMalloc(&s->d_search, sizeof(DlfDevSearch)));
-        HIP_TRY(hipHostMalloc(&s->h_search, sizeof(DlfDevSearch), hipHostMallocDefault));
-    }
-    if (!s->d_plans) HIP_TRY(hipMalloc(&s->d_plans, 2 * sizeof(DlfDevPlan)));
-    // the rounds to enqueue: one more than the previous search took (read from mapped memory without waiting: the
-    // previous result when it is already there, else the last hint); SVTGPU_DLF_ROUNDS=k fixes it (tests: 1 makes the
-    // finish kernel complete the search)
-    static const int fixed = [] {
-        const char *e = std::getenv("SVTGPU_DLF_ROUNDS");
-        return e ? std::max(1, std::min(64, std::atoi(e))) : 0;
-    }();
-    // the latest search that has completed (whichever: the caller's thread may run ahead of the device) sizes the next
-    // one's rounds with a margin of two
-    const volatile DlfDevResult *hr = (const volatile DlfDevResult *)s->h_res;
-    if (hr->seq != s->dev_seen) s->dev_seen = hr->seq, s->dev_rounds = std::max(4, std::min(16, hr->rounds + 2));
-    const int rounds = fixed ? fixed : s->dev_rounds;
-    s->dev_rounds_last = rounds;
+    if (int rc = ensure_async_result(s)) return rc;
+    if (svtgpu_comm_tiled(s->comm))
+        return async_tiled_fallback(s, recon, source, *params, dlf_avg, dlf_avg_uv, temporal_layer_index,
+                                    early_exit_convergence, tx_mode_only_4x4, stream);
     SvtGpuLfParams p  = *params;
     p.sharpness_level = 0;
-    const int ns      = (dlf_avg_uv && temporal_layer_index > 0) ? 1 : 3;
-    DlfDevSearch *D   = (DlfDevSearch *)s->d_search;
-    hipLaunchKernelGGL(dlf_search_init_kernel, dim3(1), dim3(64), 0, st, D, p, ns, dlf_avg, early_exit_convergence,
-                       tx_mode_only_4x4);
-    HIP_TRY(hipGetLastError());
-    DlfDevPlan *plans = (DlfDevPlan *)s->d_plans; // trial launch k reads plans[k & 1] and its step writes the other
-    HIP_TRY(hipMemcpyAsync(&plans[0], &D->plan, sizeof(DlfDevPlan), hipMemcpyDeviceToDevice, st));
-    LevelTables L;
-    build_level_tables(p, L); // the thresholds (sharpness 0); the levels come from the plan
-    DlfTileArgs a = base_args(recon, L);
-    int         max_items = 0;
-    for (int i = 0; i < ns; i++) {
-        DlfPlaneJob &J = a.job[i];
-        J              = plane_job(s, recon, i, true);
-        J.src = recon->plane[i], J.src_stride = recon->stride[i];
-        J.ref = source->plane[i], J.ref_stride = source->stride[i];
-        J.ntrial = MAX_TRIALS;
-        max_items += J.tiles * MAX_TRIALS;
-    }
-    a.njob = ns, a.sse = s->d_sse, a.arrive = s->d_arrive, a.plan = &D->plan, a.dyn = 1;
-    const int grid = std::max(1, max_items);
-    for (int k = 0; k < rounds; k++) {
-        a.plan = &plans[k & 1], a.next_plan = &plans[(k + 1) & 1];
-        if (recon->bytes_per_sample == 2)
-            hipLaunchKernelGGL(dlf_trial_dev_kernel<uint16_t>, dim3(grid), dim3(NTHR), 0, st, a, D, 1);
-        else
-            hipLaunchKernelGGL(dlf_trial_dev_kernel<uint8_t>, dim3(grid), dim3(NTHR), 0, st, a, D, 1);
-        HIP_TRY(hipGetLastError());
-    }
-    a.plan = &D->plan, a.next_plan = nullptr; // the finisher: one workgroup stepping the search's own copy
-    const int seq = ++s->dev_seq;
-    if (recon->bytes_per_sample == 2)
-        hipLaunchKernelGGL(dlf_finish_kernel<uint16_t>, dim3(1), dim3(NTHR), 0, st, a, D, (DlfDevResult *)s->d_res,
-                           (DlfDevResult *)s->h_res_dev, seq);
-    else
-        hipLaunchKernelGGL(dlf_finish_kernel<uint8_t>, dim3(1), dim3(NTHR), 0, st, a, D, (DlfDevResult *)s->d_res,
-                           (DlfDevResult *)s->h_res_dev, seq);
-    HIP_TRY(hipGetLastError());
+    const int ns = searches_for(dlf_avg_uv, temporal_layer_index), bps = recon->bytes_per_sample;
+    const int rounds = async_size_rounds(s);
+    if (int rc = async_init(s, p, ns, dlf_avg, early_exit_convergence, tx_mode_only_4x4, st)) return rc;
+    DlfTileArgs a = base_args(recon, p); // the thresholds (sharpness 0); the levels come from the plan
+    for (int i = 0; i < ns; i++) a.job[i] = trial_job(s, recon, source, i, MAX_TRIALS);
+    a.njob = ns, a.sse = s->d_sse, a.arrive = s->d_arrive, a.dyn = 1;
+    if (int rc = async_rounds(s, a, bps, rounds, st)) return rc;
+    if (int rc = async_finish(s, a, bps, st)) return rc;
     s->dev_params = p, s->dev_ready = 1, s->dev_pending = 1;
     return SVTGPU_OK;
 }
@@ -1590,15 +1332,12 @@ extern "C" int svtgpu_dlf_read_levels(SvtGpuDlfState *s, SvtGpuLfParams *params_
                                       "stream wait", __FILE__, __LINE__);
             return SVTGPU_ERR_HIP;
         }
-        if (s->mi_on_device) { // the device grid's verdict (its records kernel ran before the search)
-            s->mi_on_device = 0;
-            if (take_bad_mi(s)) return SVTGPU_ERR_INVALID_ARG;
-        }
+        // the device grid's verdict (its records kernel ran before the search)
+        if (int rc = collect_mi_verdict(s, nullptr, false)) return rc;
     }
     const volatile DlfDevResult *r = (const volatile DlfDevResult *)s->h_res;
     SvtGpuLfParams               p = s->dev_params;
-    p.filter_level[0] = r->levels[0], p.filter_level[1] = r->levels[1];
-    p.filter_level_u = r->levels[2], p.filter_level_v = r->levels[3];
+    set_levels(p, r->levels[0], r->levels[1], r->levels[2], r->levels[3]);
     *params_out = p;
     return SVTGPU_OK;
 }

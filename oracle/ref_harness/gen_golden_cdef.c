@@ -234,6 +234,70 @@ static void gen_search_one_dual(const char *dir) {
     golden_close(&g);
 }
 
+/* ---- search_one_dual on tables built to tie (tests/cdef_pick_cases.py's const, mod, lane and two rows): the first
+ * minimum in (j, k) order decides every case.  A file of its own; cdef_search_one_dual.bin stays as it is. ---- */
+static void tie_rows(int family, uint64_t arg, int r, uint64_t *m0, uint64_t *m1) {
+    for (int j = 0; j < 64; j++) {
+        switch (family) {
+        case 0: m0[j] = m1[j] = arg; break;                                                         /* const */
+        case 1: m0[j] = 1000u * ((j + 3) % 4) + 500, m1[j] = 700u * ((j + 5) % 8) + 100; break;     /* mod */
+        case 2:                                                                                      /* lane */
+            m0[j] = 65536u * (j != 5 && j != 8) + 9;
+            m1[j] = 65536u * (j != 3 && j != 8) + 9;
+            break;
+        default:                                                                                     /* two */
+            m0[j] = ((uint64_t)((j + 1 + r) % 4) << 20) + 64;
+            m1[j] = ((uint64_t)((j + (r ? 7 : 2)) % 8) << 20) + 64;
+        }
+    }
+}
+
+static void gen_search_one_dual_ties(const char *dir) {
+    char path[512];
+    snprintf(path, sizeof path, "%s/cdef_search_one_dual_ties.bin", dir);
+    GoldenFile g = golden_open(path);
+    enum { N = 15, SB = 8 };
+    /* family, sb_count, nb, start, end */
+    static const int cases[N][5] = {{0, 8, 0, 0, 64}, {0, 5, 3, 0, 64}, {0, 8, 7, 3, 48}, {0, 1, 1, 0, 4},
+                                    {1, 8, 0, 0, 64}, {1, 5, 2, 3, 64}, {1, 8, 5, 0, 48}, {1, 2, 4, 3, 48},
+                                    {2, 8, 0, 0, 64}, {2, 5, 1, 3, 64}, {2, 8, 6, 0, 48},
+                                    {3, 8, 0, 0, 64}, {3, 8, 1, 0, 64}, {3, 2, 2, 3, 48}, {3, 8, 7, 0, 4}};
+    static uint64_t mse[N][2][SB][64], args[N];
+    static int32_t  lev[N][2][16], lev_out[N][2][16], prm[N][3], fam[N], sbs[N];
+    static uint64_t res[N];
+    for (int n = 0; n < N; n++) {
+        const int family = cases[n][0], sb = cases[n][1], nb = cases[n][2], start = cases[n][3], end = cases[n][4];
+        args[n] = family ? 0 : n == 1 ? (uint64_t)1 << 31 : n == 2 ? ((uint64_t)1 << 31) - 1 : 1000;
+        for (int s = 0; s < sb; s++) tie_rows(family, args[n], family == 3 ? s % 2 : 0, mse[n][0][s], mse[n][1][s]);
+        for (int i = 0; i < 16; i++) { /* the strengths selected so far: any searched index */
+            lev[n][0][i] = (7 * i + n) % end;
+            lev[n][1][i] = (5 * i + 2 * n + 1) % end;
+        }
+        uint64_t *rows0[SB], *rows1[SB];
+        for (int s = 0; s < SB; s++) {
+            rows0[s] = mse[n][0][s];
+            rows1[s] = mse[n][1][s];
+        }
+        uint64_t **m[2] = {rows0, rows1};
+        memcpy(lev_out[n], lev[n], sizeof lev[n]);
+        res[n] = svt_search_one_dual_c(lev_out[n][0], lev_out[n][1], nb, m, sb, start, end);
+        prm[n][0] = nb;
+        prm[n][1] = start;
+        prm[n][2] = end;
+        fam[n]    = family;
+        sbs[n]    = sb;
+    }
+    golden_put(&g, "mse", 'Q', 4, (uint32_t[]){N, 2, SB, 64}, mse);
+    golden_put(&g, "lev_in", 'i', 3, (uint32_t[]){N, 2, 16}, lev);
+    golden_put(&g, "lev_out", 'i', 3, (uint32_t[]){N, 2, 16}, lev_out);
+    golden_put2(&g, "params", 'i', N, 3, prm);
+    golden_put1(&g, "family", 'i', N, fam);
+    golden_put1(&g, "arg", 'Q', N, args);
+    golden_put1(&g, "sb", 'i', N, sbs);
+    golden_put1(&g, "best", 'Q', N, res);
+    golden_close(&g);
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <out_dir>\n", argv[0]);
@@ -244,6 +308,7 @@ int main(int argc, char **argv) {
     gen_filter_block(argv[1]);
     gen_cdef_dist(argv[1]);
     gen_search_one_dual(argv[1]);
+    gen_search_one_dual_ties(argv[1]);
     printf("cdef golden vectors written to %s\n", argv[1]);
     return 0;
 }

@@ -57,7 +57,7 @@ def run_cdef_dist(fn16, fn8, g, n):
 def run_search_one_dual(fn, g, n):
     mse = np.ascontiguousarray(g["mse"][n])  # [2][SB][64]
     nb, start, end = [int(x) for x in g["params"][n]]
-    sb = mse.shape[1]
+    sb = int(g["sb"][n]) if "sb" in g else mse.shape[1]  # the tie golden's cases use the first sb rows
     U64P = ctypes.POINTER(ctypes.c_uint64)
     rows = [(U64P * sb)(*[ctypes.cast(mse[p, i].ctypes.data, U64P) for i in range(sb)]) for p in range(2)]
     arr = (ctypes.POINTER(U64P) * 2)(*[ctypes.cast(r, ctypes.POINTER(U64P)) for r in rows])

@@ -373,3 +373,28 @@ def dlf_case(w, h, bd, rname, sname):
     out = oracle.dlf_frame(rec, bd, mi, picked)
     _freeze(mi, *rec, *src, *out)
     return rec, src, mi, picked, out
+
+
+# --------------------------------------------------------------------------------------------- 8. CDEF pick
+# recon against source.  A flat, black, white or checkerboard recon is left unchanged by every strength (the
+# checkerboard's full-swing steps exceed every damping limit), so every searched strength of a filter block has the
+# same MSE and every call of the pick ties.
+CDEF_PAIRS = (("flat", "noise"), ("zero", "noise"), ("max", "noise"), ("checker", "noise"), ("flat", "flat"))
+CDEF_TIED = ("flat", "zero", "max", "checker")
+CDEF_LEVELS = (1, 2, 12)  # 64 strengths; 48 with the second pass's chroma at default_mse_uv * 64; 4 with the bias 62
+CDEF_CASES = [(w, h, bd, lv, r, s) for (w, h) in ((64, 64), (136, 72)) for bd in (8, 10) for lv in CDEF_LEVELS
+              for r, s in CDEF_PAIRS]
+CDEF_Q, CDEF_LAMBDA = 128, 60000
+
+
+@functools.lru_cache(maxsize=None)
+def cdef_case(w, h, bd, level, rname, sname):
+    """(rec, src, (mse, skip, dir, var), (parameter tuple, per-FB strengths), filtered frame) from the oracle's
+    cdef_search_frame -> cdef_pick -> cdef_apply_frame."""
+    rec, src = planes(rname, w, h, bd), planes(sname, w, h, bd)
+    ctrls = oracle.controls(level)
+    mse, skip, d, v = oracle.cdef_search_frame(rec, src, bd, ctrls, CDEF_Q)
+    prm, fbs = oracle.cdef_pick(w, h, mse, skip, ctrls, CDEF_Q, CDEF_LAMBDA)
+    out = oracle.cdef_apply_frame(rec, bd, None, d, v, prm, fbs)
+    _freeze(*rec, *src, mse, skip, d, v, fbs, *out)
+    return rec, src, (mse, skip, d, v), (prm.as_tuple(), fbs), out

@@ -62,6 +62,17 @@ def test_search_one_dual_shim_golden(ctx):
         assert l0 == list(g["lev_out"][n][0]) and l1 == list(g["lev_out"][n][1]), n
 
 
+def test_search_one_dual_ties_shim_golden(ctx):
+    """The reference's first minimum in (j, k) order where many strength pairs share it (const, mod, lane and two
+    rows of cdef_pick_cases.py, 1 to 8 blocks, start 0 and 3, end 64, 48 and 4)."""
+    L = svtgpu.lib()
+    g = cc.load("cdef_search_one_dual_ties.bin")
+    for n in range(len(g["best"])):
+        best, l0, l1, _ = cc.run_search_one_dual(L.svtgpu_search_one_dual, g, n)
+        assert best == int(g["best"][n]), n
+        assert l0 == list(g["lev_out"][n][0]) and l1 == list(g["lev_out"][n][1]), n
+
+
 # ------------------------------------------------------------------ frame level vs oracle
 FRAME_CASES = [
     # (width, height, bit_depth, cdef_level, p_skip, base_q_idx)

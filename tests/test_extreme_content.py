@@ -202,3 +202,32 @@ def test_dlf_oracle_runs(w, h, bd, rname, sname):
         assert all(np.array_equal(a, b) for a, b in zip(out, rec))
     if rname == "checker":  # full-swing steps at every edge exceed every filter's limit: nothing may move either
         assert all(int(a.max()) <= (1 << bd) - 1 for a in out)
+
+
+# --------------------------------------------------------------------------------------------- 8. CDEF pick
+@pytest.mark.parametrize("w,h,bd,level,rname,sname", ec.CDEF_CASES)
+def test_cdef_pick_oracle_on_tied_content(w, h, bd, level, rname, sname):
+    rec, src, (mse, skip, d, v), (prm, fbs), out = ec.cdef_case(w, h, bd, level, rname, sname)
+    c = oracle.controls(level)
+    nf, end = c.first_pass_fs_num, c.first_pass_fs_num + c.default_second_pass_fs_num
+    uv = np.array([(c.default_first_pass_fs_uv[g] if g < nf else c.default_second_pass_fs_uv[g - nf]) != -1
+                   for g in range(end)])
+    live = skip == 0
+    assert live.all()  # no block mask: every filter block is searched
+    if rname in ec.CDEF_TIED:
+        # no strength moves a sample of a constant plane: equal MSE for every searched strength of a live block (the
+        # chroma strengths a level leaves unsearched carry the constant default_mse_uv * 64)
+        assert (mse[0][live][:, :end] == mse[0][live][:, :1]).all()
+        assert (mse[1][live][:, :end][:, uv] == mse[1][live][:, :1]).all()
+        assert (mse[1][live][:, :end][:, ~uv] == 1040400 * 64).all()
+        assert (sname == "flat") == (not mse[0].any())
+        # every pair ties in the first call (or, under the bias, strength 0 wins): one zero strength, nothing filtered
+        assert prm[1:] == (0, (0,), (0,)) and not fbs.any()
+        assert all(np.array_equal(a, b) for a, b in zip(out, rec))
+    if level >= 2:
+        assert not uv.all() and uv[:nf].all()
+    # the restated pick agrees on these tables too
+    import cdef_pick_cases as pc
+    rprm, rfbs = pc.finish_cdef_search(mse, skip, c, ec.CDEF_Q, ec.CDEF_LAMBDA)
+    assert rprm == prm
+    np.testing.assert_array_equal(rfbs, fbs)

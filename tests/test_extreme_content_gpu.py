@@ -19,7 +19,10 @@ One-line kernel changes these cases catch and smooth content does not (reasoned 
      minima at row 1 (wave 1) tied with row 4 (wave 0); noise never ties.
   6. ccso_bins_kernel: NQ_SHIFT lowered to 32 -- 4352 samples x 1023^2 in one bin (136x72, 10 bit, max against zero)
      carry into the count; errors of a few levels never do.
-  7. DLF level search: a trial level accepted on an equal cost -- only flat content makes every level cost the same."""
+  7. DLF level search: a trial level accepted on an equal cost -- only flat content makes every level cost the same.
+  8. CDEF pick: an argmin that keeps a later minimum, or an RD choice with "<=" -- a flat, black, white or checkerboard recon gives
+     every searched strength of every filter block the same MSE, so every call of the pick ties and the frame must
+     come back with the single strength 0 and unfiltered (test_cdef_pick_ties_gpu.py has the table cases)."""
 import ctypes
 
 import numpy as np
@@ -231,6 +234,30 @@ def test_dlf_pick_and_filter_vs_oracle(ctx, w, h, bd, rname, sname):
     for p in range(3):  # the search leaves the recon unfiltered
         np.testing.assert_array_equal(back[p], rec[p])
     st.filter_to(R, O, got)
+    out = O.download()
+    for p in range(3):
+        np.testing.assert_array_equal(out[p], want_out[p], err_msg="plane %d" % p)
+    st.close()
+
+
+# --------------------------------------------------------------------------------------------- 8. CDEF pick
+@pytest.mark.parametrize("w,h,bd,level,rname,sname", ec.CDEF_CASES)
+def test_cdef_search_pick_apply_vs_oracle(ctx, w, h, bd, level, rname, sname):
+    """search -> pick -> apply where every strength of a filter block has the same MSE (flat, black and white recon;
+    from level 2 on also the unsearched chroma strengths' constant), one and three filter blocks with partial
+    right / bottom blocks: the tables, the frame parameters, the per-FB strengths and every output plane."""
+    rec, src, (omse, oskip, od, ov), (oprm, ofbs), want_out = ec.cdef_case(w, h, bd, level, rname, sname)
+    R, S, O = _frame(ctx, rec, bd), _frame(ctx, src, bd), svtgpu.Frame(ctx, w, h, bd)
+    ctrls = svtgpu.cdef_controls(level)
+    st = svtgpu.CdefState(ctx, w, h)
+    st.search(R, S, ctrls, ec.CDEF_Q)
+    mse, skip, d, v = st.read()
+    np.testing.assert_array_equal(skip, oskip)
+    np.testing.assert_array_equal(mse, omse)
+    prm, fbs = st.pick(ctrls, ec.CDEF_Q, ec.CDEF_LAMBDA)
+    assert prm.as_tuple() == oprm
+    np.testing.assert_array_equal(fbs, ofbs)
+    st.apply(R, O, prm)
     out = O.download()
     for p in range(3):
         np.testing.assert_array_equal(out[p], want_out[p], err_msg="plane %d" % p)

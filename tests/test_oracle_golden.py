@@ -46,6 +46,17 @@ def test_search_one_dual_golden(L):
         assert l0 == list(g["lev_out"][n][0]) and l1 == list(g["lev_out"][n][1]), n
 
 
+def test_search_one_dual_ties_golden(L):
+    """Tables on which many strength pairs share the minimum (const, mod, lane and two rows of cdef_pick_cases.py):
+    the oracle returns the reference's first minimum in (j, k) order."""
+    g = cc.load("cdef_search_one_dual_ties.bin")
+    assert len(g["best"]) >= 12
+    for n in range(len(g["best"])):
+        best, l0, l1, _ = cc.run_search_one_dual(L.oracle_search_one_dual, g, n)
+        assert best == int(g["best"][n]), n
+        assert l0 == list(g["lev_out"][n][0]) and l1 == list(g["lev_out"][n][1]), n
+
+
 def test_controls_level1_match_encmodeconfig():
     c = oracle.controls(1)  # EncModeConfig.c:866-904
     assert c.first_pass_fs_num == 16 and c.default_second_pass_fs_num == 48

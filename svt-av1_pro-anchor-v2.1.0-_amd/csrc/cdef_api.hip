@@ -121,28 +121,27 @@ extern "C" int svtgpu_cdef_state_create(SvtGpuContext *ctx, int32_t width, int32
     s->geo       = frame_geo(width, height);
     s->nfb       = s->geo.nvfb * s->geo.nhfb;
     s->mask_all  = 1;
-    s->pick_settle = 24; // the first pick checks after step 24 (then after the previous pick's settling step)
-    s->pick_parts = 64;
     const size_t nfb = s->nfb;
+    const PickLayout L(nfb); // the pick's buffers
     bool ok = hipMalloc(&s->d_mask, (size_t)s->geo.b8_rows * s->geo.b8_cols) == hipSuccess &&
               hipMalloc(&s->d_mse, nfb * 2 * 64 * 8) == hipSuccess && hipMalloc(&s->d_skip, (nfb + 7) & ~(size_t)7) == hipSuccess &&
               hipMalloc(&s->d_dir, nfb * 64) == hipSuccess && hipMalloc(&s->d_var, nfb * 64 * 4) == hipSuccess &&
               hipMalloc(&s->d_fb_strength, nfb) == hipSuccess &&
-              hipMalloc(&s->d_pick_part, (nfb * 128 + (size_t)3 * 4 * 4096 + 41 * 4 + (size_t)nfb * 64) * 8) == hipSuccess &&
-              hipMalloc(&s->d_pick_out, 8 * 8) == hipSuccess && hipMalloc(&s->d_pick_lev, (size_t)(41 * 4 * 32 + 4 * 32 + 64) * 4) == hipSuccess &&
-              hipMalloc(&s->d_fb_list, (2 * nfb + 1) * 4) == hipSuccess &&
-              hipMalloc(&s->d_pick_xch, SVTGPU_PICK_XCH_BYTES) == hipSuccess &&
-              hipMalloc(&s->d_apick, 64) == hipSuccess &&
-              hipHostMalloc((void **)&s->h_pick, 512 + nfb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
+              hipMalloc(&s->d_pick_part, L.part_words * 8) == hipSuccess &&
+              hipMalloc(&s->d_pick_out, L.out_words * 8) == hipSuccess && hipMalloc(&s->d_pick_lev, L.lev_words * 4) == hipSuccess &&
+              hipMalloc(&s->d_fb_list, L.list_words * 4) == hipSuccess &&
+              hipMalloc(&s->d_pick_xch, L.xch_bytes) == hipSuccess &&
+              hipMalloc(&s->d_apick, L.apick_bytes) == hipSuccess &&
+              hipHostMalloc((void **)&s->h_pick, L.rec_bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
               hipHostGetDevicePointer((void **)&s->h_pick_dev, s->h_pick, 0) == hipSuccess;
     if (!ok) {
         svtgpu_cdef_state_destroy(s);
         return SVTGPU_ERR_OOM;
     }
     HIP_TRY(hipMemset(s->d_fb_strength, 0, nfb));
-    HIP_TRY(hipMemset(s->d_apick, 0, 64));
-    std::memset(s->h_pick, 0, 512 + nfb); // no record carries a sequence number yet
-    HIP_TRY(hipMemset(s->d_pick_xch, 0, SVTGPU_PICK_XCH_BYTES)); // no word carries a valid tag
+    HIP_TRY(hipMemset(s->d_apick, 0, L.apick_bytes));
+    std::memset(s->h_pick, 0, L.rec_bytes); // no record carries a sequence number yet
+    HIP_TRY(hipMemset(s->d_pick_xch, 0, L.xch_bytes)); // no word carries a valid tag
     HIP_TRY(hipMemset(s->d_skip, 0, (nfb + 7) & ~(size_t)7)); // the padding stays 0 (the tables' word sums)
     HIP_TRY(hipMemset(s->d_skip, 1, nfb));
     // the memsets above run on the null stream: done before any call on the caller's (non-blocking) streams, whose

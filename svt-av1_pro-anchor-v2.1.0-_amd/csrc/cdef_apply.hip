@@ -288,7 +288,7 @@ __global__ void cdef_set_params_kernel(SvtGpuCdefParams *d, const SvtGpuCdefPara
     if (threadIdx.x == 0) *d = p;
 }
 int svtgpu_launch_cdef_set_params(SvtGpuCdefFrameState *s, const SvtGpuCdefParams *p, hipStream_t st) {
-    hipLaunchKernelGGL(cdef_set_params_kernel, dim3(1), dim3(64), 0, st, (SvtGpuCdefParams *)((uint8_t *)s->d_apick + 16), *p);
+    hipLaunchKernelGGL(cdef_set_params_kernel, dim3(1), dim3(64), 0, st, (SvtGpuCdefParams *)((uint8_t *)s->d_apick + PickLayout::apick_params), *p);
     HIP_TRY(hipGetLastError());
     return SVTGPU_OK;
 }
@@ -319,7 +319,7 @@ int svtgpu_launch_cdef_apply(SvtGpuCdefFrameState *s, const SvtGpuFrame *recon, 
     A.fb_strength = s->d_fb_strength;
     if (p) A.prm = *p;
     else std::memset(&A.prm, 0, sizeof A.prm);
-    A.dprm        = p ? nullptr : (const SvtGpuCdefParams *)((const uint8_t *)s->d_apick + 16);
+    A.dprm        = p ? nullptr : (const SvtGpuCdefParams *)((const uint8_t *)s->d_apick + PickLayout::apick_params);
     const dim3 grid((r1 - r0) * A.fbw);
     A.wgclk = svtgpu_wgclk_begin((int)grid.x);
     if (recon->bit_depth > 8)

@@ -10,6 +10,8 @@
 // for every FB; workgroups past the non-skipped count read on the device find no work).  The RD choice over
 // nb (:853-872) and the per-FB assignment run on the device too and write the result straight into mapped
 // pinned memory: one host synchronisation per pick.  The filter_map remap (:911-919) stays on the host.
+// The integer rules -- the schedule, the buffer layouts, the switches, the settle policy and index arithmetic, the RD
+// choice and the parameter conversion -- are in cdef_pick_plan.h (no HIP in it: tests/cdef_pick_plan_check.cpp).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -17,13 +19,8 @@
 
 #include "svtgpu_internal.h"
 
-#define NT 256
-#define MAX_CHAINS 4
-#define NSTEPS 40            // longest chain: nb = 8 → 8 + 32 calls (EbEncCdef.c:714-726)
-#define PICK_CHUNK 48        // max FBs per workgroup (a multiple of 4; their low words staged in LDS: <= 25.7 KB)
-// LDS row of a staged FB (dwords): 128 entries + 4, so the per-FB best (a lane per FB reading its row) spreads over 8
-// banks instead of one, and rows stay 16-B aligned for the accumulation's quad reads
-#define MROW 132
+// the kernels' short names of the plan's constants
+constexpr int NT = PICK_NT, MAX_CHAINS = PICK_MAX_CHAINS, NSTEPS = PICK_NSTEPS, MROW = PICK_MROW;
 
 struct StepChain {
     int32_t chain;       // 0..3 (nb = 1 << chain)
@@ -304,11 +301,7 @@ __global__ void __launch_bounds__(NT) sod_step_kernel(const StepArgs A) {
 // LDS and 256 threads (several fit per CU, and a pick launched beside another finds room); a poll gives up after
 // a bounded wait and sets a status bit, so a grid that cannot drain still ends.  Partial sums fit 56 bits:
 // an entry is < 2^41 (a 64x64 block's SSE at 12 bits is < 2^37), a chunk sums <= PS_CH of them, a total <= 2^15.
-#define PS_GRID  256
-#define PS_NCH   64  // FB chunks (x 4 row groups = PS_GRID)
-#define PS_CH    32  // FBs per chunk at most: frames up to 2048 non-skipped 64x64 blocks (3840x2160: 2040)
-constexpr unsigned long long PS_LOW = (1ull << 56) - 1;
-
+// (PS_GRID, PS_NCH, PS_CH and the tag mask PS_LOW: cdef_pick_plan.h)
 struct PersistArgs {
     const uint64_t     *wmse;   // [fb_alloc][2][64] compacted, bias applied
     const int32_t      *count;  // live FB count (device)
@@ -324,21 +317,6 @@ struct PersistArgs {
     const int32_t      *skip;   // the asynchronous pick's fallback: nonzero = every chain settled at the check, exit
     const uint32_t     *dep;    // ... its epoch, counted on the device (the check raises it when this launch will run)
 };
-
-// chain c's call at step s (the host schedule of the launch path): nb_sel = selection size of this call (-1: the
-// chain finished with the previous call; -2: the chain ended before), prev = the previous call's size (-1: none)
-struct ChainStep {
-    int nb, nb_sel, prev, shift;
-};
-__device__ __forceinline__ ChainStep chain_step(int c, int step) {
-    const int nb = 1 << c, len = 5 * nb;
-    ChainStep r;
-    r.nb     = nb;
-    r.nb_sel = step > len ? -2 : step < len ? (step < nb ? step : nb - 1) : -1;
-    r.prev   = step == 0 || step > len ? -1 : (step - 1 < nb ? step - 1 : nb - 1);
-    r.shift  = step >= 1 && step < len && step >= nb;
-    return r;
-}
 
 // poll the N tagged words p[i * stride] (those with use set) until every tag matches; false after the bounded wait
 template <int N>
@@ -413,7 +391,7 @@ __global__ void __launch_bounds__(NT, 4) sod_persist_kernel(const PersistArgs A)
         // selection; a finishing chain publishes its list and value
         {
             const int       c = w;
-            const ChainStep C = chain_step(c, step);
+            const PickChainStep C = pick_chain_step(c, step);
             if (C.prev >= 0) {
                 unsigned long long v[2] = {PS_LOW, PS_LOW};
                 if (!ps_poll<2>(A.amin + (c * 64 + lane) * 2, 1, lane < end, v, ptag)) s_fail = 1;
@@ -431,18 +409,18 @@ __global__ void __launch_bounds__(NT, 4) sod_persist_kernel(const PersistArgs A)
                     sl[c][16 + C.prev] = any ? bi & 63 : 0;
                     if (C.shift)
                         for (int q = 0; q < C.nb - 1; q++) sl[c][q] = sl[c][q + 1], sl[c][16 + q] = sl[c][16 + q + 1];
-                    if (li == 0 && C.nb_sel == -1) A.best[c] = any ? bv : ((uint64_t)1 << 63);
+                    if (li == 0 && C.nb_sel == PICK_FINISH) A.best[c] = any ? bv : ((uint64_t)1 << 63);
                 }
             }
         }
         __syncthreads();
-        if (li == 0 && t < MAX_CHAINS * 32 && chain_step(t >> 5, step).nb_sel == -1) A.fin[t] = sl[t >> 5][t & 31];
+        if (li == 0 && t < MAX_CHAINS * 32 && pick_chain_step(t >> 5, step).nb_sel == PICK_FINISH) A.fin[t] = sl[t >> 5][t & 31];
         if (step == NSTEPS) break; // the last step only finishes the longest chain
         if (A.stat && t == 0) tk[2] += __builtin_amdgcn_s_memrealtime() - t0, t0 = __builtin_amdgcn_s_memrealtime();
         // 2. per-FB best over each live chain's selection (EbEncCdef.c:645-651): wave c, lane f
         {
             const int       c = w;
-            const ChainStep C = chain_step(c, step);
+            const PickChainStep C = pick_chain_step(c, step);
             if (C.nb_sel >= 0 && lane < nfb) {
                 uint64_t b = (uint64_t)1 << 63;
                 for (int q = 0; q < C.nb_sel; q++) {
@@ -459,7 +437,7 @@ __global__ void __launch_bounds__(NT, 4) sod_persist_kernel(const PersistArgs A)
         const int j0 = 16 * g + 4 * w, k = lane;
 #pragma unroll 1
         for (int c = 0; c < MAX_CHAINS; c++) {
-            if (chain_step(c, step).nb_sel < 0) continue;
+            if (pick_chain_step(c, step).nb_sel < 0) continue;
             uint64_t acc[4] = {0, 0, 0, 0};
             if (!wide) {
 #pragma unroll 4
@@ -491,7 +469,7 @@ __global__ void __launch_bounds__(NT, 4) sod_persist_kernel(const PersistArgs A)
         {
             int na = 0, c = -1;
             for (int q = 0; q < MAX_CHAINS; q++)
-                if (chain_step(q, step).nb_sel >= 0) {
+                if (pick_chain_step(q, step).nb_sel >= 0) {
                     if (na == (li >> 6)) c = q;
                     na++;
                 }
@@ -527,16 +505,10 @@ __global__ void __launch_bounds__(NT, 4) sod_persist_kernel(const PersistArgs A)
 }
 
 // ---- the settle check: the launch path's steps after T skipped when every chain has settled by then ----
-// After step T's launch every chain c (nb = 1 << c, calls 0 .. L - 1, L = 5 nb) has either finished (L <= T) or
-// entered call T with the selection lev[T].  If lev[T]'s state (entries [0, nb - 1) of both halves) equals lev[T - nb]'s
-// with T - nb >= nb, the chain repeats with period nb from call T - nb on (sod_step_kernel's period shortcut), so its
-// last call L - 1 equals call a = T - nb + (L - 1 - T + nb) mod nb: the final list is lev[a] with slot nb - 1 taken from
-// lev[b] (b = the period twin of L: lev[t][nb - 1] is the result of call t - 1) and the value val[a + 1] -- exactly what
-// steps T + 1 .. L would produce.  One lane per chain; out[0] = 1 when every unfinished chain settled (their fin / best
-// written), out[1] = the latest step at which a chain that needs one settled (or finished): the host's next T.
-struct SettleOut {
-    int32_t settled, step, seq; // seq: the asynchronous pick that wrote it (its next T is read without a wait)
-};
+// One lane per chain applies pick_settle_chain (cdef_pick_plan.h: the period argument and the index arithmetic) to the
+// lists the steps up to T left and writes the final list and value of a chain that settled before it finished.
+// out->settled = 1 when every unfinished chain settled, out->step = the latest step at which a chain that needs one
+// settled (or finished): the host's next T.
 // flag (device memory, asynchronous pick): the settled word the later steps read
 // dep: the persistent fallback's epoch (asynchronous pick), raised when the check finds a chain unsettled -- only then
 // does the fallback launch run, so its exchange words' epochs differ from those of its last four real runs
@@ -545,28 +517,9 @@ __global__ void pick_settle_kernel(const int32_t *lev, const uint64_t *val, int3
     __shared__ int s_ok[MAX_CHAINS], s_at[MAX_CHAINS];
     const int c = threadIdx.x;
     if (c < MAX_CHAINS) {
-        const int nb = 1 << c, L = 5 * nb;
-        auto lv   = [&](int s, int i) { return lev[((size_t)s * MAX_CHAINS + c) * 32 + i]; };
-        auto same = [&](int s1, int s2) {
-            for (int q = 0; q < nb - 1; q++)
-                if (lv(s1, q) != lv(s2, q) || lv(s1, 16 + q) != lv(s2, 16 + q)) return false;
-            return true;
-        };
-        int at = L; // the first step from which the chain repeats (L: it finishes first)
-        for (int st = 2 * nb; st <= min(T, L - 1); st++)
-            if (same(st, st - nb)) {
-                at = st;
-                break;
-            }
-        bool ok = L <= T || at <= T;
-        if (L > T && ok) {
-            const int base = T - nb, a = base + (L - 1 - base) % nb, b = base + (L - base) % nb;
-            for (int i = 0; i < 32; i++) fin[c * 32 + i] = lv(a, i);
-            fin[c * 32 + nb - 1]      = lv(b, nb - 1);
-            fin[c * 32 + 16 + nb - 1] = lv(b, 16 + nb - 1);
-            best[c]                   = val[(size_t)(a + 1) * MAX_CHAINS + c];
-        }
-        s_ok[c] = ok, s_at[c] = at;
+        const PickSettle S = pick_settle_chain(lev, c, T);
+        if (S.copies()) pick_settle_write(lev, val, c, S, fin, best);
+        s_ok[c] = S.settled, s_at[c] = S.at;
     }
     __syncthreads();
     if (c == 0) {
@@ -582,18 +535,9 @@ __global__ void pick_settle_kernel(const int32_t *lev, const uint64_t *val, int3
     }
 }
 
-// ---- RD choice over the number of signalled strengths (EbEncCdef.c:853-872) ----
-struct PickOut {
-    int32_t  sb_count, nbits, status, seq; // seq: the asynchronous pick that wrote it (0: a synchronous one)
-    int32_t  gi[32]; // [0, 16) luma, [16, 32) chroma strength indices of the chosen list (zero past nb)
-    uint64_t best[MAX_CHAINS];
-};
-// the asynchronous pick's conversion of the chosen list into the frame parameters: strength index gi -> its code
-// (filter_map, EbEncCdef.c:911-919), the damping (:921)
-struct PickMap {
-    uint8_t code[64];
-    uint8_t damping;
-};
+// ---- RD choice over the number of signalled strengths (EbEncCdef.c:853-872), per-FB strengths, parameters ----
+// dprm: the asynchronous pick's frame parameters in device memory (what svtgpu_cdef_apply_frame reads with
+// params == NULL), or null
 __global__ void pick_final_kernel(const uint64_t *best, const int32_t *fin, const int32_t *count, uint64_t lambda,
                                   PickOut *out, int32_t *status, const uint64_t *wmse, const int32_t *fb_inv, int nfb,
                                   int8_t *fb_strength, int8_t *host_fbs, SvtGpuCdefParams *dprm, const PickMap map,
@@ -602,36 +546,18 @@ __global__ void pick_final_kernel(const uint64_t *best, const int32_t *fin, cons
     __shared__ int32_t s_nb;
     const int t = threadIdx.x;
     if (t == 0) { // every workgroup makes the same choice; workgroup 0 publishes it
-        const int sb_count  = *count;
-        uint64_t  best_cost = (uint64_t)1 << 63;
-        int       nbits = 0, chosen = -1; // no list chosen: the strengths stay zero
-        for (int i = 0; i <= 3; i++) {
-            const int      nb   = 1 << i;
-            const int      bits = sb_count * i + nb * 6 * 2;
-            const int64_t  rate = (int64_t)bits << 9;                                                  // av1_cost_literal
-            const uint64_t cost = (uint64_t)(((rate * (int64_t)lambda + 256) >> 9) + ((int64_t)(best[i] * 16) << 7)); // RDCOST
-            if (cost < best_cost) best_cost = cost, nbits = i, chosen = i;
-        }
-        const int nb = 1 << nbits;
-        for (int j = 0; j < 16; j++) {
-            gi[j]      = chosen >= 0 && j < nb ? fin[chosen * 32 + j] : 0;
-            gi[16 + j] = chosen >= 0 && j < nb ? fin[chosen * 32 + 16 + j] : 0;
-        }
-        s_nb = nb;
+        const int        sb_count = *count;
+        const PickChoice ch       = pick_rd_choice(best, sb_count, lambda);
+        pick_chosen_list(fin, ch, gi);
+        s_nb = 1 << ch.nbits;
         if (blockIdx.x == 0) {
             for (int j = 0; j < 32; j++) out->gi[j] = gi[j];
             out->sb_count = sb_count;
-            out->nbits    = nbits;
+            out->nbits    = ch.nbits;
             for (int c = 0; c < MAX_CHAINS; c++) out->best[c] = best[c];
             out->status = *status; // the persistent kernel's (0 on the launch path), re-armed for the next pick
             *status     = 0;
-            if (dprm) { // the parameters the apply reads (svtgpu_cdef_apply_frame with params == NULL)
-                SvtGpuCdefParams q;
-                memset(&q, 0, sizeof q);
-                q.cdef_damping = map.damping, q.cdef_bits = (uint8_t)nbits;
-                for (int j = 0; j < nb; j++) q.cdef_y_strength[j] = map.code[gi[j]], q.cdef_uv_strength[j] = map.code[gi[16 + j]];
-                *dprm = q;
-            }
+            if (dprm) *dprm = pick_params_from(map, ch.nbits, gi);
             if (seq) {
                 __threadfence_system();
                 __hip_atomic_store(&out->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -643,236 +569,168 @@ __global__ void pick_final_kernel(const uint64_t *best, const int32_t *fin, cons
     const int fb = blockIdx.x * blockDim.x + t;
     if (fb >= nfb) return;
     const int i  = fb_inv[fb];
-    int       bg = 0;
-    if (i >= 0) {
-        const uint64_t *m0 = wmse + (size_t)i * 128, *m1 = m0 + 64;
-        uint64_t        bc = (uint64_t)1 << 63;
-        for (int g = 0; g < s_nb; g++) {
-            const uint64_t c = m0[gi[g]] + m1[gi[16 + g]];
-            if (c < bc) bc = c, bg = g;
-        }
-    }
+    const int bg = i >= 0 ? pick_fb_strength(wmse + (size_t)i * 128, wmse + (size_t)i * 128 + 64, gi, s_nb) : 0;
     fb_strength[fb] = (int8_t)bg;
     if (host_fbs) host_fbs[fb] = (int8_t)bg;
 }
 
-// FB-chunk workgroups per step across the live chains (x 4 row tiles): more parts spread the accumulation, fewer
-// parts mean fewer u64 atomics into the 4096 totals (SVTGPU_PICK_PARTS for sweeps)
-static int pick_parts() {
-    static const int v = [] {
-        const char *e = std::getenv("SVTGPU_PICK_PARTS");
-        return e && std::atoi(e) > 0 ? std::atoi(e) : 64;
-    }();
-    return v;
+// ---- the host path ----
+// the pick's buffers of a state, carved by PickLayout
+struct PickBufs {
+    uint64_t           *wmse, *tot, *val, *best;
+    uint32_t           *wmse32;
+    int32_t            *lev, *fin, *wide, *fb_list, *count, *fb_inv;
+    unsigned long long *part, *amin, *stat; // the persistent kernel's exchange and diagnostics
+    int32_t            *status;
+    int32_t            *flag; // the asynchronous pick: the settled word, the fallback's epoch, the apply's parameters
+    uint32_t           *dep;
+    SvtGpuCdefParams   *dprm;
+    PickOut            *h_out, *d_out; // the mapped record: host and device addresses
+    SettleOut          *h_settle, *d_settle;
+    int8_t             *h_fbs, *d_fbs;
+};
+static PickBufs pick_bufs(const SvtGpuCdefFrameState *s) {
+    const PickLayout L(s->nfb);
+    PickBufs         B;
+    B.wmse = s->d_pick_part + L.part_wmse, B.tot = s->d_pick_part + L.part_tot, B.val = s->d_pick_part + L.part_val;
+    B.wmse32 = (uint32_t *)(s->d_pick_part + L.part_wmse32);
+    B.best   = s->d_pick_out;
+    B.lev = s->d_pick_lev + L.lev_lev, B.fin = s->d_pick_lev + L.lev_fin, B.wide = s->d_pick_lev + L.lev_wide;
+    B.fb_list = s->d_fb_list + L.list_fb, B.count = s->d_fb_list + L.list_count, B.fb_inv = s->d_fb_list + L.list_inv;
+    unsigned long long *xch = (unsigned long long *)s->d_pick_xch;
+    B.part = xch + L.xch_part, B.amin = xch + L.xch_amin, B.stat = xch + L.xch_stat;
+    B.status = (int32_t *)(xch + L.xch_status);
+    uint8_t *ap = (uint8_t *)s->d_apick;
+    B.flag = (int32_t *)(ap + L.apick_flag), B.dep = (uint32_t *)(ap + L.apick_dep);
+    B.dprm = (SvtGpuCdefParams *)(ap + L.apick_params);
+    B.h_out = (PickOut *)(s->h_pick + L.rec_out), B.d_out = (PickOut *)(s->h_pick_dev + L.rec_out);
+    B.h_settle = (SettleOut *)(s->h_pick + L.rec_settle), B.d_settle = (SettleOut *)(s->h_pick_dev + L.rec_settle);
+    B.h_fbs = (int8_t *)(s->h_pick + L.rec_fbs), B.d_fbs = (int8_t *)(s->h_pick_dev + L.rec_fbs);
+    return B;
 }
 
-// FBs per workgroup at most (SVTGPU_PICK_CHUNK, a multiple of 4 up to PICK_CHUNK, for sweeps)
-static int pick_chunk() {
-    static const int v = [] {
-        const char *e = std::getenv("SVTGPU_PICK_CHUNK");
-        const int   c = e ? std::atoi(e) : 0;
-        return c >= 4 && c <= PICK_CHUNK ? c & ~3 : PICK_CHUNK;
-    }();
-    return v;
-}
-
-void cdef_pick_host_result(SvtGpuCdefFrameState *s, const PickMap &map, SvtGpuCdefParams *params,
-                           int8_t *fb_strength_out);
-
-// params == nullptr: the asynchronous pick (svtgpu_cdef_pick_async) -- no host wait: the settle check's outcome reaches
-// the later steps through a device flag (they exit at once when every chain has settled), the final kernel writes the
-// frame parameters to device memory for the apply, and the host reads the result later (svtgpu_cdef_read_params)
-int svtgpu_cdef_pick_impl(SvtGpuCdefFrameState *s, const SvtGpuCdefControls *ctrls, int32_t base_q_idx,
-                          uint64_t lambda, SvtGpuCdefParams *params, int8_t *fb_strength_out, hipStream_t st) {
-    const bool async_ = params == nullptr;
+// the non-skipped FBs in raster order, then their rows with the zero-strength bias; tot0: the first step's accumulators
+// to clear (launch path) or null
+static void launch_compact_gather(const SvtGpuCdefFrameState *s, const PickBufs &B, int bias, uint64_t *tot0, hipStream_t st) {
     const int nfb = s->nfb;
-    const int end = ctrls->first_pass_fs_num + ctrls->default_second_pass_fs_num;
-    if (end <= 0 || end > 64)
-        return SVTGPU_ERR_INVALID_ARG;
-    uint64_t *wmse = s->d_pick_part; // layout: [nfb*128] wmse, then partials
-    const size_t wmse_elems = (size_t)nfb * 128;
-    int32_t  *d_count = s->d_fb_list + nfb;
-    StepArgs  A;
-    A.lev  = s->d_pick_lev;                                  // [NSTEPS+1][4][32]
-    A.fin  = s->d_pick_lev + (NSTEPS + 1) * MAX_CHAINS * 32; // [4][32]
-    A.wide = A.fin + MAX_CHAINS * 32 + 33;                   // after the chosen list (32) and nb
-    // the persistent launch (SVTGPU_PICK_PERSIST=1; default: the launch per step) while its chunks hold every FB
-    const char *pe      = std::getenv("SVTGPU_PICK_PERSIST");
-    const bool  persist = pe && pe[0] == '1' && nfb <= PS_NCH * PS_CH;
-    int32_t    *d_inv   = s->d_fb_list + nfb + 1;
-    A.tot               = wmse + wmse_elems;                          // [3][4][4096]
-    A.val               = A.tot + (size_t)3 * MAX_CHAINS * 4096;      // [NSTEPS+1][4]
-    uint32_t *wmse32    = (uint32_t *)(A.val + (NSTEPS + 1) * MAX_CHAINS); // [nfb][128] low words
-    A.wmse32            = wmse32;
-    hipLaunchKernelGGL(pick_compact_kernel, dim3(1), dim3(NT), 0, st, s->d_skip, nfb, s->d_fb_list, d_count,
-                       (int32_t *)A.wide, d_inv);
-    const int sb_max = nfb; // launch shapes for every FB; the kernels read the non-skipped count on the device
+    hipLaunchKernelGGL(pick_compact_kernel, dim3(1), dim3(NT), 0, st, s->d_skip, nfb, B.fb_list, B.count, B.wide, B.fb_inv);
+    hipLaunchKernelGGL(pick_gather_kernel, dim3(nfb), dim3(128), 0, st, s->d_mse, nfb, B.fb_list, B.count, bias, B.wmse,
+                       B.wmse32, B.wide, tot0);
+}
 
-    A.wmse     = wmse;
-    A.fb_alloc = nfb;
-    A.count    = d_count;
-    A.start_gi = 0;
-    A.end_gi   = end;
-    A.best     = s->d_pick_out;
-    A.skip     = nullptr;
-    hipLaunchKernelGGL(pick_gather_kernel, dim3(nfb), dim3(128), 0, st, s->d_mse, nfb, s->d_fb_list, d_count,
-                       (int)ctrls->zero_fs_cost_bias, wmse, wmse32, (int32_t *)A.wide, persist ? nullptr : A.tot);
-    unsigned long long *xch = (unsigned long long *)s->d_pick_xch, *stat = nullptr;
-    int32_t            *d_status = (int32_t *)(xch + PS_NCH * 4 * 4096 + 4 * 64 * 2);
-    if (persist) {
-        static const bool stats = std::getenv("SVTGPU_PICK_STATS") != nullptr;
-        if (s->pick_xch_end != end) { // words of a different strength count could carry a current tag
-            HIP_TRY(hipMemsetAsync(xch, 0, SVTGPU_PICK_XCH_BYTES, st));
-            s->pick_xch_end = end;
-        }
-        if (stats) stat = xch + PS_NCH * 4 * 4096 + 4 * 64 * 2 + 8;
-        PersistArgs P;
-        P.wmse     = wmse;
-        P.count    = d_count;
-        P.wide     = A.wide;
-        P.chunk    = std::max(1, (nfb + PS_NCH - 1) / PS_NCH);
-        P.fb_alloc = nfb;
-        P.end_gi   = end;
-        P.epoch    = s->pick_epoch++;
-        P.part     = xch;
-        P.amin     = xch + PS_NCH * 4 * 4096;
-        P.fin      = A.fin;
-        P.best     = A.best;
-        P.status   = d_status;
-        P.stat     = stat;
-        P.skip     = nullptr;
-        P.dep      = nullptr;
-        hipLaunchKernelGGL(sod_persist_kernel, dim3(PS_GRID), dim3(NT), 0, st, P);
+// The persistent kernel's exchange words are valid by their tags alone, and words of a different strength count could
+// carry a current tag: they are cleared, in stream order, when `end` changes.  Before every persistent launch.
+static int xch_prepare(SvtGpuCdefFrameState *s, int end, hipStream_t st) {
+    if (s->pick_xch_end == end) return SVTGPU_OK;
+    HIP_TRY(hipMemsetAsync(s->d_pick_xch, 0, PickLayout::xch_bytes, st));
+    s->pick_xch_end = end;
+    return SVTGPU_OK;
+}
+
+// One persistent launch runs the whole pick.  The pick proper: tagged by the host's epoch, diagnostics in stat (or
+// null).  The asynchronous pick's fallback: returns at once when *skip says every chain settled at the check, tagged by
+// the epoch *dep the check counts on the device.
+static void launch_persist(const PickBufs &B, int nfb, int end, uint32_t epoch, unsigned long long *stat,
+                           const int32_t *skip, const uint32_t *dep, hipStream_t st) {
+    PersistArgs P;
+    P.wmse     = B.wmse;
+    P.count    = B.count;
+    P.wide     = B.wide;
+    P.chunk    = ps_chunk(nfb);
+    P.fb_alloc = nfb;
+    P.end_gi   = end;
+    P.epoch    = epoch;
+    P.part     = B.part;
+    P.amin     = B.amin;
+    P.fin      = B.fin;
+    P.best     = B.best;
+    P.status   = B.status;
+    P.stat     = stat;
+    P.skip     = skip;
+    P.dep      = dep;
+    hipLaunchKernelGGL(sod_persist_kernel, dim3(PS_GRID), dim3(NT), 0, st, P);
+}
+
+// what every step launch of a pick shares
+static StepArgs step_args(const PickBufs &B, int nfb, int end) {
+    StepArgs A{};
+    A.wmse = B.wmse, A.wmse32 = B.wmse32, A.count = B.count, A.wide = B.wide;
+    A.start_gi = 0, A.end_gi = end, A.fb_alloc = nfb;
+    A.tot = B.tot, A.lev = B.lev, A.fin = B.fin, A.best = B.best, A.val = B.val;
+    return A;
+}
+// step `step` of the launch path: the schedule's entry of every chain that has not ended, shaped for their number.
+// skip: the asynchronous pick's settled word (steps after the check) or null
+static void launch_step(StepArgs &A, int step, const PickKnobs &K, const int32_t *skip, hipStream_t st) {
+    int na = 0;
+    for (int c = 0; c < MAX_CHAINS; c++) {
+        const PickChainStep C = pick_chain_step(c, step);
+        if (C.nb_sel != PICK_ENDED) A.ch[na++] = StepChain{c, C.nb, C.nb_sel, C.prev, C.shift};
     }
-    // the settle checkpoint (SVTGPU_PICK_SETTLE=0: off): after step T one small kernel checks whether every chain has
-    // settled into its period and, if so, writes the final lists, and the host skips the remaining launches (one
-    // wait instead of up to 40 - T dependent launches, each of which waits for free CU slots when other frames' kernels
-    // hold the device).  T follows the last pick's settling step; an unsettled check moves it 4 steps later
-    static const bool settle_on = [] {
-        const char *e = std::getenv("SVTGPU_PICK_SETTLE");
-        return !(e && e[0] == '0');
-    }();
-    SettleOut *h_settle = (SettleOut *)(s->h_pick + 448), *d_settle = (SettleOut *)(s->h_pick_dev + 448);
-    static_assert(sizeof(PickOut) <= 448, "pick output slot below the settle record");
-    int32_t *d_flag = (int32_t *)s->d_apick; // asynchronous: the settled word (device memory)
-    if (async_) {
-        // the last asynchronous check whose record has landed (read without a wait: the host may run ahead of the
-        // device) moves T as the synchronous path does right after its check
-        const volatile SettleOut *hs = (const volatile SettleOut *)h_settle;
-        if (hs->seq != 0 && hs->seq != s->settle_seen) {
-            s->settle_seen = hs->seq;
-            if (hs->settled) {
-                s->pick_settle = hs->step, s->pick_miss = 0;
-            } else {
-                s->pick_settle = std::min(s->pick_settle + 4, NSTEPS - 4);
-                if (++s->pick_miss >= 2) s->pick_skip = 8, s->pick_miss = 0;
-            }
-        }
-    }
-    // after two consecutive checks that found a chain unsettled the next 8 picks skip the check (its host wait saves
-    // nothing on a sequence that does not settle), then it is tried again from step 24
-    const bool check = settle_on && s->pick_skip == 0;
-    if (s->pick_skip > 0 && --s->pick_skip == 0) s->pick_settle = 24;
-    const int T = check ? std::min(std::max(s->pick_settle, 16), NSTEPS) : NSTEPS;
-    // asynchronous: after the check no further step is launched -- when a chain has not settled, one persistent launch
-    // (sod_persist_kernel, which returns at once when the check's flag says settled) recomputes the whole pick.  The
-    // flag-only step launches it replaces each needed 256 workgroup slots, which at four frames in flight waited for
-    // CUs held by other frames' kernels.  Frames with more FBs than its chunks hold keep the flagged launches.
-    const char *afb         = std::getenv("SVTGPU_PICK_ASYNC_FALLBACK"); // =steps: the flagged step launches (A/B)
-    const bool  async_steps = afb && !std::strcmp(afb, "steps");
-    const bool pfb = async_ && !persist && !async_steps && T < NSTEPS && nfb <= PS_NCH * PS_CH;
-    if (pfb && s->pick_xch_end != end) { // words of a different strength count could carry a current tag
-        HIP_TRY(hipMemsetAsync(s->d_pick_xch, 0, SVTGPU_PICK_XCH_BYTES, st));
-        s->pick_xch_end = end;
-    }
-    for (int step = 0; step <= NSTEPS && !persist && !(pfb && step > T); step++) {
-        int na = 0;
-        for (int c = 0; c < MAX_CHAINS; c++) {
-            const int nb = 1 << c, len = 5 * nb; // nb calls + 4*nb refinements
-            if (step > len) continue;
-            StepChain &C   = A.ch[na++];
-            C.chain        = c;
-            C.nb           = nb;
-            C.nb_sel       = step < len ? (step < nb ? step : nb - 1) : -1;
-            C.prev_nb_sel  = step == 0 ? -1 : (step - 1 < nb ? step - 1 : nb - 1);
-            C.prev_shift   = step >= 1 && step < len && step >= nb; // shift before calls nb.. (refinements)
-        }
-        A.step = step;
-        A.skip = async_ && step > T ? d_flag : nullptr;
-        // ~256 workgroups per step whatever the number of live chains (64 parts x 4 row tiles: 256 parts spent
-        // more on the u64 atomics than they gained, 0.66 -> 0.59 ms per pick + apply); chunk <= PICK_CHUNK FBs
-        const int want  = std::max(1, pick_parts() / std::max(na, 1));
-        A.chunk         = std::min(pick_chunk(), std::max(4, (sb_max + want - 1) / std::max(want, 1)));
-        const int parts = std::max(1, (sb_max + A.chunk - 1) / A.chunk);
-        const size_t lds = (size_t)A.chunk * (MROW * 4 + 8);
-        A.na    = na;
-        A.wgclk = svtgpu_wgclk_begin(4 * parts * na);
-        hipLaunchKernelGGL(sod_step_kernel, dim3(4 * parts * na), dim3(NT), lds, st, A);
-        svtgpu_wgclk_end("sod_step", 4 * parts * na, st);
-        if (step == T && T < NSTEPS && async_) { // the check in stream order; the later steps read its flag
-            hipLaunchKernelGGL(pick_settle_kernel, dim3(1), dim3(64), 0, st, (const int32_t *)A.lev,
-                               (const uint64_t *)A.val, A.fin, A.best, T, d_settle, d_flag, ++s->settle_seq,
-                               pfb ? (uint32_t *)((uint8_t *)s->d_apick + 8) : (uint32_t *)nullptr);
-            HIP_TRY(hipGetLastError());
-        } else if (step == T && T < NSTEPS) {
-            hipLaunchKernelGGL(pick_settle_kernel, dim3(1), dim3(64), 0, st, (const int32_t *)A.lev,
-                               (const uint64_t *)A.val, A.fin, A.best, T, d_settle, (int32_t *)nullptr, 0,
-                               (uint32_t *)nullptr);
-            HIP_TRY(hipGetLastError());
-            if (int rc = svtgpu_comm_wait(s->comm, st)) return rc; // bounded behind the tables' exchange
-            svtgpu_count_xfer(1, sizeof(SettleOut));
-            if (h_settle->settled) {
-                s->pick_settle = h_settle->step;
-                s->pick_miss   = 0;
-                break;
-            }
-            s->pick_settle = std::min(T + 4, NSTEPS - 4); // keep checking: a later frame may settle
-            if (++s->pick_miss >= 2) s->pick_skip = 8, s->pick_miss = 0;
-        }
-    }
+    const PickStepShape sh = pick_step_shape(K, A.fb_alloc, na);
+    A.step = step, A.na = na, A.chunk = sh.chunk, A.skip = skip;
+    A.wgclk = svtgpu_wgclk_begin(sh.grid);
+    hipLaunchKernelGGL(sod_step_kernel, dim3(sh.grid), dim3(NT), sh.lds, st, A);
+    svtgpu_wgclk_end("sod_step", sh.grid, st);
+}
+
+// The settle check after step T, in stream order.  The synchronous pick waits for its record; the asynchronous pick's
+// later launches read its flag instead, its record carries a sequence number for the host to take later, and with a
+// persistent fallback (pfb) the check counts that launch's epoch.
+static int launch_settle(SvtGpuCdefFrameState *s, const PickBufs &B, int T, bool async_, bool pfb, hipStream_t st) {
+    hipLaunchKernelGGL(pick_settle_kernel, dim3(1), dim3(64), 0, st, (const int32_t *)B.lev, (const uint64_t *)B.val,
+                       B.fin, B.best, T, B.d_settle, async_ ? B.flag : (int32_t *)nullptr, async_ ? ++s->settle_seq : 0,
+                       pfb ? B.dep : (uint32_t *)nullptr);
     HIP_TRY(hipGetLastError());
-    if (pfb) { // the fallback: the whole pick again, only when the check found a chain unsettled
-        PersistArgs P;
-        P.wmse     = wmse;
-        P.count    = d_count;
-        P.wide     = A.wide;
-        P.chunk    = std::max(1, (nfb + PS_NCH - 1) / PS_NCH);
-        P.fb_alloc = nfb;
-        P.end_gi   = end;
-        P.epoch    = 0;
-        P.part     = (unsigned long long *)s->d_pick_xch;
-        P.amin     = P.part + PS_NCH * 4 * 4096;
-        P.fin      = A.fin;
-        P.best     = A.best;
-        P.status   = d_status;
-        P.stat     = nullptr;
-        P.skip     = d_flag;
-        P.dep      = (const uint32_t *)((const uint8_t *)s->d_apick + 8);
-        hipLaunchKernelGGL(sod_persist_kernel, dim3(PS_GRID), dim3(NT), 0, st, P);
-        HIP_TRY(hipGetLastError());
+    return SVTGPU_OK;
+}
+
+// The launch path: steps 0 .. NSTEPS with the settle check after step T (T == NSTEPS: no check).  Synchronous: the
+// host waits for the check and stops launching when every chain has settled (one wait instead of up to 40 - T
+// dependent launches, each of which waits for free CU slots when other frames' kernels hold the device).
+// Asynchronous: no wait -- with the persistent fallback (pfb) no step follows the check; else the later steps read
+// the check's flag and return at once when every chain has settled.
+static int run_steps(SvtGpuCdefFrameState *s, const PickBufs &B, const PickKnobs &K, int end, int T, bool async_, bool pfb,
+                     hipStream_t st) {
+    StepArgs  A    = step_args(B, s->nfb, end);
+    const int last = pfb ? T : NSTEPS;
+    for (int step = 0; step <= last; step++) {
+        launch_step(A, step, K, async_ && step > T ? B.flag : nullptr, st);
+        if (step != T || T == NSTEPS) continue;
+        if (int rc = launch_settle(s, B, T, async_, pfb, st)) return rc;
+        if (async_) continue;
+        if (int rc = svtgpu_comm_wait(s->comm, st)) return rc; // bounded behind the tables' exchange
+        svtgpu_count_xfer(1, sizeof(SettleOut));
+        s->pick_policy.outcome_sync(B.h_settle->settled != 0, B.h_settle->step, T);
+        if (B.h_settle->settled) break;
     }
-    PickOut *h_out = (PickOut *)s->h_pick;
-    static_assert(sizeof(PickOut) <= 512, "pick output slot");
-    int8_t *host_fbs = fb_strength_out || async_ ? (int8_t *)(s->h_pick_dev + 512) : nullptr;
-    PickMap map;
-    std::memset(&map, 0, sizeof map);
-    const int nf = ctrls->first_pass_fs_num;
-    for (int g = 0; g < end; g++) // gi -> strength code (filter_map, EbEncCdef.c:911-919)
-        map.code[g] = g < nf ? ctrls->default_first_pass_fs[g] : ctrls->default_second_pass_fs[g - nf];
-    map.damping = (uint8_t)(3 + (base_q_idx >> 6)); // :921
-    const int seq = async_ ? ++s->apick_seq : 0;
-    hipLaunchKernelGGL(pick_final_kernel, dim3((nfb + NT - 1) / NT), dim3(NT), 0, st, (const uint64_t *)s->d_pick_out,
-                       (const int32_t *)A.fin, (const int32_t *)d_count, (uint64_t)lambda, (PickOut *)s->h_pick_dev,
-                       d_status, (const uint64_t *)wmse, (const int32_t *)d_inv, nfb, s->d_fb_strength, host_fbs,
-                       async_ ? (SvtGpuCdefParams *)((uint8_t *)s->d_apick + 16) : (SvtGpuCdefParams *)nullptr, map, seq);
-    HIP_TRY(hipGetLastError());
-    if (async_) {
-        std::memcpy(s->apick_map, map.code, 64);
-        s->apick_damping = map.damping;
-        return SVTGPU_OK;
-    }
-    if (int rc = svtgpu_comm_wait(s->comm, st)) return rc; // the only wait of the pick (bounded when tiled)
-    if (h_out->status) {
+    return SVTGPU_OK;
+}
+
+// The asynchronous pick learns a check's outcome from the last record that has landed, read without a wait (the host may
+// run ahead of the device), at the start of a later pick.
+static void settle_take_async(SvtGpuCdefFrameState *s, const PickBufs &B) {
+    const volatile SettleOut *hs = B.h_settle;
+    if (hs->seq == 0 || hs->seq == s->settle_seen) return;
+    s->settle_seen = hs->seq;
+    s->pick_policy.outcome_async(hs->settled != 0, hs->step);
+}
+
+// the pick's result from the mapped record (after the stream wait): the parameters through the strength map, the
+// per-FB strengths
+static void cdef_pick_host_result(SvtGpuCdefFrameState *s, const PickMap &map, SvtGpuCdefParams *params,
+                                  int8_t *fb_strength_out) {
+    const PickBufs B = pick_bufs(s);
+    *params          = pick_params_from(map, B.h_out->nbits, B.h_out->gi);
+    if (fb_strength_out) memcpy(fb_strength_out, B.h_fbs, s->nfb);
+    svtgpu_count_xfer(1, sizeof(PickOut) + (fb_strength_out ? s->nfb : 0)); // mapped memory
+}
+
+// the synchronous pick's only wait (bounded when tiled), then its result; stat: the persistent kernel's diagnostics or null
+static int pick_read_sync(SvtGpuCdefFrameState *s, const PickBufs &B, unsigned long long *stat, const PickMap &map,
+                          SvtGpuCdefParams *params, int8_t *fb_strength_out, hipStream_t st) {
+    if (int rc = svtgpu_comm_wait(s->comm, st)) return rc;
+    if (B.h_out->status) {
         svtgpu_set_last_hip_error(hipErrorUnknown, "CDEF pick: the persistent step exchange timed out", __FILE__, __LINE__);
         return SVTGPU_ERR_HIP;
     }
@@ -887,21 +745,43 @@ int svtgpu_cdef_pick_impl(SvtGpuCdefFrameState *s, const SvtGpuCdefControls *ctr
     return SVTGPU_OK;
 }
 
-// the pick's result from the mapped record (after the stream wait): the parameters through the strength map, the
-// per-FB strengths
-void cdef_pick_host_result(SvtGpuCdefFrameState *s, const PickMap &map, SvtGpuCdefParams *params,
-                           int8_t *fb_strength_out) {
-    const PickOut *h_out = (const PickOut *)s->h_pick;
-    memset(params, 0, sizeof(*params));
-    const int nbits = h_out->nbits, nb = 1 << nbits;
-    params->cdef_bits    = (uint8_t)nbits;
-    params->cdef_damping = map.damping;
-    for (int j = 0; j < nb; j++) {
-        params->cdef_y_strength[j]  = map.code[h_out->gi[j]];
-        params->cdef_uv_strength[j] = map.code[h_out->gi[16 + j]];
-    }
-    if (fb_strength_out) memcpy(fb_strength_out, s->h_pick + 512, s->nfb);
-    svtgpu_count_xfer(1, sizeof(PickOut) + (fb_strength_out ? s->nfb : 0)); // mapped memory
+// params == nullptr: the asynchronous pick (svtgpu_cdef_pick_async) -- no host wait: the settle check's outcome reaches
+// the later steps through a device flag (they exit at once when every chain has settled), the final kernel writes the
+// frame parameters to device memory for the apply, and the host reads the result later (svtgpu_cdef_read_params).
+// After the check the asynchronous pick launches no further step: when a chain has not settled, one persistent launch
+// (which returns at once when the check's flag says settled) recomputes the whole pick.  The flag-only step launches it
+// replaces each needed 256 workgroup slots, which at four frames in flight waited for CUs held by other frames'
+// kernels.  Frames with more FBs than its chunks hold, and SVTGPU_PICK_ASYNC_FALLBACK=steps, keep the flagged launches.
+int svtgpu_cdef_pick_impl(SvtGpuCdefFrameState *s, const SvtGpuCdefControls *ctrls, int32_t base_q_idx,
+                          uint64_t lambda, SvtGpuCdefParams *params, int8_t *fb_strength_out, hipStream_t st) {
+    const bool async_ = params == nullptr;
+    const int  nfb = s->nfb, end = ctrls->first_pass_fs_num + ctrls->default_second_pass_fs_num;
+    if (end <= 0 || end > 64)
+        return SVTGPU_ERR_INVALID_ARG;
+    const PickKnobs K       = pick_knobs();
+    const PickBufs  B       = pick_bufs(s);
+    const bool      persist = K.persist && ps_fits(nfb); // while its chunks hold every FB
+    launch_compact_gather(s, B, ctrls->zero_fs_cost_bias, persist ? nullptr : B.tot, st);
+    if (async_) settle_take_async(s, B);
+    const int  T   = s->pick_policy.begin(K.settle); // on either path: a persistent pick counts as one without a check
+    const bool pfb = async_ && !persist && !K.async_steps && T < NSTEPS && ps_fits(nfb); // the persistent fallback
+    unsigned long long *stat = persist && K.stats ? B.stat : nullptr;
+    if (persist || pfb)
+        if (int rc = xch_prepare(s, end, st)) return rc;
+    if (persist) launch_persist(B, nfb, end, s->pick_epoch++, stat, nullptr, nullptr, st);
+    else if (int rc = run_steps(s, B, K, end, T, async_, pfb, st)) return rc;
+    if (pfb) launch_persist(B, nfb, end, 0, nullptr, B.flag, B.dep, st);
+    HIP_TRY(hipGetLastError());
+    const PickMap map = pick_map_from(*ctrls, base_q_idx);
+    hipLaunchKernelGGL(pick_final_kernel, dim3((nfb + NT - 1) / NT), dim3(NT), 0, st, (const uint64_t *)B.best,
+                       (const int32_t *)B.fin, (const int32_t *)B.count, lambda, B.d_out, B.status, (const uint64_t *)B.wmse,
+                       (const int32_t *)B.fb_inv, nfb, s->d_fb_strength, fb_strength_out || async_ ? B.d_fbs : (int8_t *)nullptr,
+                       async_ ? B.dprm : (SvtGpuCdefParams *)nullptr, map, async_ ? ++s->apick_seq : 0);
+    HIP_TRY(hipGetLastError());
+    if (!async_) return pick_read_sync(s, B, stat, map, params, fb_strength_out, st);
+    std::memcpy(s->apick_map, map.code, 64); // the read-back's strength map
+    s->apick_damping = map.damping;
+    return SVTGPU_OK;
 }
 
 // svtgpu_cdef_read_params: the last asynchronous pick's result, after a (bounded) wait for the stream
@@ -913,7 +793,7 @@ int svtgpu_cdef_pick_read(SvtGpuCdefFrameState *s, SvtGpuCdefParams *params, int
         if (fb_strength_out) memset(fb_strength_out, 0, s->nfb);
         return SVTGPU_OK;
     }
-    const volatile PickOut *h_out = (const volatile PickOut *)s->h_pick;
+    const volatile PickOut *h_out = pick_bufs(s).h_out;
     if (h_out->seq != s->apick_seq) {
         svtgpu_set_last_hip_error(hipErrorUnknown, "CDEF asynchronous pick: result record missing after the stream wait",
                                   __FILE__, __LINE__);

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "../../include/svtgpu.h"
+#include "cdef_pick_plan.h"
 
 #define SVTGPU_VERSION_STR "svtgpu 0.1.0 (gfx950)"
 
@@ -81,10 +82,6 @@ int  svtgpu_prio_enter(SvtGpuPrioLane *l, hipStream_t st, hipStream_t *out);
 int  svtgpu_prio_leave(SvtGpuPrioLane *l, hipStream_t hs, hipStream_t st);
 void svtgpu_prio_destroy(SvtGpuPrioLane *l);
 
-// persistent pick exchange (cdef_pick.hip): [64 chunks][4 chains][4096] partial sums, [4][64][2] row minima,
-// then status and diagnostics words
-#define SVTGPU_PICK_XCH_BYTES ((size_t)(64 * 4 * 4096 + 4 * 64 * 2 + 16) * 8)
-
 struct SvtGpuCdefFrameState {
     SvtGpuContext *ctx;
     int32_t        width, height;
@@ -96,20 +93,20 @@ struct SvtGpuCdefFrameState {
     uint8_t       *d_dir;         // [nfb][64]
     int32_t       *d_var;         // [nfb][64]
     int8_t        *d_fb_strength; // [nfb]
-    // pick scratch
-    uint64_t      *d_pick_part;   // partial tot_mse tables
-    uint64_t      *d_pick_out;    // [chains][4] (best, j, k)
-    int32_t       *d_pick_lev;    // [chains][2][16]
+    // pick scratch: every offset and size in PickLayout (cdef_pick_plan.h)
+    uint64_t      *d_pick_part;   // compacted mse tables [nfb][2][64], the steps' rotating tot_mse accumulators
+                                  // [3][4][4096], the calls' values [41][4], the tables' low words (32-bit) [nfb][2][64]
+    uint64_t      *d_pick_out;    // [4] the value of each chain's last call
+    int32_t       *d_pick_lev;    // [41][4][32] the selection entering each call ([0, 16) luma, [16, 32) chroma), [4][32]
+                                  // the chains' final lists, the width flag
     int32_t       *d_fb_list;     // compacted non-skip FB indices [nfb], their count, FB -> index or -1 [nfb]
     uint64_t      *d_pick_xch;    // persistent pick: tagged partial sums, row minima, status, diagnostics (cdef_pick.hip)
     uint32_t       pick_epoch;    // picks run by the persistent kernel (tags its exchange words)
-    int32_t        pick_settle;   // the launch path's settle checkpoint: the step after which the pick checks
-    int32_t        pick_miss;     // consecutive checks that found a chain unsettled
-    int32_t        pick_skip;     // picks left that run without the check (after 2 misses: 8)
+    PickSettlePolicy pick_policy; // the launch path's settle checkpoint: where the next pick checks, misses, skips
     int32_t        pick_xch_end;  // the strength count of the words in d_pick_xch (0: none written)
-    uint8_t       *h_pick;        // pinned, mapped: the pick's result (PickOut) then the per-FB strengths [nfb]
+    uint8_t       *h_pick;        // pinned, mapped: the pick's result (PickOut), the settle record (SettleOut), then the
+                                  // per-FB strengths [nfb]
     uint8_t       *h_pick_dev;    // its device address
-    int32_t        pick_parts;
     int32_t        mask_all;      // mask == every block
     int32_t        fb_rect[4];    // {col0, row0, col1, row1}: the filter blocks searched (tiling over GPUs)
     int32_t        out_rect[4];   // {x0, y0, x1, y1} luma: the samples the apply writes (tiling over GPUs)
@@ -123,7 +120,8 @@ struct SvtGpuCdefFrameState {
     int8_t        *h_fb_kind;     // host copy
     uint8_t       *d_mse_rem;     // [3][nfb][64] remainders of the per-FB distortion shift (SB128 only)
     SvtGpuPrioLane prio;          // the pick's launch chain
-    // svtgpu_cdef_pick_async: [0] the settle check's flag for the later steps, [16..] the parameters the apply reads
+    // svtgpu_cdef_pick_async: the settle check's flag for the later steps, the persistent fallback's epoch, the
+    // parameters the apply reads (PickLayout::apick_*)
     void          *d_apick;
     int32_t        settle_seq, settle_seen; // settle checks enqueued / the last one whose record the host has taken
     int32_t        apick_seq;               // asynchronous picks enqueued (the record's seq)

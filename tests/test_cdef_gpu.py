@@ -364,6 +364,39 @@ def test_cdef_pick_settled_chains_vs_oracle(ctx, monkeypatch, scale_hi):
     assert seen == {True, False}  # settled and unsettled chains both covered
 
 
+def test_cdef_pick_unsettled_skip_path_vs_oracle(ctx, monkeypatch):
+    """The checkpoint policy's skip path on the device: a 640x384 frame (60 blocks) whose convex table leaves a chain
+    unsettled through its last call (asserted with _settle_calls), picked 12 times with the synchronous pick and 12
+    times with pick_async + read_params on one state.  Every check misses, so the picks run through two misses, the 8
+    picks without a check and the check from step 24 again (synchronous: steps to the end after a miss; asynchronous:
+    the persistent fallback after a miss, no fallback on the picks without a check); every result equals the oracle's."""
+    import torch
+    monkeypatch.setenv("SVTGPU_PICK_PERSIST", "0")
+    w, h, q, lam = 640, 384, 128, 60000
+    ctrls = svtgpu.cdef_controls(1)
+    st = svtgpu.CdefState(ctx, w, h)
+    assert st.nfb == 60
+    rng = np.random.default_rng(11)  # found on the CPU: the chain of 2 strengths never settles
+    j = np.arange(64)
+    opt = rng.integers(0, 64, size=(2, st.nfb, 1))
+    scale = rng.integers(1 << 10, 1 << 14, size=(2, st.nfb, 1))
+    mse = (scale * (64 + (j - opt) ** 2) + rng.integers(0, 1 << 12, size=(2, st.nfb, 64))).astype(np.uint64)
+    skip = (rng.random(st.nfb) < 0.1).astype(np.uint8)
+    assert any(x is None for x in _settle_calls(mse, skip)[1:])
+    mse_t = torch.from_numpy(mse.view(np.int64)).cuda()
+    skip_t = torch.from_numpy(skip).cuda()
+    st.bind_tables(mse_t.data_ptr(), skip_t.data_ptr())
+    torch.cuda.synchronize()
+    oprm, ofbs = oracle.cdef_pick(w, h, mse, skip, ctrls, q, lam)
+    for k in range(12):
+        prm, fbs = st.pick(ctrls, q, lam)
+        assert prm.as_tuple() == oprm.as_tuple() and np.array_equal(fbs, ofbs), ("sync", k)
+    for k in range(12):
+        st.pick_async(ctrls, q, lam)
+        prm, fbs = st.read_params()
+        assert prm.as_tuple() == oprm.as_tuple() and np.array_equal(fbs, ofbs), ("async", k)
+
+
 @pytest.mark.parametrize("persist,fallback", [("0", "persist"), ("0", "steps"), ("1", "persist")])
 def test_cdef_pick_async_vs_oracle(ctx, monkeypatch, persist, fallback):
     """svtgpu_cdef_pick_async (no host wait: the settle check's outcome reaches the later steps through a device flag,

@@ -114,10 +114,11 @@ const char *svtgpu_version(void);
  * svtgpu_tf_*, SvtGpuTfBlock / SvtGpuTfParams / SvtGpuTfPlanes, and its nine RTCD shims; 13: the eight single-reference
  * interpolation shims svtgpu_av1_(highbd_)convolve_*_sr, SvtGpuTfMotion and svtgpu_tf_predict_frame; 14: the temporal
  * filter's sub-pel search svtgpu_tf_search_frame / _read, SvtGpuTfFullpel / SvtGpuTfSearchParams, and the device chain
- * svtgpu_tf_compensate_filter_frame); 15: the diagnostic read-back svtgpu_lr_read_sgr_planes).
+ * svtgpu_tf_compensate_filter_frame); 15: the diagnostic read-back svtgpu_lr_read_sgr_planes; 16: the eight compound
+ * shims svtgpu_av1_(highbd_)jnt_convolve_*, svtgpu_dist_wtd_weights, SvtGpuCompoundBlock and svtgpu_compound_predict_batch).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 15
+#define SVTGPU_ABI_VERSION 16
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1192,8 +1193,8 @@ void svtgpu_tf_get_final_filtered_pixels(int32_t tf_chroma, uint8_t **src_center
  * tf_32x32_inter_prediction (EbTemporalFiltering.c:2230-2580) for every (reference, 64x64 block) of a picture in one launch,
  * bit-exact with the reference's C.  With it the device chain of the temporal filter is: upload the padded reference
  * pictures, svtgpu_tf_predict_frame, svtgpu_tf_filter_frame; the host supplies the per-block motion records only.  The
- * tf_*_sub_pel_search walks are the next section's; ME / HME, the compound (jnt_) and scaled convolves and intrabc stay on
- * the host.
+ * tf_*_sub_pel_search walks are the next section's and the compound (jnt_) convolves the one after; ME / HME, the masked
+ * compounds, the scaled convolves and intrabc stay on the host.
  * ========================================================================================= */
 /* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
  * the 8-tap kernel rows already selected for the phase (av1_get_interp_filter_subpel_kernel of the InterpFilterParams);
@@ -1320,6 +1321,103 @@ int svtgpu_tf_compensate_filter_frame(SvtGpuTfState *state, const SvtGpuTfPlanes
                                       int32_t n_refs, int32_t border_x, int32_t border_y,
                                       const SvtGpuTfParams *filter_params, int32_t sub_sampling_shift,
                                       const SvtGpuTfPlanes *pred, const SvtGpuTfPlanes *out, void *stream);
+
+/* =========================================================================================
+ * AV1 compound (two-reference) inter prediction.  The per-block family svt_av1_jnt_convolve_{2d,x,y,2d_copy} and
+ * svt_av1_highbd_jnt_convolve_* (EbInterPrediction.c:503-677, :861-1040: what the reference's svt_aom_convolve[][][1] /
+ * svt_aom_convolveHbd[][][1] tables hold), the frame-distance weights of COMPOUND_DISTWTD
+ * (svt_av1_dist_wtd_comp_weight_assign, :276-318), and svt_aom_inter_prediction (EbEncInterPrediction.c:4070) with
+ * is_compound = 1 for a list of blocks in one launch, bit-exact with the reference's C.  The masked compounds
+ * (COMPOUND_WEDGE, COMPOUND_DIFFWTD, the blend_a64_* family), inter-intra, warped and scaled references, intrabc and
+ * 12-bit pictures at frame level (the shims handle 12 bits) stay on the host.
+ * ========================================================================================= */
+/* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
+ * the 8-tap kernel rows already selected for the phase, as for the _sr shims; the other arguments are the ConvolveParams
+ * spelt out: round_0 / round_1 (get_conv_params_no_round with is_compound = 1: 3 / 7, at 12 bits 5 / 7; each 0 .. 7),
+ * conv_dst / conv_dst_stride (its dst: CONV_BUF_TYPE, stride in elements >= w), do_average, use_jnt_comp_avg, fwd_offset,
+ * bck_offset.  do_average == 0 writes only conv_dst -- the rounded sum with its 1 << offset_bits bias -- and leaves dst
+ * alone (dst may be null); do_average == 1 reads conv_dst, combines by (tmp + res) >> 1 or, with use_jnt_comp_avg, by
+ * (tmp * fwd_offset + res * bck_offset) >> 4, removes the two offsets, rounds by 14 - round_0 - round_1 and clips to the bit
+ * depth into dst; conv_dst is then left as it was.  Each form reads of src what its C function reads (as the _sr shims).
+ * w, h in {4, 8, 16, 32, 64, 128}; bd 8 for the 8-bit entries, 10 or 12 for the highbd ones.  svtgpu_rtcd.h's adapters carry
+ * the reference's prototypes. */
+void svtgpu_av1_jnt_convolve_2d(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                                int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                                int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride, int32_t do_average,
+                                int32_t use_jnt_comp_avg, int32_t fwd_offset, int32_t bck_offset);
+void svtgpu_av1_jnt_convolve_x(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                               int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                               int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride, int32_t do_average,
+                               int32_t use_jnt_comp_avg, int32_t fwd_offset, int32_t bck_offset);
+void svtgpu_av1_jnt_convolve_y(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                               int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                               int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride, int32_t do_average,
+                               int32_t use_jnt_comp_avg, int32_t fwd_offset, int32_t bck_offset);
+void svtgpu_av1_jnt_convolve_2d_copy(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w,
+                                     int32_t h, const int16_t *filter_x, const int16_t *filter_y, int32_t round_0,
+                                     int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride, int32_t do_average,
+                                     int32_t use_jnt_comp_avg, int32_t fwd_offset, int32_t bck_offset);
+void svtgpu_av1_highbd_jnt_convolve_2d(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                       int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                       int32_t round_0, int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride,
+                                       int32_t do_average, int32_t use_jnt_comp_avg, int32_t fwd_offset,
+                                       int32_t bck_offset, int32_t bd);
+void svtgpu_av1_highbd_jnt_convolve_x(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                      int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                      int32_t round_0, int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride,
+                                      int32_t do_average, int32_t use_jnt_comp_avg, int32_t fwd_offset,
+                                      int32_t bck_offset, int32_t bd);
+void svtgpu_av1_highbd_jnt_convolve_y(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                      int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                      int32_t round_0, int32_t round_1, uint16_t *conv_dst, int32_t conv_dst_stride,
+                                      int32_t do_average, int32_t use_jnt_comp_avg, int32_t fwd_offset,
+                                      int32_t bck_offset, int32_t bd);
+void svtgpu_av1_highbd_jnt_convolve_2d_copy(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride,
+                                            int32_t w, int32_t h, const int16_t *filter_x, const int16_t *filter_y,
+                                            int32_t round_0, int32_t round_1, uint16_t *conv_dst,
+                                            int32_t conv_dst_stride, int32_t do_average, int32_t use_jnt_comp_avg,
+                                            int32_t fwd_offset, int32_t bck_offset, int32_t bd);
+/* The two offsets of COMPOUND_DISTWTD from the frame distances: d0 = |distance from the current frame to the forward
+ * reference|, d1 = |distance to the backward reference| (clamped to MAX_FRAME_DISTANCE = 31 here, as the reference clamps
+ * them), order_idx 0 or 1; the table walk of svt_av1_dist_wtd_comp_weight_assign.  The offsets sum to 16.  Host only.
+ * SVTGPU_ERR_INVALID_ARG: a negative distance, an order_idx outside 0 / 1, a null pointer. */
+int svtgpu_dist_wtd_weights(int32_t d0, int32_t d1, int32_t order_idx, int32_t *fwd_offset, int32_t *bck_offset);
+typedef struct SvtGpuCompoundBlock {      /* one bi-predicted block; 32 bytes */
+    int16_t x, y;                          /* luma position of the block in the picture, multiples of 4 */
+    uint8_t w_log2, h_log2;                /* luma size 8 .. 128; min(w, h) >= 8 (is_comp_ref_allowed), ratio <= 4 */
+    uint8_t ref0, ref1;                    /* indices into refs[] */
+    int16_t mv0_x, mv0_y, mv1_x, mv1_y;    /* 1/8 luma sample */
+    uint8_t filter_x, filter_y;            /* 0 EIGHTTAP_REGULAR, 1 EIGHTTAP_SMOOTH, 2 MULTITAP_SHARP, 3 BILINEAR (dual filter) */
+    uint8_t dist_wtd;                      /* 0 COMPOUND_AVERAGE, 1 COMPOUND_DISTWTD with the two offsets below */
+    uint8_t fwd_offset, bck_offset;        /* as svtgpu_dist_wtd_weights; ignored when dist_wtd == 0 */
+    uint8_t reserved[11];
+} SvtGpuCompoundBlock;
+/* The bi-predicted blocks of one picture in one launch: for every block of blocks[n_blocks] (host memory, copied before
+ * the call returns) the compound predictor from refs[ref0] with (mv0_x, mv0_y) and refs[ref1] with (mv1_x, mv1_y) into
+ * `pred` at the block's position, luma and -- with chroma != 0 -- the two 4:2:0 chroma planes; what svt_aom_inter_prediction
+ * writes with is_compound = 1, COMPOUND_AVERAGE or COMPOUND_DISTWTD, translation, unscaled references, no OBMC and no
+ * inter-intra: its MV clamp (clamp_mv_to_umv_border_sb with the block's own edges), position and phase arithmetic, the
+ * chroma block at ((x >> 3) << 3) / 2, per direction the 4-tap tables when that dimension of the plane's block is <= 4
+ * (av1_get_convolve_filter_params), per plane and reference the copy / x / y / 2-D form by which phases are non-zero.
+ * The sizes are the seventeen AV1 block sizes from 8x8 to 128x128 (128 only beside 64 or 128).  Samples of pred outside
+ * the listed blocks are left alone; blocks that overlap give an unspecified one of their results.
+ * `state` gives the picture size (width and height multiples of 8: the area a block must stay inside) and the grow-only
+ * metadata buffer, as for svtgpu_tf_predict_frame; refs[r].plane[p] points at sample (0, 0) of a padded reference picture
+ * with border_x / border_y (luma samples, chroma halved) readable samples on every side and strides of at least width +
+ * 2 * border_x; pred->plane[p] at sample (0, 0) of the predictor picture, 16-byte aligned with strides of at least the
+ * width and a multiple of 16 bytes.  Every read coordinate is clamped into [-border, size + border - 1], so no MV makes
+ * the kernel read outside the planes; a clamped MV reaches the block's size + 4 + 3 samples out of the plane, so from a
+ * border of the largest listed block's luma size + 14 (142 for 128x128: its 64-wide chroma reaches 71 chroma samples)
+ * the clamp never acts and the result is the reference's.  On edge-replicated borders it is the reference's from any
+ * border.  chroma == 0 leaves planes 1 and 2 unread and unwritten (they may be null).  Bit depth 8 or 10.  Runs in stream
+ * order with no host wait (the call waits only for the previous call's metadata upload on this state).
+ * SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any launch: a null pointer, n_refs < 0, n_blocks < 0,
+ * a bit depth other than 8 or 10, a negative border, a misaligned or too narrow plane, a block that leaves the picture
+ * area or is not at a multiple of 4, a size outside the rule, a ref index >= n_refs, a filter kind above 3, dist_wtd above
+ * 1, offsets that do not sum to 16 when dist_wtd is set.  n_blocks == 0 returns 0 and launches nothing. */
+int svtgpu_compound_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                                  int32_t border_y, const SvtGpuCompoundBlock *blocks, int32_t n_blocks, int32_t bit_depth,
+                                  int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
 
 /* =========================================================================================
  * Loop restoration

@@ -15,6 +15,8 @@
  *         svtgpu_install_resize_rtcd();                   // svt_av1_resize_plane / svt_av1_highbd_resize_plane
  *         svtgpu_install_tf_rtcd();                       // the temporal filter's nine pointers (define
  *                                                         //   SVTGPU_RTCD_WITH_TF before including this header)
+ *         svtgpu_install_compound_rtcd();                 // the eight compound (jnt_) convolves (define
+ *                                                         //   SVTGPU_RTCD_WITH_COMPOUND); same install point as the next
  *         svtgpu_install_interp_rtcd();                   // the eight single-reference convolves (define
  *                                                         //   SVTGPU_RTCD_WITH_INTERP); must precede
  *                                                         //   svt_aom_asm_set_convolve_asm_table(), :1533, which copies them
@@ -464,4 +466,66 @@ static inline int svtgpu_interp_rtcd_installed(int k) {
     }
 }
 #endif /* SVTGPU_RTCD_WITH_INTERP */
+
+/* The compound (two-reference) family (common_dsp_rtcd.h: svt_av1_jnt_convolve_{2d,x,y,2d_copy} and the four
+ * svt_av1_highbd_jnt_convolve_*): eight pointers, the [][][1] half of svt_aom_convolve / svt_aom_convolveHbd.  The adapters
+ * pick the kernel rows as the single-reference ones do and spell the ConvolveParams out: round_0, round_1, dst,
+ * dst_stride, do_average, use_jnt_comp_avg, fwd_offset, bck_offset.  Opt-in: define SVTGPU_RTCD_WITH_COMPOUND before
+ * including this header, in a unit that has included convolve.h.  The install point is svtgpu_install_interp_rtcd's:
+ * after the RTCD setup and BEFORE svt_aom_asm_set_convolve_asm_table() / svt_aom_asm_set_convolve_hbd_asm_table(), which
+ * copy the pointers. */
+#ifdef SVTGPU_RTCD_WITH_COMPOUND
+#define SVTGPU_ADAPT_JNT_CONVOLVE(name)                                                                                    \
+    static void svtgpu_adapt_jnt_convolve_##name(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, \
+                                                 int32_t w, int32_t h, InterpFilterParams *filter_params_x,                \
+                                                 InterpFilterParams *filter_params_y, const int32_t subpel_x_q4,           \
+                                                 const int32_t subpel_y_q4, ConvolveParams *conv_params) {                 \
+        svtgpu_av1_jnt_convolve_##name(                                                                                    \
+            src, src_stride, dst, dst_stride, w, h,                                                                        \
+            filter_params_x ? av1_get_interp_filter_subpel_kernel(*filter_params_x, subpel_x_q4 & SUBPEL_MASK) : NULL,     \
+            filter_params_y ? av1_get_interp_filter_subpel_kernel(*filter_params_y, subpel_y_q4 & SUBPEL_MASK) : NULL,     \
+            conv_params->round_0, conv_params->round_1, conv_params->dst, conv_params->dst_stride, conv_params->do_average, \
+            conv_params->use_jnt_comp_avg, conv_params->fwd_offset, conv_params->bck_offset);                              \
+    }                                                                                                                      \
+    static void svtgpu_adapt_highbd_jnt_convolve_##name(                                                                   \
+        const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride, int32_t w, int32_t h,                  \
+        const InterpFilterParams *filter_params_x, const InterpFilterParams *filter_params_y, const int32_t subpel_x_q4,   \
+        const int32_t subpel_y_q4, ConvolveParams *conv_params, int32_t bd) {                                              \
+        svtgpu_av1_highbd_jnt_convolve_##name(                                                                             \
+            src, src_stride, dst, dst_stride, w, h,                                                                        \
+            filter_params_x ? av1_get_interp_filter_subpel_kernel(*filter_params_x, subpel_x_q4 & SUBPEL_MASK) : NULL,     \
+            filter_params_y ? av1_get_interp_filter_subpel_kernel(*filter_params_y, subpel_y_q4 & SUBPEL_MASK) : NULL,     \
+            conv_params->round_0, conv_params->round_1, conv_params->dst, conv_params->dst_stride, conv_params->do_average, \
+            conv_params->use_jnt_comp_avg, conv_params->fwd_offset, conv_params->bck_offset, bd);                          \
+    }
+SVTGPU_ADAPT_JNT_CONVOLVE(2d)
+SVTGPU_ADAPT_JNT_CONVOLVE(x)
+SVTGPU_ADAPT_JNT_CONVOLVE(y)
+SVTGPU_ADAPT_JNT_CONVOLVE(2d_copy)
+#undef SVTGPU_ADAPT_JNT_CONVOLVE
+static inline void svtgpu_install_compound_rtcd(void) {
+    svt_av1_jnt_convolve_2d             = svtgpu_adapt_jnt_convolve_2d;
+    svt_av1_jnt_convolve_x              = svtgpu_adapt_jnt_convolve_x;
+    svt_av1_jnt_convolve_y              = svtgpu_adapt_jnt_convolve_y;
+    svt_av1_jnt_convolve_2d_copy        = svtgpu_adapt_jnt_convolve_2d_copy;
+    svt_av1_highbd_jnt_convolve_2d      = svtgpu_adapt_highbd_jnt_convolve_2d;
+    svt_av1_highbd_jnt_convolve_x       = svtgpu_adapt_highbd_jnt_convolve_x;
+    svt_av1_highbd_jnt_convolve_y       = svtgpu_adapt_highbd_jnt_convolve_y;
+    svt_av1_highbd_jnt_convolve_2d_copy = svtgpu_adapt_highbd_jnt_convolve_2d_copy;
+}
+/* 1 when pointer i (0..7, the order above) is the library's: the adapters are private to the installing unit */
+static inline int svtgpu_compound_rtcd_bound(int i) {
+    switch (i) {
+    case 0: return svt_av1_jnt_convolve_2d == svtgpu_adapt_jnt_convolve_2d;
+    case 1: return svt_av1_jnt_convolve_x == svtgpu_adapt_jnt_convolve_x;
+    case 2: return svt_av1_jnt_convolve_y == svtgpu_adapt_jnt_convolve_y;
+    case 3: return svt_av1_jnt_convolve_2d_copy == svtgpu_adapt_jnt_convolve_2d_copy;
+    case 4: return svt_av1_highbd_jnt_convolve_2d == svtgpu_adapt_highbd_jnt_convolve_2d;
+    case 5: return svt_av1_highbd_jnt_convolve_x == svtgpu_adapt_highbd_jnt_convolve_x;
+    case 6: return svt_av1_highbd_jnt_convolve_y == svtgpu_adapt_highbd_jnt_convolve_y;
+    case 7: return svt_av1_highbd_jnt_convolve_2d_copy == svtgpu_adapt_highbd_jnt_convolve_2d_copy;
+    default: return 0;
+    }
+}
+#endif /* SVTGPU_RTCD_WITH_COMPOUND */
 #endif /* SVTGPU_RTCD_H */

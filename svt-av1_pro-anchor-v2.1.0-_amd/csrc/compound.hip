@@ -1,0 +1,517 @@
+// compound.hip — AV1 compound (two-reference) inter prediction on gfx950: svt_av1_jnt_convolve_{2d,x,y,2d_copy}_c and
+// svt_av1_highbd_jnt_convolve_*_c (EbInterPrediction.c:503-677, :861-1040) behind eight RTCD shims, and the bi-predicted
+// blocks of a picture (svt_aom_inter_prediction with is_compound = 1, COMPOUND_AVERAGE or COMPOUND_DISTWTD, translation,
+// unscaled references; EbEncInterPrediction.c:4070) as one launch, svtgpu_compound_predict_batch.
+//
+//   unit         four horizontally adjacent outputs of a tile: what one lane computes at a time.  A tile of tw x th outputs
+//                (at most 32 x 32) has tw * th / 4 units; unit u is row u / (tw / 4), columns 4 * (u % (tw / 4)) .. + 3.
+//   tile pass    one reference of one tile: the lanes stage rows -3 .. th + 3 and columns -4 .. tw + 3 of the reference
+//                (every coordinate clamped into the readable border; groups of four columns, one load where no clamp
+//                acts) into the tile's LDS window as 16-bit samples, whose row stride tw + 8 keeps every group of four
+//                8-byte aligned.  The 2-D form then runs the horizontal filter into an int16 LDS intermediate of th + 7
+//                rows; the last step of every form (x, y, copy: from the window; 2-D: from the intermediate) gives a
+//                unit's four CONV_BUF_TYPE values from 8-byte LDS reads.  Each form restates its own C function.
+//   combine      reference 0's values stay in the lane's registers (the same lane owns the same units in both passes, at
+//                most four of them); after reference 1's pass the lane averages or distance-weights, removes the offsets,
+//                rounds, clips and stores four samples with one vector store.  CONV_BUF_TYPE never reaches global memory.
+//   wave item    what one wave does: one tile of 64 or more units, or 64 / units tiles of one shape side by side, lane
+//                l on tile l / units ("slot").  So four 8x8 luma blocks, or the sixteen 4x4 chroma blocks of eight 8x8
+//                blocks, fill a wave.  The host builds the item list while it checks the blocks (it walks them anyway,
+//                and a device-side prefix over tile counts would cost a second launch or a search per workgroup); the
+//                list travels in the state's metadata buffer behind the plane descriptors and the blocks.
+//   workgroup    four waves, four consecutive items; no workgroup barrier, no atomics: a wave's LDS slice is private and
+//                its DS operations complete in order.
+//
+// Bounds.  Reference reads: coordinates clamped into [-border, size + border - 1] of the plane, which the entry's contract
+// makes readable.  Predictor writes: inside the block, which the entry checked against the state's picture area and the
+// strides against that.  blocks[] and refs[] indices are checked on the host.  LDS: slot s of a wave uses window
+// [s * (th + 7) * (tw + 8), + (th + 7) * (tw + 8)) and intermediate [s * (th + 7) * tw, + (th + 7) * tw); the largest are
+// one 32x32 tile (39 * 40 = 1560, 39 * 32 = 1248) and sixteen 4x4 tiles (16 * 132 = 2112, 16 * 44 = 704) <= kWinCap, kImCap.
+#include <cstring>
+#include <vector>
+
+#include "compound_weights.h"
+#include "interp_tables.h"
+#include "svtgpu_internal.h"
+
+static_assert(sizeof(SvtGpuCompoundBlock) == 32, "SvtGpuCompoundBlock is 32 bytes");
+
+namespace {
+
+constexpr int kMaxRefs = 26; // as svtgpu_tf_predict_frame
+constexpr int kTile    = 32;
+constexpr int kWinCap  = 2112, kImCap = 1248, kWaveLds = kWinCap + kImCap; // 16-bit elements per wave
+constexpr int kMaxSlots = 16;
+enum { kCopy = 0, kHorz = 1, kVert = 2, k2d = 3 };
+
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+typedef int16_t  i16x4 __attribute__((ext_vector_type(4)));
+typedef int16_t  i16x8 __attribute__((ext_vector_type(8)));
+typedef uint8_t  u8x4 __attribute__((ext_vector_type(4)));
+template <typename T> struct Vec4;
+template <> struct Vec4<uint8_t> { typedef u8x4 type; };
+template <> struct Vec4<uint16_t> { typedef u16x4 type; };
+
+struct Rounds {
+    int32_t r0, r1, bd;
+};
+
+__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+__device__ __forceinline__ int round_shift(int v, int n) { return (v + ((1 << n) >> 1)) >> n; } // ROUND_POWER_OF_TWO
+__device__ __forceinline__ void wave_lds_sync() { // the wave's LDS stores before its LDS loads (in order within a wave)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ void load_taps(const int16_t *p, int f[8]) { // a 16-byte aligned row of eight taps
+    const i16x8 v = *(const i16x8 *)p;
+#pragma unroll
+    for (int k = 0; k < 8; k++) f[k] = v[k];
+}
+
+// One lane's part of staging a tile's window.  ref points at sample (0, 0) of a plane readable over [x_lo, x_hi] x
+// [y_lo, y_hi]; window row r, column c holds the sample at (sx - 4 + c, sy - 3 + r).  Rows 3 .. th + 2 only when the form
+// has no vertical filter.
+template <typename T>
+__device__ __forceinline__ void stage_window(const T *__restrict__ ref, int stride, int x_lo, int x_hi, int y_lo, int y_hi,
+                                             int sx, int sy, int tw, int th, int mode, uint16_t *win, int li, int lps) {
+    const int ws = tw + 8, g = ws >> 2; // g in {3, 4, 6, 10}
+    const int r_first = (mode & kVert) ? 0 : 3, r_cnt = (mode & kVert) ? th + 7 : th;
+    const int recip = (1 << 20) / g + 1; // u / g, exact for u < 39 * 10 (the error is below u / 2^20 < 1 / g)
+    for (int u = li; u < r_cnt * g; u += lps) {
+        const int rr = (u * recip) >> 20, cg = u - rr * g, row = r_first + rr;
+        const int gy = clamp_i(sy - 3 + row, y_lo, y_hi), gx = sx - 4 + 4 * cg;
+        const T  *p = ref + (ptrdiff_t)gy * stride;
+        u16x4     v;
+        if (gx >= x_lo && gx + 3 <= x_hi) {
+            T t[4];
+            __builtin_memcpy(t, p + gx, sizeof t);
+            v = (u16x4){t[0], t[1], t[2], t[3]};
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = p[clamp_i(gx + k, x_lo, x_hi)];
+        }
+        *(u16x4 *)(win + row * ws + 4 * cg) = v;
+    }
+}
+
+// The 2-D form's horizontal pass (svt_av1_jnt_convolve_2d_c :516-527): window rows 0 .. th + 6 into im[th + 7][tw].
+__device__ __forceinline__ void horizontal_to_im(const uint16_t *win, int16_t *im, int twl, int th, const int fx[8], Rounds cr,
+                                                 int li, int lps) {
+    const int tw = 1 << twl, ws = tw + 8, gl = twl - 2;
+    for (int u = li; u < (th + 7) << gl; u += lps) {
+        const int    rr = u >> gl, x4 = (u & ((1 << gl) - 1)) << 2;
+        const u16x4 *p = (const u16x4 *)(win + rr * ws + x4);
+        const u16x4  a = p[0], b = p[1], c = p[2];
+        const int    s[12] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3], c[0], c[1], c[2], c[3]};
+        i16x4        o;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            int sum = 1 << (cr.bd + 6);
+#pragma unroll
+            for (int k = 0; k < 8; k++) sum += fx[k] * s[j + 1 + k];
+            o[j] = (int16_t)round_shift(sum, cr.r0);
+        }
+        *(i16x4 *)(im + rr * tw + x4) = o;
+    }
+}
+
+// The four CONV_BUF_TYPE values of the unit at row y, columns x4 .. x4 + 3, by the form's own C function: copy
+// (:641-677), x (:599-639), y (:557-597), 2-D's vertical pass (:529-554).  The 2-D and copy forms hold the value in a
+// uint16_t, the x and y forms in an int32_t.
+__device__ __forceinline__ void final_unit(int mode, const uint16_t *win, const int16_t *im, int tw, int y, int x4,
+                                           const int fx[8], const int fy[8], Rounds cr, int res[4]) {
+    const int ws = tw + 8, offset_bits = cr.bd + 14 - cr.r0;
+    const int round_offset = (1 << (offset_bits - cr.r1)) + (1 << (offset_bits - cr.r1 - 1));
+    if (mode == kCopy) {
+        const u16x4 v = *(const u16x4 *)(win + (y + 3) * ws + x4 + 4);
+        const int   bits = 14 - cr.r0 - cr.r1;
+#pragma unroll
+        for (int j = 0; j < 4; j++) res[j] = (uint16_t)((uint16_t)((int)v[j] << bits) + (uint16_t)round_offset);
+    } else if (mode == kHorz) {
+        const u16x4 *p = (const u16x4 *)(win + (y + 3) * ws + x4);
+        const u16x4  a = p[0], b = p[1], c = p[2];
+        const int    s[12] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3], c[0], c[1], c[2], c[3]};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            int sum = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) sum += fx[k] * s[j + 1 + k];
+            res[j] = (1 << (7 - cr.r1)) * round_shift(sum, cr.r0) + round_offset;
+        }
+    } else if (mode == kVert) {
+        int sum[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const u16x4 v = *(const u16x4 *)(win + (y + k) * ws + x4 + 4);
+#pragma unroll
+            for (int j = 0; j < 4; j++) sum[j] += fy[k] * (int)v[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) res[j] = round_shift(sum[j] * (1 << (7 - cr.r0)), cr.r1) + round_offset;
+    } else {
+        int sum[4] = {1 << offset_bits, 1 << offset_bits, 1 << offset_bits, 1 << offset_bits};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const i16x4 v = *(const i16x4 *)(im + (y + k) * tw + x4);
+#pragma unroll
+            for (int j = 0; j < 4; j++) sum[j] += fy[k] * (int)v[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) res[j] = (uint16_t)round_shift(sum[j], cr.r1);
+    }
+}
+
+// the second pass's tail, the same in all eight functions: tmp = the first pass's CONV_BUF_TYPE value
+__device__ __forceinline__ int combine(int tmp, int res, int dist_wtd, int fwd, int bck, Rounds cr) {
+    const int offset_bits = cr.bd + 14 - cr.r0, m = (1 << cr.bd) - 1;
+    tmp = dist_wtd ? (tmp * fwd + res * bck) >> compound_weights::kDistPrecisionBits : (tmp + res) >> 1;
+    tmp -= (1 << (offset_bits - cr.r1)) + (1 << (offset_bits - cr.r1 - 1));
+    const int v = round_shift(tmp, 14 - cr.r0 - cr.r1);
+    return v < 0 ? 0 : v > m ? m : v;
+}
+
+// One reference pass of a tile for one lane: stage, (2-D: horizontal pass,) then emit(i, y, x4, res) for the lane's units
+// u = li + i * lps < units, i < 4.  Every lane of the wave that is in a slot calls it; the lanes of a slot share win / im.
+template <typename T, typename Emit>
+__device__ __forceinline__ void tile_pass(const T *__restrict__ ref, int stride, int x_lo, int x_hi, int y_lo, int y_hi, int sx,
+                                          int sy, int twl, int thl, int mode, const int16_t *fxp, const int16_t *fyp, Rounds cr,
+                                          uint16_t *win, int16_t *im, int li, int lps, Emit emit) {
+    const int tw = 1 << twl, th = 1 << thl, gl = twl - 2, units = 1 << (twl + thl - 2);
+    int       fx[8], fy[8];
+    load_taps(fxp, fx);
+    load_taps(fyp, fy);
+    stage_window<T>(ref, stride, x_lo, x_hi, y_lo, y_hi, sx, sy, tw, th, mode, win, li, lps);
+    wave_lds_sync();
+    if (mode == k2d) horizontal_to_im(win, im, twl, th, fx, cr, li, lps);
+    wave_lds_sync();
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int u = li + i * lps;
+        if (u < units) {
+            const int y = u >> gl, x4 = (u & ((1 << gl) - 1)) << 2;
+            int       res[4];
+            final_unit(mode, win, im, tw, y, x4, fx, fy, cr, res);
+            emit(i, y, x4, res);
+        }
+    }
+    wave_lds_sync(); // this pass's LDS reads before the next pass's stores
+}
+
+// ---------------------------------------------------------------------------------------------
+// the frame kernel
+// ---------------------------------------------------------------------------------------------
+struct CompSlot { // one tile: block, plane, the tile's origin in the block's plane (samples)
+    uint32_t blk;
+    uint8_t  plane, ox, oy, reserved;
+};
+struct CompItem { // one wave's work: nslots tiles of 2^tw_log2 x 2^th_log2 outputs
+    CompSlot slot[kMaxSlots];
+    uint8_t  tw_log2, th_log2, nslots, reserved[13];
+};
+static_assert(sizeof(CompItem) == 144 && sizeof(CompItem) % 16 == 0, "CompItem is 144 bytes");
+struct CompArgs {
+    const SvtGpuTfPlanes      *refs;   // [n_refs]
+    const SvtGpuCompoundBlock *blocks; // [n_blocks]
+    const CompItem            *items;  // [n_items]
+    SvtGpuTfPlanes             pred;
+    int32_t                    n_items, width, height, border_x, border_y, bd;
+};
+
+// av1_get_interp_filter_params_with_block_size: the table of filter kind `kind` for a dimension of `size` samples
+__device__ __forceinline__ int filter_table(int kind, int size) {
+    if (size <= 4 && (kind == kInterpRegular || kind == kInterpSharp)) return kInterpRegular4;
+    if (size <= 4 && kind == kInterpSmooth) return kInterpSmooth4;
+    return kind;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void compound_kernel(const CompArgs a) {
+    __shared__ __attribute__((aligned(16))) uint16_t lds_all[4 * kWaveLds];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int it = blockIdx.x * 4 + wave;
+    if (it >= a.n_items) return;
+    const CompItem &item = a.items[it];
+    const int twl = item.tw_log2, thl = item.th_log2, tw = 1 << twl, th = 1 << thl;
+    const int ul = twl + thl - 2, lpl = ul < 6 ? ul : 6, lps = 1 << lpl, slot = lane >> lpl, li = lane & (lps - 1);
+    if (slot >= item.nslots) return;
+    const CompSlot            sl = item.slot[slot];
+    const SvtGpuCompoundBlock b  = a.blocks[sl.blk];
+    uint16_t *win = lds_all + wave * kWaveLds + slot * ((th + 7) * (tw + 8));
+    int16_t  *im  = (int16_t *)(lds_all + wave * kWaveLds + kWinCap) + slot * ((th + 7) * tw);
+
+    const int    p = sl.plane, ss = p > 0, sc = 1 - ss;
+    const int    bw = 1 << b.w_log2, bh = 1 << b.h_log2, pbw = bw >> ss, pbh = bh >> ss; // the block in luma and in the plane
+    const int    pw = a.width >> ss, ph = a.height >> ss, bdx = a.border_x >> ss, bdy = a.border_y >> ss;
+    // the block's origin in the plane: chroma at ((x >> 3) << 3) / 2 (EbEncInterPrediction.c:4269)
+    const int    px = ss ? ((b.x >> 3) << 3) >> 1 : b.x, py = ss ? ((b.y >> 3) << 3) >> 1 : b.y;
+    const Rounds cr = {3, 7, a.bd}; // get_conv_params_no_round(is_compound = 1) at 8 and 10 bits
+    const int    fxt = filter_table(b.filter_x, pbw), fyt = filter_table(b.filter_y, pbh);
+    typedef typename Vec4<T>::type V4;
+    // the plane by selects, not by a lane-varying index into the kernel arguments (that would put them in scratch)
+    void *const pplane  = p == 0 ? a.pred.plane[0] : p == 1 ? a.pred.plane[1] : a.pred.plane[2];
+    const int   pstride = p == 0 ? a.pred.stride[0] : p == 1 ? a.pred.stride[1] : a.pred.stride[2];
+    T          *dst = (T *)pplane + (size_t)(py + sl.oy) * pstride + px + sl.ox;
+    u16x4 first[4];
+    for (int r = 0; r < 2; r++) {
+        const SvtGpuTfPlanes &rp = a.refs[r ? b.ref1 : b.ref0];
+        // clamp_mv_to_umv_border_sb (:28-48) with the block's own edges, 1/16 sample of the plane
+        int       qx = (int16_t)((r ? b.mv1_x : b.mv0_x) * (1 << sc)), qy = (int16_t)((r ? b.mv1_y : b.mv0_y) * (1 << sc));
+        const int spx = (4 + pbw) << 4, spy = (4 + pbh) << 4;
+        const int lo_x = -(b.x * 8) * (1 << sc) - spx, hi_x = ((a.width - bw - b.x) * 8) * (1 << sc) + spx - 16;
+        const int lo_y = -(b.y * 8) * (1 << sc) - spy, hi_y = ((a.height - bh - b.y) * 8) * (1 << sc) + spy - 16;
+        qx = (int16_t)clamp_i(qx, lo_x, hi_x), qy = (int16_t)clamp_i(qy, lo_y, hi_y);
+        const int phx = qx & 15, phy = qy & 15, mode = (phx ? kHorz : 0) | (phy ? kVert : 0);
+        const int sx = px + (qx >> 4) + sl.ox, sy = py + (qy >> 4) + sl.oy;
+        tile_pass<T>((const T *)rp.plane[p], rp.stride[p], -bdx, pw + bdx - 1, -bdy, ph + bdy - 1, sx, sy, twl, thl, mode,
+                     kInterpFilters[fxt][phx], kInterpFilters[fyt][phy], cr, win, im, li, lps,
+                     [&](int i, int y, int x4, const int res[4]) __attribute__((always_inline)) {
+                         if (r == 0) {
+                             first[i] = (u16x4){(uint16_t)res[0], (uint16_t)res[1], (uint16_t)res[2], (uint16_t)res[3]};
+                         } else {
+                             V4 o;
+#pragma unroll
+                             for (int j = 0; j < 4; j++)
+                                 o[j] = (T)combine(first[i][j], res[j], b.dist_wtd, b.fwd_offset, b.bck_offset, cr);
+                             *(V4 *)(dst + (size_t)y * pstride + x4) = o;
+                         }
+                     });
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the shims' kernel: src is the staged (h + 7) x (w + 7) window (origin at (3, 3)); conv the packed w x h CONV_BUF_TYPE
+// block (written when do_average == 0, read otherwise); dst the packed w x h pixel block.  One wave per tile.
+// ---------------------------------------------------------------------------------------------
+struct JntArgs {
+    const void    *src;
+    uint16_t      *conv;
+    void          *dst;
+    const int16_t *taps; // fx[8], fy[8]
+    int32_t        w, h, mode, do_average, dist_wtd, fwd, bck;
+    Rounds         cr;
+};
+template <typename T>
+__global__ __launch_bounds__(64) void jnt_block_kernel(const JntArgs a) {
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kWaveLds];
+    const int twl = 31 - __clz(a.w < kTile ? a.w : kTile), thl = 31 - __clz(a.h < kTile ? a.h : kTile);
+    const int tw = 1 << twl, th = 1 << thl, ul = twl + thl - 2, lps = ul < 6 ? 1 << ul : 64, li = (int)threadIdx.x;
+    if (li >= lps) return;
+    const int tx = blockIdx.x * tw, ty = blockIdx.y * th, ws = a.w + 7;
+    typedef typename Vec4<T>::type V4;
+    // the window is the whole plane here: size (w + 1) x (h + 1) with a border of 3 spans columns -3 .. w + 3
+    tile_pass<T>((const T *)a.src + 3 * ws + 3, ws, -3, a.w + 3, -3, a.h + 3, tx, ty, twl, thl, a.mode, a.taps, a.taps + 8, a.cr,
+                 lds, (int16_t *)(lds + kWinCap), li, lps, [&](int, int y, int x4, const int res[4]) __attribute__((always_inline)) {
+                     uint16_t *c = a.conv + (size_t)(ty + y) * a.w + tx + x4;
+                     if (!a.do_average) {
+                         *(u16x4 *)c = (u16x4){(uint16_t)res[0], (uint16_t)res[1], (uint16_t)res[2], (uint16_t)res[3]};
+                     } else {
+                         const u16x4 f = *(const u16x4 *)c;
+                         V4          o;
+#pragma unroll
+                         for (int j = 0; j < 4; j++) o[j] = (T)combine(f[j], res[j], a.dist_wtd, a.fwd, a.bck, a.cr);
+                         *(V4 *)((T *)a.dst + (size_t)(ty + y) * a.w + tx + x4) = o;
+                     }
+                 });
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+struct ThreadStage { // the calling thread's staging buffers: grown, never freed per call
+    uint8_t             *d   = nullptr;
+    size_t               cap = 0;
+    std::vector<uint8_t> h;
+};
+thread_local ThreadStage t_stage;
+
+uint8_t *stage_reserve(size_t need, hipStream_t st) {
+    ThreadStage &t = t_stage;
+    if (need > t.cap) {
+        if (t.d) {
+            HIP_OR_DIE(hipStreamSynchronize(st));
+            (void)hipFree(t.d);
+        }
+        need = (need + (need >> 1) + 0xfff) & ~(size_t)0xfff;
+        HIP_OR_DIE(hipMalloc(&t.d, need));
+        t.cap = need;
+    }
+    if (t.h.size() < t.cap) t.h.resize(t.cap);
+    return t.d;
+}
+
+bool size_ok(int v) { return v >= 4 && v <= 128 && !(v & (v - 1)); }
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+template <typename T>
+void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, int w, int h, const int16_t *fx, const int16_t *fy,
+              int round_0, int round_1, uint16_t *conv_dst, int conv_dst_stride, int do_average, int use_jnt_comp_avg,
+              int fwd_offset, int bck_offset, int bd) {
+    if (!src || !conv_dst || (do_average && !dst) || !size_ok(w) || !size_ok(h) || ((mode & kHorz) && !fx) ||
+        ((mode & kVert) && !fy) || (sizeof(T) == 1 ? bd != 8 : (bd != 10 && bd != 12)) || round_0 < 0 || round_0 > 7 ||
+        round_1 < 0 || round_1 > 7 || conv_dst_stride < w)
+        svtgpu_fatal("svtgpu compound convolve shim: bad arguments");
+    const int    ws = w + 7, hs = h + 7;
+    const size_t win = align16((size_t)ws * hs * sizeof(T)), conv = (size_t)w * h * sizeof(uint16_t), out = (size_t)w * h * sizeof(T);
+    const size_t o_taps = win, o_conv = o_taps + 32, o_out = o_conv + align16(conv);
+    hipStream_t  st = svtgpu_shim_stream();
+    uint8_t     *d  = stage_reserve(o_out + out, st);
+    uint8_t     *hb = t_stage.h.data();
+    T           *hw = (T *)hb;
+    // what the reference's C reads of src, and nothing else (as the single-reference shims)
+    memset(hb, 0, o_conv);
+    const int y0 = (mode & kVert) ? -3 : 0, y1 = (mode & kVert) ? h + 4 : h, x0 = (mode & kHorz) ? -3 : 0,
+              x1 = (mode & kHorz) ? w + 4 : w;
+    for (int y = y0; y < y1; y++)
+        memcpy(hw + (size_t)(y + 3) * ws + x0 + 3, src + (ptrdiff_t)y * src_stride + x0, (size_t)(x1 - x0) * sizeof(T));
+    if (fx) memcpy(hb + o_taps, fx, 16);
+    if (fy) memcpy(hb + o_taps + 16, fy, 16);
+    size_t up = o_conv;
+    if (do_average) {
+        for (int y = 0; y < h; y++)
+            memcpy(hb + o_conv + (size_t)y * w * 2, conv_dst + (ptrdiff_t)y * conv_dst_stride, (size_t)w * 2);
+        up = o_conv + conv;
+    }
+    HIP_OR_DIE(hipMemcpyAsync(d, hb, up, hipMemcpyHostToDevice, st));
+    JntArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = d, a.conv = (uint16_t *)(d + o_conv), a.dst = d + o_out, a.taps = (const int16_t *)(d + o_taps);
+    a.w = w, a.h = h, a.mode = mode, a.do_average = do_average, a.dist_wtd = use_jnt_comp_avg, a.fwd = fwd_offset,
+    a.bck = bck_offset, a.cr = {round_0, round_1, bd};
+    const dim3 grid((unsigned)((w + kTile - 1) / kTile), (unsigned)((h + kTile - 1) / kTile));
+    hipLaunchKernelGGL(jnt_block_kernel<T>, grid, dim3(64), 0, st, a);
+    HIP_OR_DIE(hipGetLastError());
+    const size_t o_back = do_average ? o_out : o_conv, n_back = do_average ? out : conv;
+    HIP_OR_DIE(hipMemcpyAsync(hb + o_back, d + o_back, n_back, hipMemcpyDeviceToHost, st));
+    HIP_OR_DIE(hipStreamSynchronize(st));
+    if (do_average)
+        for (int y = 0; y < h; y++)
+            memcpy(dst + (ptrdiff_t)y * dst_stride, (const T *)(hb + o_out) + (size_t)y * w, (size_t)w * sizeof(T));
+    else
+        for (int y = 0; y < h; y++)
+            memcpy(conv_dst + (ptrdiff_t)y * conv_dst_stride, hb + o_conv + (size_t)y * w * 2, (size_t)w * 2);
+}
+
+// the AV1 block sizes a compound may have (is_comp_ref_allowed: min(w, h) >= 8): 8x8 .. 128x128, ratio at most 4, and
+// 128 only beside 64 or 128
+bool block_size_ok(int wl, int hl) {
+    if (wl < 3 || wl > 7 || hl < 3 || hl > 7) return false;
+    const int d = wl > hl ? wl - hl : hl - wl;
+    return d <= 2 && !((wl == 7 || hl == 7) && d > 1);
+}
+
+struct ItemBuilder { // tiles -> wave items; small tiles of one shape gathered, up to 64 / units to an item
+    std::vector<CompItem> items;
+    int                   open[3][3]; // the item still taking slots for tile shape (tw_log2 - 2, th_log2 - 2), or -1
+    ItemBuilder() {
+        for (auto &row : open)
+            for (int &v : row) v = -1;
+    }
+    void add(uint32_t blk, int plane, int ox, int oy, int twl, int thl) {
+        const int units = 1 << (twl + thl - 2), cap = units >= 64 ? 1 : 64 / units;
+        int      *slot_of = cap > 1 && twl <= 4 && thl <= 4 ? &open[twl - 2][thl - 2] : nullptr; // cap > 1 only for shapes up to 16x4 / 8x8 / 4x16
+        int       k = slot_of ? *slot_of : -1;
+        if (k < 0) {
+            CompItem it;
+            memset(&it, 0, sizeof it);
+            it.tw_log2 = (uint8_t)twl, it.th_log2 = (uint8_t)thl;
+            items.push_back(it);
+            k = (int)items.size() - 1;
+        }
+        CompItem &it = items[k];
+        CompSlot &s  = it.slot[it.nslots++];
+        s.blk = blk, s.plane = (uint8_t)plane, s.ox = (uint8_t)ox, s.oy = (uint8_t)oy;
+        if (slot_of) *slot_of = it.nslots < cap ? k : -1;
+    }
+};
+
+} // namespace
+
+extern "C" int svtgpu_dist_wtd_weights(int32_t d0, int32_t d1, int32_t order_idx, int32_t *fwd_offset, int32_t *bck_offset) {
+    return compound_weights::select(d0, d1, order_idx, fwd_offset, bck_offset) ? SVTGPU_OK : SVTGPU_ERR_INVALID_ARG;
+}
+
+extern "C" int svtgpu_compound_predict_batch(SvtGpuTfState *s, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                                             int32_t border_y, const SvtGpuCompoundBlock *blocks, int32_t n_blocks,
+                                             int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream) {
+    if (n_refs > kMaxRefs) return SVTGPU_ERR_UNSUPPORTED;
+    if (!s || !refs || !pred || n_refs < 0 || n_blocks < 0 || (n_blocks && !blocks) || (bit_depth != 8 && bit_depth != 10) ||
+        border_x < 0 || border_y < 0)
+        return SVTGPU_ERR_INVALID_ARG;
+    SvtGpuContext *ctx;
+    int32_t        width, height, blk_cols, nblk;
+    svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
+    const int bs = bit_depth > 8 ? 2 : 1, nplanes = chroma ? 3 : 1; // without chroma planes 1 and 2 are not looked at
+    for (int p = 0; p < nplanes; p++) {
+        const int ss = p > 0;
+        for (int r = 0; r < n_refs; r++)
+            if (!refs[r].plane[p] || ((uintptr_t)refs[r].plane[p] & (bs - 1)) ||
+                refs[r].stride[p] < (width >> ss) + 2 * (border_x >> ss))
+                return SVTGPU_ERR_INVALID_ARG;
+        if (!pred->plane[p] || pred->stride[p] < (width >> ss) || (((size_t)pred->stride[p] * bs) & 15) ||
+            ((uintptr_t)pred->plane[p] & 15))
+            return SVTGPU_ERR_INVALID_ARG;
+    }
+    ItemBuilder build;
+    for (int i = 0; i < n_blocks; i++) {
+        const SvtGpuCompoundBlock &b = blocks[i];
+        if (!block_size_ok(b.w_log2, b.h_log2) || b.x < 0 || b.y < 0 || (b.x & 3) || (b.y & 3) ||
+            b.x + (1 << b.w_log2) > width || b.y + (1 << b.h_log2) > height || b.ref0 >= n_refs || b.ref1 >= n_refs ||
+            b.filter_x > 3 || b.filter_y > 3 || b.dist_wtd > 1 ||
+            (b.dist_wtd && b.fwd_offset + b.bck_offset != (1 << compound_weights::kDistPrecisionBits)))
+            return SVTGPU_ERR_INVALID_ARG;
+        for (int p = 0; p < nplanes; p++) {
+            const int pwl = b.w_log2 - (p > 0), phl = b.h_log2 - (p > 0), twl = pwl < 5 ? pwl : 5, thl = phl < 5 ? phl : 5;
+            for (int oy = 0; oy < (1 << phl); oy += 1 << thl)
+                for (int ox = 0; ox < (1 << pwl); ox += 1 << twl) build.add((uint32_t)i, p, ox, oy, twl, thl);
+        }
+    }
+    if (!n_blocks) return SVTGPU_OK;
+    hipStream_t  st = pick_stream(ctx, stream);
+    const size_t n_items = build.items.size();
+    const size_t o_blk = align16((size_t)n_refs * sizeof(SvtGpuTfPlanes)), o_item = o_blk + (size_t)n_blocks * sizeof(SvtGpuCompoundBlock);
+    const size_t total = o_item + n_items * sizeof(CompItem);
+    uint8_t     *hm, *dm;
+    if (int rc = svtgpu_tf_meta_begin(s, total, &hm, &dm)) return rc;
+    memcpy(hm, refs, (size_t)n_refs * sizeof(SvtGpuTfPlanes));
+    memcpy(hm + o_blk, blocks, (size_t)n_blocks * sizeof(SvtGpuCompoundBlock));
+    memcpy(hm + o_item, build.items.data(), n_items * sizeof(CompItem));
+    if (int rc = svtgpu_tf_meta_upload(s, total, st)) return rc;
+    CompArgs a;
+    memset(&a, 0, sizeof a);
+    a.refs = (const SvtGpuTfPlanes *)dm, a.blocks = (const SvtGpuCompoundBlock *)(dm + o_blk);
+    a.items = (const CompItem *)(dm + o_item), a.pred = *pred, a.n_items = (int32_t)n_items;
+    a.width = width, a.height = height, a.border_x = border_x, a.border_y = border_y, a.bd = bit_depth;
+    const dim3 grid((unsigned)((n_items + 3) / 4));
+    if (bit_depth == 8)
+        hipLaunchKernelGGL(compound_kernel<uint8_t>, grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(compound_kernel<uint16_t>, grid, dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return SVTGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// RTCD shims: host pointers, synchronous.  svtgpu_rtcd.h's adapters, compiled inside the encoder, select the kernel rows
+// from the reference's InterpFilterParams and spell its ConvolveParams out.
+// ---------------------------------------------------------------------------------------------
+#define SVTGPU_JNT_SHIM(name, mode)                                                                                          \
+    extern "C" void svtgpu_av1_jnt_convolve_##name(                                                                          \
+        const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w, int32_t h,                      \
+        const int16_t *filter_x, const int16_t *filter_y, int32_t round_0, int32_t round_1, uint16_t *conv_dst,              \
+        int32_t conv_dst_stride, int32_t do_average, int32_t use_jnt_comp_avg, int32_t fwd_offset, int32_t bck_offset) {     \
+        shim_jnt<uint8_t>(mode, src, src_stride, dst, dst_stride, w, h, filter_x, filter_y, round_0, round_1, conv_dst,      \
+                          conv_dst_stride, do_average, use_jnt_comp_avg, fwd_offset, bck_offset, 8);                         \
+    }                                                                                                                        \
+    extern "C" void svtgpu_av1_highbd_jnt_convolve_##name(                                                                   \
+        const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride, int32_t w, int32_t h,                    \
+        const int16_t *filter_x, const int16_t *filter_y, int32_t round_0, int32_t round_1, uint16_t *conv_dst,              \
+        int32_t conv_dst_stride, int32_t do_average, int32_t use_jnt_comp_avg, int32_t fwd_offset, int32_t bck_offset,       \
+        int32_t bd) {                                                                                                        \
+        shim_jnt<uint16_t>(mode, src, src_stride, dst, dst_stride, w, h, filter_x, filter_y, round_0, round_1, conv_dst,     \
+                           conv_dst_stride, do_average, use_jnt_comp_avg, fwd_offset, bck_offset, bd);                       \
+    }
+SVTGPU_JNT_SHIM(2d, k2d)
+SVTGPU_JNT_SHIM(x, kHorz)
+SVTGPU_JNT_SHIM(y, kVert)
+SVTGPU_JNT_SHIM(2d_copy, kCopy)

@@ -336,6 +336,32 @@ assert ctypes.sizeof(TfFullpel) == 352 and ctypes.sizeof(TfSearchParams) == 40 a
 _I16P = ctypes.POINTER(ctypes.c_int16)
 _CONVOLVE_SR = [_P, _I32, _P, _I32, _I32, _I32, _I16P, _I16P, _I32, _I32]
 INTERP_FORMS = ("2d_sr", "x_sr", "y_sr", "2d_copy_sr")
+_U16P = ctypes.POINTER(ctypes.c_uint16)
+# ... conv_dst, conv_dst_stride, do_average, use_jnt_comp_avg, fwd_offset, bck_offset
+_CONVOLVE_JNT = _CONVOLVE_SR + [_P, _I32, _I32, _I32, _I32, _I32]
+COMPOUND_FORMS = ("2d_copy", "x", "y", "2d")  # by (phase_x != 0) | (phase_y != 0) << 1
+
+
+class CompoundBlock(ctypes.Structure):
+    """Mirror of SvtGpuCompoundBlock: one bi-predicted block, 32 bytes."""
+    _fields_ = [("x", ctypes.c_int16), ("y", ctypes.c_int16), ("w_log2", ctypes.c_uint8), ("h_log2", ctypes.c_uint8),
+                ("ref0", ctypes.c_uint8), ("ref1", ctypes.c_uint8), ("mv0_x", ctypes.c_int16), ("mv0_y", ctypes.c_int16),
+                ("mv1_x", ctypes.c_int16), ("mv1_y", ctypes.c_int16), ("filter_x", ctypes.c_uint8),
+                ("filter_y", ctypes.c_uint8), ("dist_wtd", ctypes.c_uint8), ("fwd_offset", ctypes.c_uint8),
+                ("bck_offset", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 11)]
+
+    @classmethod
+    def make(cls, x, y, w, h, ref0, ref1, mv0, mv1, filter_x, filter_y, dist_wtd=0, fwd_offset=0, bck_offset=0):
+        """w, h: luma size in samples (powers of two); mv0 / mv1 (x, y) in 1/8 luma sample."""
+        b = cls()
+        b.x, b.y, b.w_log2, b.h_log2 = int(x), int(y), int(w).bit_length() - 1, int(h).bit_length() - 1
+        b.ref0, b.ref1, b.mv0_x, b.mv0_y, b.mv1_x, b.mv1_y = int(ref0), int(ref1), int(mv0[0]), int(mv0[1]), int(mv1[0]), int(mv1[1])
+        b.filter_x, b.filter_y, b.dist_wtd = int(filter_x), int(filter_y), int(dist_wtd)
+        b.fwd_offset, b.bck_offset = int(fwd_offset), int(bck_offset)
+        return b
+
+
+assert ctypes.sizeof(CompoundBlock) == 32
 
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
@@ -496,6 +522,12 @@ _SIGS = {
     "svtgpu_interp_tables": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I32)]),
     "svtgpu_tf_predict_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32, ctypes.POINTER(TfMotion),
                                                _I32, _I32, ctypes.POINTER(TfPlanes), _P]),
+    **{"svtgpu_av1_jnt_convolve_" + f: (None, _CONVOLVE_JNT) for f in COMPOUND_FORMS},
+    **{"svtgpu_av1_highbd_jnt_convolve_" + f: (None, _CONVOLVE_JNT + [_I32]) for f in COMPOUND_FORMS},
+    "svtgpu_dist_wtd_weights": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+    "svtgpu_compound_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
+                                                     ctypes.POINTER(CompoundBlock), _I32, _I32, _I32,
+                                                     ctypes.POINTER(TfPlanes), _P]),
     "svtgpu_tf_search_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                               ctypes.POINTER(TfFullpel), ctypes.POINTER(TfSearchParams), _P]),
     "svtgpu_tf_search_read": (ctypes.c_int, [_P, _I32, ctypes.POINTER(TfMotion), ctypes.POINTER(TfBlock), _P]),
@@ -1607,6 +1639,14 @@ class TfState:
         check(lib().svtgpu_tf_predict_frame(self.h, ra if n else None, n, int(border_x), int(border_y), ma if n else None,
                                             int(bit_depth), int(tf_chroma), pa if n else None, stream))
 
+    def compound_predict_batch(self, refs, border_x, border_y, blocks, bit_depth, chroma, pred, stream=None):
+        """svtgpu_compound_predict_batch: refs a list of TfPlanes at sample (0, 0) of the padded pictures; blocks a list of
+        CompoundBlock; pred one TfPlanes, the predictor picture."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (CompoundBlock * max(nb, 1))(*blocks)
+        check(lib().svtgpu_compound_predict_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, int(bit_depth),
+                                                  int(chroma), ctypes.byref(pred), stream))
+
     def search_frame(self, centre, refs, border_x, border_y, fullpel, params, stream=None):
         """centre: TfPlanes (luma read); refs: a list of TfPlanes at sample (0, 0) of the padded pictures; fullpel: a list
         of TfFullpel, [reference][block] flattened; params: TfSearchParams.  The records stay on the device."""
@@ -1652,6 +1692,31 @@ def convolve_sr(form, src, x0, y0, w, h, filter_x, filter_y, round_0, round_1, b
     dp = dst.ctypes.data + (dy0 * dst.strides[0] + dx0 * dst.itemsize)
     args = [sp, src.strides[0] // src.itemsize, dp, dst.strides[0] // dst.itemsize, int(w), int(h), fx, fy, int(round_0),
             int(round_1)]
+    fn(*(args + [int(bd)] if hbd else args))
+
+
+def dist_wtd_weights(d0, d1, order_idx):
+    """svtgpu_dist_wtd_weights: (fwd_offset, bck_offset) of COMPOUND_DISTWTD from the two frame distances (host only)."""
+    f, b = _I32(0), _I32(0)
+    check(lib().svtgpu_dist_wtd_weights(int(d0), int(d1), int(order_idx), ctypes.byref(f), ctypes.byref(b)))
+    return int(f.value), int(b.value)
+
+
+def jnt_convolve(form, src, x0, y0, w, h, filter_x, filter_y, round_0, round_1, bd, conv_dst, do_average, dist_wtd=0,
+                 fwd_offset=0, bck_offset=0, dst=None, dx0=0, dy0=0):
+    """One of the eight compound shims (form in COMPOUND_FORMS): the w x h block at (x0, y0) of the host array `src`
+    (uint8 at bd 8, else uint16) with the uint16 array `conv_dst` as ConvolveParams::dst (block at its (0, 0)); with
+    do_average the pixels land in `dst` at (dx0, dy0), in place."""
+    hbd = src.dtype == np.uint16
+    fn = getattr(lib(), ("svtgpu_av1_highbd_jnt_convolve_" if hbd else "svtgpu_av1_jnt_convolve_") + form)
+    fx = (ctypes.c_int16 * 8)(*[int(v) for v in filter_x])
+    fy = (ctypes.c_int16 * 8)(*[int(v) for v in filter_y])
+    assert conv_dst.dtype == np.uint16 and (dst is None or dst.dtype == src.dtype)
+    sp = src.ctypes.data + (y0 * src.strides[0] + x0 * src.itemsize)
+    dp = None if dst is None else dst.ctypes.data + (dy0 * dst.strides[0] + dx0 * dst.itemsize)
+    args = [sp, src.strides[0] // src.itemsize, dp, 0 if dst is None else dst.strides[0] // dst.itemsize, int(w), int(h), fx,
+            fy, int(round_0), int(round_1), conv_dst.ctypes.data, conv_dst.strides[0] // 2, int(do_average), int(dist_wtd),
+            int(fwd_offset), int(bck_offset)]
     fn(*(args + [int(bd)] if hbd else args))
 
 

@@ -115,10 +115,12 @@ const char *svtgpu_version(void);
  * interpolation shims svtgpu_av1_(highbd_)convolve_*_sr, SvtGpuTfMotion and svtgpu_tf_predict_frame; 14: the temporal
  * filter's sub-pel search svtgpu_tf_search_frame / _read, SvtGpuTfFullpel / SvtGpuTfSearchParams, and the device chain
  * svtgpu_tf_compensate_filter_frame); 15: the diagnostic read-back svtgpu_lr_read_sgr_planes; 16: the eight compound
- * shims svtgpu_av1_(highbd_)jnt_convolve_*, svtgpu_dist_wtd_weights, SvtGpuCompoundBlock and svtgpu_compound_predict_batch).
+ * shims svtgpu_av1_(highbd_)jnt_convolve_*, svtgpu_dist_wtd_weights, SvtGpuCompoundBlock and svtgpu_compound_predict_batch; 17: the masked compounds: the three shims
+ * svtgpu_av1_build_compound_diffwtd_mask_d16 / svtgpu_aom_(lowbd|highbd)_blend_a64_d16_mask, svtgpu_wedge_mask,
+ * SvtGpuMaskedCompoundBlock and svtgpu_masked_compound_predict_batch).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 16
+#define SVTGPU_ABI_VERSION 17
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1193,8 +1195,8 @@ void svtgpu_tf_get_final_filtered_pixels(int32_t tf_chroma, uint8_t **src_center
  * tf_32x32_inter_prediction (EbTemporalFiltering.c:2230-2580) for every (reference, 64x64 block) of a picture in one launch,
  * bit-exact with the reference's C.  With it the device chain of the temporal filter is: upload the padded reference
  * pictures, svtgpu_tf_predict_frame, svtgpu_tf_filter_frame; the host supplies the per-block motion records only.  The
- * tf_*_sub_pel_search walks are the next section's and the compound (jnt_) convolves the one after; ME / HME, the masked
- * compounds, the scaled convolves and intrabc stay on the host.
+ * tf_*_sub_pel_search walks are the next section's, the compound (jnt_) convolves the one after and the masked compounds the
+ * one after that; ME / HME, the scaled convolves and intrabc stay on the host.
  * ========================================================================================= */
 /* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
  * the 8-tap kernel rows already selected for the phase (av1_get_interp_filter_subpel_kernel of the InterpFilterParams);
@@ -1328,8 +1330,8 @@ int svtgpu_tf_compensate_filter_frame(SvtGpuTfState *state, const SvtGpuTfPlanes
  * svt_aom_convolveHbd[][][1] tables hold), the frame-distance weights of COMPOUND_DISTWTD
  * (svt_av1_dist_wtd_comp_weight_assign, :276-318), and svt_aom_inter_prediction (EbEncInterPrediction.c:4070) with
  * is_compound = 1 for a list of blocks in one launch, bit-exact with the reference's C.  The masked compounds
- * (COMPOUND_WEDGE, COMPOUND_DIFFWTD, the blend_a64_* family), inter-intra, warped and scaled references, intrabc and
- * 12-bit pictures at frame level (the shims handle 12 bits) stay on the host.
+ * (COMPOUND_WEDGE, COMPOUND_DIFFWTD) are the next section's; inter-intra, OBMC blending, warped and scaled references,
+ * intrabc and 12-bit pictures at frame level (the shims handle 12 bits) stay on the host.
  * ========================================================================================= */
 /* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
  * the 8-tap kernel rows already selected for the phase, as for the _sr shims; the other arguments are the ConvolveParams
@@ -1418,6 +1420,72 @@ typedef struct SvtGpuCompoundBlock {      /* one bi-predicted block; 32 bytes */
 int svtgpu_compound_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
                                   int32_t border_y, const SvtGpuCompoundBlock *blocks, int32_t n_blocks, int32_t bit_depth,
                                   int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
+
+/* =========================================================================================
+ * AV1 masked compound inter prediction: COMPOUND_WEDGE and COMPOUND_DIFFWTD, the other two of the four inter-inter
+ * compound types.  The DIFFWTD mask svt_av1_build_compound_diffwtd_mask_d16 (C_DEFAULT/EbInterPrediction_c.c:15-40), the
+ * blends svt_aom_lowbd_blend_a64_d16_mask / svt_aom_highbd_blend_a64_d16_mask (EbBlend_a64_mask.c:34-195), the wedge masks
+ * of svt_av1_init_wedge_masks (EbInterPrediction.c:1445-2132), and svt_aom_inter_prediction with a masked compound type
+ * (reference 1 through av1_make_masked_scaled_inter_predictor, EbEncInterPrediction.c:50-164) for a list of blocks,
+ * bit-exact with the reference's C.  Inter-intra (it needs intra prediction), OBMC blending, warped and scaled
+ * references, the encoder's wedge / DIFFWTD search (pick_wedge, svt_av1_wedge_sse_from_residuals) and 12-bit pictures at
+ * frame level stay on the host.
+ * ========================================================================================= */
+/* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread; the ConvolveParams spelt
+ * out as round_0 / round_1 (each 0 .. 7, their sum at most 14).  w, h in {4, 8, 16, 32, 64, 128}; strides in elements.
+ * The mask shim writes mask[h][w] packed with stride w, as the reference does: m = min(38 + (|src0 - src1| rounded by
+ * 14 - round_0 - round_1 + bd - 8) / 16, 64), or 64 - m for mask_type 1 (DIFFWTD_38_INV); bd 8, 10 or 12.  The blend shims
+ * write dst = clip(round(((m * src0 + (64 - m) * src1) >> 6) - the two offsets, 14 - round_0 - round_1)) with m the mask
+ * value (subw = subh = 0), the rounded mean of a 2x2 (1, 1), or AOM_BLEND_AVG of a horizontal (1, 0) or vertical (0, 1)
+ * pair; they read (h << subh) rows of (w << subw) mask bytes, mask_stride >= w << subw.  src0 / src1 may alias dst (all
+ * reads happen first).  bd 8 for the lowbd entry; 8, 10 or 12 for the highbd one, whose dst is the uint16_t block behind a
+ * uint8_t pointer, as in the reference.  svtgpu_rtcd.h's adapters carry the reference's prototypes. */
+void svtgpu_av1_build_compound_diffwtd_mask_d16(uint8_t *mask, int32_t mask_type, const uint16_t *src0, int32_t src0_stride,
+                                                const uint16_t *src1, int32_t src1_stride, int32_t h, int32_t w,
+                                                int32_t round_0, int32_t round_1, int32_t bd);
+void svtgpu_aom_lowbd_blend_a64_d16_mask(uint8_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride,
+                                         const uint16_t *src1, uint32_t src1_stride, const uint8_t *mask,
+                                         uint32_t mask_stride, int32_t w, int32_t h, int32_t subw, int32_t subh,
+                                         int32_t round_0, int32_t round_1);
+void svtgpu_aom_highbd_blend_a64_d16_mask(uint8_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride,
+                                          const uint16_t *src1, uint32_t src1_stride, const uint8_t *mask,
+                                          uint32_t mask_stride, int32_t w, int32_t h, int32_t subw, int32_t subh,
+                                          int32_t round_0, int32_t round_1, int32_t bd);
+/* The wedge mask svt_aom_get_contiguous_soft_mask(wedge_index, wedge_sign, bsize) of a w x h block into mask[h][w], stride
+ * w (csrc/wedge_masks.h).  Host only.  SVTGPU_ERR_INVALID_ARG: a size without wedges (they exist for 8x8, 8x16, 16x8, 16x16,
+ * 16x32, 32x16, 32x32, 8x32, 32x8), an index outside 0 .. 15, a sign outside 0 / 1, a null pointer. */
+int svtgpu_wedge_mask(int32_t w, int32_t h, int32_t wedge_index, int32_t wedge_sign, uint8_t *mask);
+typedef struct SvtGpuMaskedCompoundBlock { /* one masked bi-predicted block; 32 bytes; the first 18 as SvtGpuCompoundBlock */
+    int16_t x, y;                          /* luma position of the block in the picture, multiples of 4 */
+    uint8_t w_log2, h_log2;                /* luma size 8 .. 128; min(w, h) >= 8, ratio <= 4; wedge: 8 .. 32 each way */
+    uint8_t ref0, ref1;                    /* indices into refs[] */
+    int16_t mv0_x, mv0_y, mv1_x, mv1_y;    /* 1/8 luma sample */
+    uint8_t filter_x, filter_y;            /* 0 EIGHTTAP_REGULAR, 1 EIGHTTAP_SMOOTH, 2 MULTITAP_SHARP, 3 BILINEAR (dual filter) */
+    uint8_t comp_type;                     /* 0 COMPOUND_WEDGE, 1 COMPOUND_DIFFWTD */
+    uint8_t wedge_index, wedge_sign;       /* 0 .. 15, 0 / 1; checked for both types, used by COMPOUND_WEDGE */
+    uint8_t mask_type;                     /* 0 DIFFWTD_38, 1 DIFFWTD_38_INV; checked for both types, used by COMPOUND_DIFFWTD */
+    uint8_t reserved[10];                  /* must be zero */
+} SvtGpuMaskedCompoundBlock;
+/* The masked bi-predicted blocks of one picture: for every block of blocks[n_blocks] (host memory, copied before the call
+ * returns) the predictor from refs[ref0] with (mv0_x, mv0_y) and refs[ref1] with (mv1_x, mv1_y), blended per sample by the
+ * block's wedge mask or by the DIFFWTD mask made from the two luma predictions, into `pred` at the block's position, luma
+ * and -- with chroma != 0 -- the two 4:2:0 chroma planes, whose mask values are the rounded means of the luma mask's 2x2s;
+ * what svt_aom_inter_prediction writes with is_compound = 1 and COMPOUND_WEDGE or COMPOUND_DIFFWTD, translation, unscaled
+ * references, no OBMC and no inter-intra.  Everything svtgpu_compound_predict_batch documents holds here word for word:
+ * the MV clamp, position and phase arithmetic, the chroma block at ((x >> 3) << 3) / 2, the 4-tap tables for a dimension
+ * <= 4, the form per plane and reference, the seventeen sizes, `state`, refs, pred, the readable border and the read clamp
+ * (from a border of the largest listed block's luma size + 14 the result is the reference's; on edge-replicated borders
+ * from any border), chroma == 0, bit depth 8 or 10, samples outside the listed blocks left alone, overlapping blocks
+ * unspecified.  Runs in stream order with no host wait: one launch, and a second one behind it in the same stream for the
+ * chroma of the DIFFWTD blocks, which reads the masks their luma left in a plane of `state` (width x height bytes,
+ * allocated at the first such call).  Calls on one state must therefore be queued on one stream, or ordered by the caller.
+ * SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any launch: every refusal of
+ * svtgpu_compound_predict_batch that does not concern dist_wtd, and comp_type above 1, a wedge block whose size has no
+ * wedges, wedge_index above 15, wedge_sign above 1, mask_type above 1, a non-zero reserved byte.  n_blocks == 0 returns 0
+ * and launches nothing. */
+int svtgpu_masked_compound_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                                         int32_t border_y, const SvtGpuMaskedCompoundBlock *blocks, int32_t n_blocks,
+                                         int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
 
 /* =========================================================================================
  * Loop restoration

@@ -15,6 +15,8 @@
  *         svtgpu_install_resize_rtcd();                   // svt_av1_resize_plane / svt_av1_highbd_resize_plane
  *         svtgpu_install_tf_rtcd();                       // the temporal filter's nine pointers (define
  *                                                         //   SVTGPU_RTCD_WITH_TF before including this header)
+ *         svtgpu_install_masked_compound_rtcd();          // the DIFFWTD mask and the two blend_a64_d16_mask (define
+ *                                                         // SVTGPU_RTCD_WITH_MASKED_COMPOUND first)
  *         svtgpu_install_compound_rtcd();                 // the eight compound (jnt_) convolves (define
  *                                                         //   SVTGPU_RTCD_WITH_COMPOUND); same install point as the next
  *         svtgpu_install_interp_rtcd();                   // the eight single-reference convolves (define
@@ -528,4 +530,45 @@ static inline int svtgpu_compound_rtcd_bound(int i) {
     }
 }
 #endif /* SVTGPU_RTCD_WITH_COMPOUND */
+/* The masked compound family (common_dsp_rtcd.h: svt_av1_build_compound_diffwtd_mask_d16, svt_aom_lowbd_blend_a64_d16_mask,
+ * svt_aom_highbd_blend_a64_d16_mask): three pointers, what av1_make_masked_scaled_inter_predictor and
+ * svt_aom_build_masked_compound_no_round call for COMPOUND_DIFFWTD and COMPOUND_WEDGE.  The adapters spell the
+ * ConvolveParams out as round_0, round_1.  Opt-in: define SVTGPU_RTCD_WITH_MASKED_COMPOUND before including this header, in a
+ * unit that has included convolve.h.  Install after the RTCD setup; nothing copies these pointers. */
+#ifdef SVTGPU_RTCD_WITH_MASKED_COMPOUND
+static void svtgpu_adapt_build_compound_diffwtd_mask_d16(uint8_t *mask, DIFFWTD_MASK_TYPE mask_type, const CONV_BUF_TYPE *src0,
+                                                         int src0_stride, const CONV_BUF_TYPE *src1, int src1_stride, int h,
+                                                         int w, ConvolveParams *conv_params, int bd) {
+    svtgpu_av1_build_compound_diffwtd_mask_d16(mask, (int32_t)mask_type, src0, src0_stride, src1, src1_stride, h, w,
+                                               conv_params->round_0, conv_params->round_1, bd);
+}
+static void svtgpu_adapt_lowbd_blend_a64_d16_mask(uint8_t *dst, uint32_t dst_stride, const CONV_BUF_TYPE *src0,
+                                                  uint32_t src0_stride, const CONV_BUF_TYPE *src1, uint32_t src1_stride,
+                                                  const uint8_t *mask, uint32_t mask_stride, int w, int h, int subw, int subh,
+                                                  ConvolveParams *conv_params) {
+    svtgpu_aom_lowbd_blend_a64_d16_mask(dst, dst_stride, src0, src0_stride, src1, src1_stride, mask, mask_stride, w, h, subw,
+                                        subh, conv_params->round_0, conv_params->round_1);
+}
+static void svtgpu_adapt_highbd_blend_a64_d16_mask(uint8_t *dst, uint32_t dst_stride, const CONV_BUF_TYPE *src0,
+                                                   uint32_t src0_stride, const CONV_BUF_TYPE *src1, uint32_t src1_stride,
+                                                   const uint8_t *mask, uint32_t mask_stride, int w, int h, int subx, int suby,
+                                                   ConvolveParams *conv_params, const int bd) {
+    svtgpu_aom_highbd_blend_a64_d16_mask(dst, dst_stride, src0, src0_stride, src1, src1_stride, mask, mask_stride, w, h, subx,
+                                         suby, conv_params->round_0, conv_params->round_1, bd);
+}
+static inline void svtgpu_install_masked_compound_rtcd(void) {
+    svt_av1_build_compound_diffwtd_mask_d16 = svtgpu_adapt_build_compound_diffwtd_mask_d16;
+    svt_aom_lowbd_blend_a64_d16_mask        = svtgpu_adapt_lowbd_blend_a64_d16_mask;
+    svt_aom_highbd_blend_a64_d16_mask       = svtgpu_adapt_highbd_blend_a64_d16_mask;
+}
+/* 1 when pointer i (0..2, the order above) is the library's: the adapters are private to the installing unit */
+static inline int svtgpu_masked_compound_rtcd_bound(int i) {
+    switch (i) {
+    case 0: return svt_av1_build_compound_diffwtd_mask_d16 == svtgpu_adapt_build_compound_diffwtd_mask_d16;
+    case 1: return svt_aom_lowbd_blend_a64_d16_mask == svtgpu_adapt_lowbd_blend_a64_d16_mask;
+    case 2: return svt_aom_highbd_blend_a64_d16_mask == svtgpu_adapt_highbd_blend_a64_d16_mask;
+    default: return 0;
+    }
+}
+#endif /* SVTGPU_RTCD_WITH_MASKED_COMPOUND */
 #endif /* SVTGPU_RTCD_H */

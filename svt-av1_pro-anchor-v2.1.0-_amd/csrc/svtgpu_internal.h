@@ -220,6 +220,8 @@ int    svtgpu_tf_err64_launch(SvtGpuTfState *s, const SvtGpuTfPlanes *centre, co
 int    svtgpu_tf_records_reserve(SvtGpuTfState *s, int n_refs, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks);
 void   svtgpu_tf_records_commit(SvtGpuTfState *s, int n_refs); // the count _get reports: set once a search is queued
 int    svtgpu_tf_records_get(SvtGpuTfState *s, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks); // the last search's n_refs
+// the state's DIFFWTD mask plane (width x height bytes, stride width) for masked_compound.hip; allocated on first use
+int    svtgpu_tf_mask_reserve(SvtGpuTfState *s, uint8_t **mask);
 
 // Diagnostics (SVTGPU_WGCLK=<file>, never on by default): per workgroup 8 words -- up to 6 time marks on the 100 MHz
 // s_memrealtime clock (slot 0 = start; the kernel's phases after it; unused slots stay 0) and the hardware id words

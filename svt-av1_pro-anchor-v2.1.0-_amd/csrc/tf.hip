@@ -549,6 +549,7 @@ struct SvtGpuTfState {
     uint8_t       *d_records;       // the search's records: [refs][nblk] SvtGpuTfMotion, then [refs][nblk] SvtGpuTfBlock
     int32_t        cap_records;     // in references; only grows
     int32_t        search_refs;     // the references of the last search
+    uint8_t       *d_mask;          // the masked compound's DIFFWTD luma masks: width x height bytes, allocated on first use
 };
 
 namespace {
@@ -638,6 +639,16 @@ int svtgpu_tf_records_reserve(SvtGpuTfState *s, int n_refs, SvtGpuTfMotion **mot
     *blocks = (SvtGpuTfBlock *)(s->d_records + (size_t)n_refs * s->nblk * sizeof(SvtGpuTfMotion));
     return SVTGPU_OK;
 }
+// The DIFFWTD mask plane of svtgpu_masked_compound_predict_batch (masked_compound.hip): one byte per luma sample of the
+// state's picture, stride width.  Allocated once, so no call queued on the state ever sees it move.
+int svtgpu_tf_mask_reserve(SvtGpuTfState *s, uint8_t **mask) {
+    if (!s->d_mask && hipMalloc(&s->d_mask, (size_t)s->width * s->height) != hipSuccess) {
+        s->d_mask = nullptr;
+        return SVTGPU_ERR_OOM;
+    }
+    *mask = s->d_mask;
+    return SVTGPU_OK;
+}
 void svtgpu_tf_records_commit(SvtGpuTfState *s, int n_refs) { s->search_refs = n_refs; }
 int  svtgpu_tf_records_get(SvtGpuTfState *s, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks) {
     *motion = (SvtGpuTfMotion *)s->d_records;
@@ -702,6 +713,7 @@ extern "C" void svtgpu_tf_state_destroy(SvtGpuTfState *s) {
     if (s->d_meta) (void)hipFree(s->d_meta);
     if (s->h_meta) (void)hipHostFree(s->h_meta);
     if (s->d_records) (void)hipFree(s->d_records);
+    if (s->d_mask) (void)hipFree(s->d_mask);
     (void)hipFree(s->d_noise);
     delete s;
 }

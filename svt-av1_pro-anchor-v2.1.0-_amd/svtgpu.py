@@ -363,6 +363,29 @@ class CompoundBlock(ctypes.Structure):
 
 assert ctypes.sizeof(CompoundBlock) == 32
 
+
+class MaskedCompoundBlock(ctypes.Structure):
+    """Mirror of SvtGpuMaskedCompoundBlock: one masked bi-predicted block, 32 bytes; the first 18 as CompoundBlock."""
+    _fields_ = [("x", ctypes.c_int16), ("y", ctypes.c_int16), ("w_log2", ctypes.c_uint8), ("h_log2", ctypes.c_uint8),
+                ("ref0", ctypes.c_uint8), ("ref1", ctypes.c_uint8), ("mv0_x", ctypes.c_int16), ("mv0_y", ctypes.c_int16),
+                ("mv1_x", ctypes.c_int16), ("mv1_y", ctypes.c_int16), ("filter_x", ctypes.c_uint8),
+                ("filter_y", ctypes.c_uint8), ("comp_type", ctypes.c_uint8), ("wedge_index", ctypes.c_uint8),
+                ("wedge_sign", ctypes.c_uint8), ("mask_type", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 10)]
+
+    @classmethod
+    def make(cls, x, y, w, h, ref0, ref1, mv0, mv1, filter_x, filter_y, comp_type, wedge_index=0, wedge_sign=0, mask_type=0):
+        """w, h: luma size in samples (powers of two); mv0 / mv1 (x, y) in 1/8 luma sample; comp_type 0 COMPOUND_WEDGE,
+        1 COMPOUND_DIFFWTD."""
+        b = cls()
+        b.x, b.y, b.w_log2, b.h_log2 = int(x), int(y), int(w).bit_length() - 1, int(h).bit_length() - 1
+        b.ref0, b.ref1, b.mv0_x, b.mv0_y, b.mv1_x, b.mv1_y = int(ref0), int(ref1), int(mv0[0]), int(mv0[1]), int(mv1[0]), int(mv1[1])
+        b.filter_x, b.filter_y, b.comp_type = int(filter_x), int(filter_y), int(comp_type)
+        b.wedge_index, b.wedge_sign, b.mask_type = int(wedge_index), int(wedge_sign), int(mask_type)
+        return b
+
+
+assert ctypes.sizeof(MaskedCompoundBlock) == 32 and MaskedCompoundBlock.filter_y.offset == CompoundBlock.filter_y.offset
+
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
     "svtgpu_version": (ctypes.c_char_p, []),
@@ -528,6 +551,15 @@ _SIGS = {
     "svtgpu_compound_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                                      ctypes.POINTER(CompoundBlock), _I32, _I32, _I32,
                                                      ctypes.POINTER(TfPlanes), _P]),
+    "svtgpu_av1_build_compound_diffwtd_mask_d16": (None, [_P, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "svtgpu_aom_lowbd_blend_a64_d16_mask": (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P,
+                                                   ctypes.c_uint32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "svtgpu_aom_highbd_blend_a64_d16_mask": (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P,
+                                                    ctypes.c_uint32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "svtgpu_wedge_mask": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P]),
+    "svtgpu_masked_compound_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
+                                                            ctypes.POINTER(MaskedCompoundBlock), _I32, _I32, _I32,
+                                                            ctypes.POINTER(TfPlanes), _P]),
     "svtgpu_tf_search_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                               ctypes.POINTER(TfFullpel), ctypes.POINTER(TfSearchParams), _P]),
     "svtgpu_tf_search_read": (ctypes.c_int, [_P, _I32, ctypes.POINTER(TfMotion), ctypes.POINTER(TfBlock), _P]),
@@ -1647,6 +1679,13 @@ class TfState:
         check(lib().svtgpu_compound_predict_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, int(bit_depth),
                                                   int(chroma), ctypes.byref(pred), stream))
 
+    def masked_compound_predict_batch(self, refs, border_x, border_y, blocks, bit_depth, chroma, pred, stream=None):
+        """svtgpu_masked_compound_predict_batch: as compound_predict_batch, on a list of MaskedCompoundBlock."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (MaskedCompoundBlock * max(nb, 1))(*blocks)
+        check(lib().svtgpu_masked_compound_predict_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, int(bit_depth),
+                                                         int(chroma), ctypes.byref(pred), stream))
+
     def search_frame(self, centre, refs, border_x, border_y, fullpel, params, stream=None):
         """centre: TfPlanes (luma read); refs: a list of TfPlanes at sample (0, 0) of the padded pictures; fullpel: a list
         of TfFullpel, [reference][block] flattened; params: TfSearchParams.  The records stay on the device."""
@@ -1718,6 +1757,37 @@ def jnt_convolve(form, src, x0, y0, w, h, filter_x, filter_y, round_0, round_1, 
             fy, int(round_0), int(round_1), conv_dst.ctypes.data, conv_dst.strides[0] // 2, int(do_average), int(dist_wtd),
             int(fwd_offset), int(bck_offset)]
     fn(*(args + [int(bd)] if hbd else args))
+
+
+def wedge_mask(w, h, wedge_index, wedge_sign):
+    """svtgpu_wedge_mask: the w x h wedge mask as a uint8 array [h][w] (host only)."""
+    m = np.zeros((int(h), int(w)), np.uint8)
+    check(lib().svtgpu_wedge_mask(int(w), int(h), int(wedge_index), int(wedge_sign), m.ctypes.data))
+    return m
+
+
+def diffwtd_mask(mask_type, src0, src1, w, h, round_0, round_1, bd):
+    """svtgpu_av1_build_compound_diffwtd_mask_d16 on the top-left w x h of the uint16 arrays src0 / src1 (any strides): the
+    packed uint8 mask [h][w]."""
+    assert src0.dtype == np.uint16 and src1.dtype == np.uint16
+    m = np.zeros((int(h), int(w)), np.uint8)
+    lib().svtgpu_av1_build_compound_diffwtd_mask_d16(m.ctypes.data, int(mask_type), src0.ctypes.data, src0.strides[0] // 2,
+                                                     src1.ctypes.data, src1.strides[0] // 2, int(h), int(w), int(round_0),
+                                                     int(round_1), int(bd))
+    return m
+
+
+def blend_a64_d16_mask(dst, dx0, dy0, src0, src1, mask, w, h, subw, subh, round_0, round_1, bd):
+    """svtgpu_aom_lowbd_blend_a64_d16_mask (dst uint8) or svtgpu_aom_highbd_blend_a64_d16_mask (dst uint16): the w x h block
+    into `dst` at (dx0, dy0), in place, from the top-left corners of the uint16 arrays src0 / src1 and the uint8 mask."""
+    assert src0.dtype == np.uint16 and src1.dtype == np.uint16 and mask.dtype == np.uint8
+    dp = dst.ctypes.data + dy0 * dst.strides[0] + dx0 * dst.itemsize
+    args = [dp, dst.strides[0] // dst.itemsize, src0.ctypes.data, src0.strides[0] // 2, src1.ctypes.data, src1.strides[0] // 2,
+            mask.ctypes.data, mask.strides[0], int(w), int(h), int(subw), int(subh), int(round_0), int(round_1)]
+    if dst.dtype == np.uint16:
+        lib().svtgpu_aom_highbd_blend_a64_d16_mask(*(args + [int(bd)]))
+    else:
+        lib().svtgpu_aom_lowbd_blend_a64_d16_mask(*args)
 
 
 def declared_symbols(header=HEADER_PATH):

@@ -117,10 +117,12 @@ const char *svtgpu_version(void);
  * svtgpu_tf_compensate_filter_frame); 15: the diagnostic read-back svtgpu_lr_read_sgr_planes; 16: the eight compound
  * shims svtgpu_av1_(highbd_)jnt_convolve_*, svtgpu_dist_wtd_weights, SvtGpuCompoundBlock and svtgpu_compound_predict_batch; 17: the masked compounds: the three shims
  * svtgpu_av1_build_compound_diffwtd_mask_d16 / svtgpu_aom_(lowbd|highbd)_blend_a64_d16_mask, svtgpu_wedge_mask,
- * SvtGpuMaskedCompoundBlock and svtgpu_masked_compound_predict_batch).
+ * SvtGpuMaskedCompoundBlock and svtgpu_masked_compound_predict_batch; 18: warped motion: the two shims
+ * svtgpu_av1_warp_affine / svtgpu_av1_highbd_warp_affine, svtgpu_warp_shear_params, svtgpu_warp_filter_table, SvtGpuWarpBlock
+ * and svtgpu_warp_predict_batch).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 17
+#define SVTGPU_ABI_VERSION 18
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -1486,6 +1488,76 @@ typedef struct SvtGpuMaskedCompoundBlock { /* one masked bi-predicted block; 32 
 int svtgpu_masked_compound_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
                                          int32_t border_y, const SvtGpuMaskedCompoundBlock *blocks, int32_t n_blocks,
                                          int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
+
+/* =========================================================================================
+ * AV1 warped-motion (affine) inter prediction: svt_av1_warp_affine / svt_av1_highbd_warp_affine (EbWarpedMotion.c:570, :822),
+ * the shear parameters of svt_get_shear_params (:1082-1105), and svt_aom_warped_motion_prediction
+ * (EbEncInterPrediction.c:2747) for a list of blocks, bit-exact with the reference's C.  What stays on the host: finding the
+ * model (svt_find_projection, svt_aom_select_samples, the global motion search), the chroma of blocks below 16 in a
+ * dimension (chroma_plane_warped_motion_prediction_sub8x8, a translation), masked compounds over warped predictors
+ * (av1_make_masked_warp_inter_predictor), inter-intra, OBMC blending, scaled references, and 12-bit pictures at frame level.
+ * ========================================================================================= */
+/* svt_get_shear_params on the six model values wmmat (as svt_warp_plane passes them): 1 and abgd = {alpha, beta, gamma,
+ * delta} when the model is valid (wmmat[2] > 0) and 4 |alpha| + 7 |beta| < 65536, 4 |gamma| + 4 |delta| < 65536; 0
+ * otherwise.  Host only.  SVTGPU_ERR_INVALID_ARG: a null pointer. */
+int svtgpu_warp_shear_params(const int32_t wmmat[6], int16_t abgd[4]);
+/* The library's warped filter table (the AV1 specification's Warped_Filters): *table points at int16_t[*rows][8], rows = 193,
+ * static storage.  Host only.  SVTGPU_ERR_INVALID_ARG: a null pointer. */
+int svtgpu_warp_filter_table(const int16_t **table, int32_t *rows);
+/* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread; the ConvolveParams spelt
+ * out: round_0, round_1, is_compound, conv_dst / conv_dst_stride (ConvolveParams::dst, ::dst_stride), do_average,
+ * use_jnt_comp_avg, fwd_offset, bck_offset.  Every other argument is the reference's.  The three output modes are the C's:
+ * is_compound == 0 writes pred = clip(round(sum, 14 - reduce_bits_horiz) - (1 << (bd - 1)) - (1 << bd)); is_compound with
+ * do_average == 0 writes only conv_dst (pred is not looked at and may be null); is_compound with do_average == 1 reads
+ * conv_dst, combines by (tmp + sum) >> 1 or, with use_jnt_comp_avg, (tmp * fwd_offset + sum * bck_offset) >> 4, removes the
+ * two offsets, rounds by 14 - round_0 - round_1, clips into pred and leaves conv_dst as it was.  Every read of the reference
+ * plane is clamped to [0, height - 1] x [0, width - 1].  The highbd form keeps the split reference of this encoder: sample =
+ * (ref8b << 2) | ((ref2b >> 6) & 3), two strides; bd 10 or 12; reduce_bits_horiz = round_0 + max(bd + 7 - round_0 - 14, 0).
+ * Unlike the other shims these return a code: 0, or SVTGPU_ERR_INVALID_ARG with nothing launched and nothing written for a
+ * p_width or p_height that is not a multiple of 8 from 8 to 128 (the AVX2 forms assume the same and every encoder call
+ * satisfies it), a null pointer that the mode reads or writes, a stride below its width, subsampling outside 0 / 1, a bd
+ * the entry does not take, rounds outside 0 .. 7 or summing above 14, do_average without is_compound, shear parameters
+ * outside the two limits above (the filter table has no row for them), or a model whose projection of a unit's centre
+ * leaves int32 (undefined in the C).  svtgpu_rtcd.h's adapters carry the reference's prototypes and abort on a refusal. */
+int svtgpu_av1_warp_affine(const int32_t *mat, const uint8_t *ref, int32_t width, int32_t height, int32_t stride, uint8_t *pred,
+                           int32_t p_col, int32_t p_row, int32_t p_width, int32_t p_height, int32_t p_stride,
+                           int32_t subsampling_x, int32_t subsampling_y, int32_t round_0, int32_t round_1, int32_t is_compound,
+                           uint16_t *conv_dst, int32_t conv_dst_stride, int32_t do_average, int32_t use_jnt_comp_avg,
+                           int32_t fwd_offset, int32_t bck_offset, int16_t alpha, int16_t beta, int16_t gamma, int16_t delta);
+int svtgpu_av1_highbd_warp_affine(const int32_t *mat, const uint8_t *ref8b, const uint8_t *ref2b, int32_t width, int32_t height,
+                                  int32_t stride8b, int32_t stride2b, uint16_t *pred, int32_t p_col, int32_t p_row,
+                                  int32_t p_width, int32_t p_height, int32_t p_stride, int32_t subsampling_x,
+                                  int32_t subsampling_y, int32_t bd, int32_t round_0, int32_t round_1, int32_t is_compound,
+                                  uint16_t *conv_dst, int32_t conv_dst_stride, int32_t do_average, int32_t use_jnt_comp_avg,
+                                  int32_t fwd_offset, int32_t bck_offset, int16_t alpha, int16_t beta, int16_t gamma,
+                                  int16_t delta);
+typedef struct SvtGpuWarpBlock {          /* one warped block; 64 bytes */
+    int16_t x, y;                          /* luma position, multiples of 8 */
+    uint8_t w_log2, h_log2;                /* luma size 8 .. 128, min(w, h) >= 8, an AV1 block size */
+    uint8_t ref0, ref1;                    /* indices into refs[]; ref1 == 0xFF: one reference */
+    uint8_t dist_wtd, fwd_offset, bck_offset, reserved0;   /* as SvtGpuCompoundBlock; ignored with one reference */
+    int32_t wmmat0[6], wmmat1[6];          /* as svt_warp_plane passes them (ROTZOOM: [5] = [2], [4] = -[3] set by the caller) */
+    uint8_t reserved[4];
+} SvtGpuWarpBlock;
+/* The warped blocks of one picture in one launch: for every block of blocks[n_blocks] (host memory, copied before the call
+ * returns) what svt_aom_warped_motion_prediction writes with no masked compound: the luma of every block, warped from
+ * refs[ref0] by wmmat0 -- and, with ref1 != 0xFF, from refs[ref1] by wmmat1, the two averaged or distance-weighted as in
+ * svtgpu_compound_predict_batch -- and, with chroma != 0, the two 4:2:0 chroma planes (subsampling_x = subsampling_y = 1, the
+ * block at (x / 2, y / 2)) of the blocks with w >= 16 and h >= 16.  A smaller block gets LUMA ONLY: its chroma is a
+ * translation in the reference (chroma_plane_warped_motion_prediction_sub8x8) and is not part of this call.  `state`, the
+ * plane formats, the pred alignment rules, stream order, n_blocks == 0 and overlapping blocks are
+ * svtgpu_compound_predict_batch's, word for word.  There is no border argument: the warp clamps every read row to
+ * [0, height - 1] and every column to [0, width - 1] of the reference plane (chroma: the halved dimensions), so
+ * refs[r].plane[p] points at sample (0, 0) of a plane with a stride of at least the plane's width and nothing outside the
+ * visible picture is read.  The host computes alpha, beta, gamma, delta per reference (svtgpu_warp_shear_params).
+ * SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any launch: a null pointer, n_refs < 0, n_blocks < 0, a
+ * bit depth other than 8 or 10, a misaligned or too narrow plane, a block that leaves the picture area or is not at a
+ * multiple of 8, a size outside the rule, ref0 >= n_refs, a ref1 that is neither 0xFF nor below n_refs, with two references
+ * dist_wtd above 1 or offsets that do not sum to 16 when it is set, a model that svtgpu_warp_shear_params does not return 1
+ * for, a model for which wmmat[2] * x + wmmat[3] * y + wmmat[0] (or the other row), evaluated in 64 bits at the centres of
+ * the block's corner units, leaves int32. */
+int svtgpu_warp_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, const SvtGpuWarpBlock *blocks,
+                              int32_t n_blocks, int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
 
 /* =========================================================================================
  * Loop restoration

@@ -17,6 +17,8 @@
  *                                                         //   SVTGPU_RTCD_WITH_TF before including this header)
  *         svtgpu_install_masked_compound_rtcd();          // the DIFFWTD mask and the two blend_a64_d16_mask (define
  *                                                         // SVTGPU_RTCD_WITH_MASKED_COMPOUND first)
+ *         svtgpu_install_warp_rtcd();                     // svt_av1_warp_affine / svt_av1_highbd_warp_affine (define
+ *                                                         //   SVTGPU_RTCD_WITH_WARP first)
  *         svtgpu_install_compound_rtcd();                 // the eight compound (jnt_) convolves (define
  *                                                         //   SVTGPU_RTCD_WITH_COMPOUND); same install point as the next
  *         svtgpu_install_interp_rtcd();                   // the eight single-reference convolves (define
@@ -571,4 +573,46 @@ static inline int svtgpu_masked_compound_rtcd_bound(int i) {
     }
 }
 #endif /* SVTGPU_RTCD_WITH_MASKED_COMPOUND */
+/* Warped motion (common_dsp_rtcd.h: svt_av1_warp_affine, svt_av1_highbd_warp_affine): two pointers, what svt_warp_plane /
+ * svt_highbd_warp_plane call.  The adapters spell the ConvolveParams out; the shims refuse what the C cannot do (a p_width
+ * or p_height that is no multiple of 8, a projection that leaves int32) with a code, which a void pointer cannot carry, so
+ * the adapters abort on it.  Opt-in: define SVTGPU_RTCD_WITH_WARP before including this header, in a unit that has included
+ * convolve.h.  Install after the RTCD setup; nothing copies these pointers. */
+#ifdef SVTGPU_RTCD_WITH_WARP
+#include <stdlib.h>
+static void svtgpu_adapt_warp_affine(const int32_t *mat, const uint8_t *ref, int width, int height, int stride, uint8_t *pred,
+                                     int p_col, int p_row, int p_width, int p_height, int p_stride, int subsampling_x,
+                                     int subsampling_y, ConvolveParams *conv_params, int16_t alpha, int16_t beta, int16_t gamma,
+                                     int16_t delta) {
+    if (svtgpu_av1_warp_affine(mat, ref, width, height, stride, pred, p_col, p_row, p_width, p_height, p_stride, subsampling_x,
+                               subsampling_y, conv_params->round_0, conv_params->round_1, conv_params->is_compound,
+                               conv_params->dst, conv_params->dst_stride, conv_params->do_average, conv_params->use_jnt_comp_avg,
+                               conv_params->fwd_offset, conv_params->bck_offset, alpha, beta, gamma, delta))
+        abort();
+}
+static void svtgpu_adapt_highbd_warp_affine(const int32_t *mat, const uint8_t *ref8b, const uint8_t *ref2b, int width, int height,
+                                            int stride8b, int stride2b, uint16_t *pred, int p_col, int p_row, int p_width,
+                                            int p_height, int p_stride, int subsampling_x, int subsampling_y, int bd,
+                                            ConvolveParams *conv_params, int16_t alpha, int16_t beta, int16_t gamma,
+                                            int16_t delta) {
+    if (svtgpu_av1_highbd_warp_affine(mat, ref8b, ref2b, width, height, stride8b, stride2b, pred, p_col, p_row, p_width, p_height,
+                                      p_stride, subsampling_x, subsampling_y, bd, conv_params->round_0, conv_params->round_1,
+                                      conv_params->is_compound, conv_params->dst, conv_params->dst_stride, conv_params->do_average,
+                                      conv_params->use_jnt_comp_avg, conv_params->fwd_offset, conv_params->bck_offset, alpha, beta,
+                                      gamma, delta))
+        abort();
+}
+static inline void svtgpu_install_warp_rtcd(void) {
+    svt_av1_warp_affine        = svtgpu_adapt_warp_affine;
+    svt_av1_highbd_warp_affine = svtgpu_adapt_highbd_warp_affine;
+}
+/* 1 when pointer i (0..1, the order above) is the library's: the adapters are private to the installing unit */
+static inline int svtgpu_warp_rtcd_bound(int i) {
+    switch (i) {
+    case 0: return svt_av1_warp_affine == svtgpu_adapt_warp_affine;
+    case 1: return svt_av1_highbd_warp_affine == svtgpu_adapt_highbd_warp_affine;
+    default: return 0;
+    }
+}
+#endif /* SVTGPU_RTCD_WITH_WARP */
 #endif /* SVTGPU_RTCD_H */

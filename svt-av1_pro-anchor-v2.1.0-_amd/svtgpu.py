@@ -386,6 +386,27 @@ class MaskedCompoundBlock(ctypes.Structure):
 
 assert ctypes.sizeof(MaskedCompoundBlock) == 32 and MaskedCompoundBlock.filter_y.offset == CompoundBlock.filter_y.offset
 
+class WarpBlock(ctypes.Structure):
+    """Mirror of SvtGpuWarpBlock: one warped block, 64 bytes."""
+    _fields_ = [("x", ctypes.c_int16), ("y", ctypes.c_int16), ("w_log2", ctypes.c_uint8), ("h_log2", ctypes.c_uint8),
+                ("ref0", ctypes.c_uint8), ("ref1", ctypes.c_uint8), ("dist_wtd", ctypes.c_uint8),
+                ("fwd_offset", ctypes.c_uint8), ("bck_offset", ctypes.c_uint8), ("reserved0", ctypes.c_uint8),
+                ("wmmat0", ctypes.c_int32 * 6), ("wmmat1", ctypes.c_int32 * 6), ("reserved", ctypes.c_uint8 * 4)]
+
+    @classmethod
+    def make(cls, x, y, w, h, ref0, wmmat0, ref1=0xFF, wmmat1=None, dist_wtd=0, fwd_offset=0, bck_offset=0):
+        """w, h: luma size in samples (powers of two); wmmat0 / wmmat1: six model values each; ref1 0xFF: one reference."""
+        b = cls()
+        b.x, b.y, b.w_log2, b.h_log2 = int(x), int(y), int(w).bit_length() - 1, int(h).bit_length() - 1
+        b.ref0, b.ref1, b.dist_wtd, b.fwd_offset, b.bck_offset = int(ref0), int(ref1), int(dist_wtd), int(fwd_offset), int(bck_offset)
+        for k in range(6):
+            b.wmmat0[k] = int(wmmat0[k])
+            b.wmmat1[k] = int(wmmat1[k]) if wmmat1 is not None else 0
+        return b
+
+
+assert ctypes.sizeof(WarpBlock) == 64 and WarpBlock.wmmat0.offset == 12 and WarpBlock.wmmat1.offset == 36
+
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
     "svtgpu_version": (ctypes.c_char_p, []),
@@ -560,6 +581,12 @@ _SIGS = {
     "svtgpu_masked_compound_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                                             ctypes.POINTER(MaskedCompoundBlock), _I32, _I32, _I32,
                                                             ctypes.POINTER(TfPlanes), _P]),
+    "svtgpu_warp_shear_params": (ctypes.c_int, [_P, _P]),
+    "svtgpu_warp_filter_table": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I32)]),
+    "svtgpu_av1_warp_affine": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P] + [_I32] * 10 + [_P] + [_I32] * 5 + [ctypes.c_int16] * 4),
+    "svtgpu_av1_highbd_warp_affine": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P] + [_I32] * 11 + [_P] + [_I32] * 5 +
+                                      [ctypes.c_int16] * 4),
+    "svtgpu_warp_predict_batch": (ctypes.c_int, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P]),
     "svtgpu_tf_search_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                               ctypes.POINTER(TfFullpel), ctypes.POINTER(TfSearchParams), _P]),
     "svtgpu_tf_search_read": (ctypes.c_int, [_P, _I32, ctypes.POINTER(TfMotion), ctypes.POINTER(TfBlock), _P]),
@@ -1686,6 +1713,13 @@ class TfState:
         check(lib().svtgpu_masked_compound_predict_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, int(bit_depth),
                                                          int(chroma), ctypes.byref(pred), stream))
 
+    def warp_predict_batch(self, refs, blocks, bit_depth, chroma, pred, stream=None):
+        """svtgpu_warp_predict_batch: refs a list of TfPlanes at sample (0, 0) of the reference pictures (no border is read);
+        blocks a list of WarpBlock; pred one TfPlanes, the predictor picture."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (WarpBlock * max(nb, 1))(*blocks)
+        check(lib().svtgpu_warp_predict_batch(self.h, ra, n, ba, nb, int(bit_depth), int(chroma), ctypes.byref(pred), stream))
+
     def search_frame(self, centre, refs, border_x, border_y, fullpel, params, stream=None):
         """centre: TfPlanes (luma read); refs: a list of TfPlanes at sample (0, 0) of the padded pictures; fullpel: a list
         of TfFullpel, [reference][block] flattened; params: TfSearchParams.  The records stay on the device."""
@@ -1788,6 +1822,43 @@ def blend_a64_d16_mask(dst, dx0, dy0, src0, src1, mask, w, h, subw, subh, round_
         lib().svtgpu_aom_highbd_blend_a64_d16_mask(*(args + [int(bd)]))
     else:
         lib().svtgpu_aom_lowbd_blend_a64_d16_mask(*args)
+
+
+def warp_filter_table():
+    """svtgpu_warp_filter_table: the library's warped filter table as an int16 array [193][8] (host only)."""
+    t, n = _P(), _I32(0)
+    check(lib().svtgpu_warp_filter_table(ctypes.byref(t), ctypes.byref(n)))
+    return np.ctypeslib.as_array(ctypes.cast(t, _I16P), (n.value, 8)).copy()
+
+
+def warp_shear_params(wmmat):
+    """svtgpu_warp_shear_params: (the reference's return value 1 / 0, [alpha, beta, gamma, delta]) of six model values."""
+    m, o = (ctypes.c_int32 * 6)(*[int(v) for v in wmmat]), (ctypes.c_int16 * 4)()
+    rc = lib().svtgpu_warp_shear_params(m, o)
+    if rc < 0:
+        check(rc)
+    return rc, [int(v) for v in o]
+
+
+def warp_affine(mat, ref, ref2b, pred, px0, py0, p_col, p_row, p_width, p_height, ss_x, ss_y, bd, round_0, round_1, is_compound,
+                conv_dst, do_average, dist_wtd, fwd_offset, bck_offset, abgd):
+    """svtgpu_av1_warp_affine (ref2b None: ref a uint8 plane) or svtgpu_av1_highbd_warp_affine (ref the uint8 plane of the
+    high bits, ref2b that of the low two): the p_width x p_height block into `pred` at (px0, py0) and / or the uint16 array
+    `conv_dst` (block at its (0, 0)), in place.  Returns the shim's code."""
+    m = (ctypes.c_int32 * 6)(*[int(v) for v in mat])
+    pp = None if pred is None else pred.ctypes.data + py0 * pred.strides[0] + px0 * pred.itemsize
+    ps = 0 if pred is None else pred.strides[0] // pred.itemsize
+    cp = None if conv_dst is None else conv_dst.ctypes.data
+    cs = 0 if conv_dst is None else conv_dst.strides[0] // 2
+    tail = [int(round_0), int(round_1), int(is_compound), cp, cs, int(do_average), int(dist_wtd), int(fwd_offset), int(bck_offset)] + \
+           [int(v) for v in abgd]
+    h, w = ref.shape
+    if ref2b is None:
+        return lib().svtgpu_av1_warp_affine(m, ref.ctypes.data, w, h, ref.strides[0], pp, int(p_col), int(p_row), int(p_width),
+                                            int(p_height), ps, int(ss_x), int(ss_y), *tail)
+    return lib().svtgpu_av1_highbd_warp_affine(m, ref.ctypes.data, ref2b.ctypes.data, w, h, ref.strides[0], ref2b.strides[0], pp,
+                                               int(p_col), int(p_row), int(p_width), int(p_height), ps, int(ss_x), int(ss_y),
+                                               int(bd), *tail)
 
 
 def declared_symbols(header=HEADER_PATH):

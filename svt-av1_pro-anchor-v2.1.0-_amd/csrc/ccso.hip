@@ -774,19 +774,17 @@ __global__ __launch_bounds__(256) void ccso_dist_kernel(const uint16_t *org, int
     atomicAdd(out, ssd);
 }
 
-// a device copy of host [base + lo, base + hi) (element units); dev() = the device address of base
-template <typename T> struct Span {
-    T        *d = nullptr;
-    ptrdiff_t lo = 0, n = 0;
-    Span(const T *base, ptrdiff_t lo_, ptrdiff_t hi, hipStream_t st) : lo(lo_), n(hi - lo_) {
-        HIP_OR_DIE(hipMalloc(&d, (size_t)n * sizeof(T)));
-        HIP_OR_DIE(hipMemcpyAsync(d, base + lo, (size_t)n * sizeof(T), hipMemcpyHostToDevice, st));
-    }
-    T   *dev() const { return d - lo; }
-    void back(T *base, hipStream_t st) const {
-        HIP_OR_DIE(hipMemcpyAsync(base + lo, d, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st));
-    }
-    ~Span() { (void)hipFree(d); }
+// host [base + lo, base + hi) (element units) as a region of the thread's stage: add() carves it, and once the call's
+// stage is reserved up() copies it there, dev() is the device address of base, back() copies it home
+template <typename T> struct Region {
+    T        *base;
+    ptrdiff_t lo, n;
+    size_t    off;
+    Region(Carver &c, const T *base_, ptrdiff_t lo_, ptrdiff_t hi)
+        : base((T *)base_), lo(lo_), n(hi - lo_), off(c((size_t)(hi - lo_) * sizeof(T))) {}
+    void up(const SvtGpuStageLease &sg, hipStream_t st) const { sg.up(off, base + lo, (size_t)n * sizeof(T), st); }
+    T   *dev(const SvtGpuStageLease &sg) const { return sg.dev<T>(off) - lo; }
+    void back(const SvtGpuStageLease &sg, hipStream_t st) const { sg.down(base + lo, off, (size_t)n * sizeof(T), st); }
 };
 
 // the span [lo, hi) of the classifier's reads: every sample of the block and its two support neighbours
@@ -811,17 +809,19 @@ extern "C" uint64_t svtgpu_compute_distortion_block(const uint16_t *org, const i
     const int bs = 1 << log2_filter_unit_size;
     const int yo = y + bs >= height ? height - y : bs, xo = x + bs >= width ? width - x : bs;
     if (yo <= 0 || xo <= 0) return 0;
-    hipStream_t         st = svtgpu_shim_stream();
-    Span<uint16_t>      so(org, x, (ptrdiff_t)org_stride * (yo - 1) + x + xo, st);
-    Span<uint16_t>      sr(rec16, x, (ptrdiff_t)rec_stride * (yo - 1) + x + xo, st);
-    unsigned long long *d_out, h_out = 0;
-    HIP_OR_DIE(hipMalloc(&d_out, sizeof(d_out[0])));
+    hipStream_t            st = svtgpu_shim_stream();
+    Carver                 c;
+    const Region<uint16_t> so(c, org, x, (ptrdiff_t)org_stride * (yo - 1) + x + xo);
+    const Region<uint16_t> sr(c, rec16, x, (ptrdiff_t)rec_stride * (yo - 1) + x + xo);
+    const size_t           o_out = c(8);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    so.up(sg, st), sr.up(sg, st);
+    unsigned long long *d_out = sg.dev<unsigned long long>(o_out), h_out = 0;
     HIP_OR_DIE(hipMemsetAsync(d_out, 0, sizeof(d_out[0]), st));
-    ccso_dist_kernel<<<1, 256, 0, st>>>(so.dev(), org_stride, sr.dev(), rec_stride, x, yo, xo, d_out);
+    ccso_dist_kernel<<<1, 256, 0, st>>>(so.dev(sg), org_stride, sr.dev(sg), rec_stride, x, yo, xo, d_out);
     HIP_OR_DIE(hipGetLastError());
-    HIP_OR_DIE(hipMemcpyAsync(&h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost, st));
+    sg.down(&h_out, o_out, sizeof(h_out), st);
     HIP_OR_DIE(hipStreamSynchronize(st));
-    (void)hipFree(d_out);
     return h_out;
 }
 
@@ -836,14 +836,17 @@ extern "C" void svtgpu_ccso_derive_src_block(const uint16_t *src_y, uint8_t *con
     ptrdiff_t   lo, hi, clo, chi;
     src_span(src_loc, true, src_y_stride, x, y_end, x_end, y_uv_hscale, y_uv_vscale, &lo, &hi);
     src_span(src_loc, false, ccso_stride, x, y_end, x_end, y_uv_hscale, y_uv_vscale, &clo, &chi);
-    Span<uint16_t> s(src_y, lo, hi, st);
-    Span<uint8_t>  c0(src_cls0, clo, chi, st), c1(src_cls1, clo, chi, st);
+    Carver                 c;
+    const Region<uint16_t> s(c, src_y, lo, hi);
+    const Region<uint8_t>  c0(c, src_cls0, clo, chi), c1(c, src_cls1, clo, chi);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    s.up(sg, st), c0.up(sg, st), c1.up(sg, st);
     BlkArgs a{};
-    a.mode = 0, a.src = s.dev(), a.cls0 = c0.dev(), a.cls1 = c1.dev(), a.src_stride = src_y_stride;
+    a.mode = 0, a.src = s.dev(sg), a.cls0 = c0.dev(sg), a.cls1 = c1.dev(sg), a.src_stride = src_y_stride;
     a.cls_stride = ccso_stride, a.x = x, a.y_end = y_end, a.x_end = x_end, a.hs = y_uv_hscale, a.vs = y_uv_vscale;
     a.q = (uint8_t)qstep, a.nq = neg_qstep, a.loc0 = src_loc[0], a.loc1 = src_loc[1], a.clf = edge_clf;
     run_block(a, st);
-    c0.back(src_cls0, st), c1.back(src_cls1, st);
+    c0.back(sg, st), c1.back(sg, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }
 
@@ -860,22 +863,22 @@ extern "C" void svtgpu_ccso_filter_block_hbd_with_buf(const uint16_t *src_y, uin
     ptrdiff_t   lo, hi, clo, chi;
     src_span(nullptr, false, src_y_stride, x, y_end, x_end, y_uv_hscale, y_uv_vscale, &lo, &hi);
     src_span(nullptr, false, ccso_stride, x, y_end, x_end, y_uv_hscale, y_uv_vscale, &clo, &chi);
-    Span<uint16_t> s(src_y, lo, hi, st), d(dst_yuv, x, (ptrdiff_t)(y_end - 1) * dst_stride + x + x_end, st);
-    Span<int8_t>   l(filter_offset, 0, SVTGPU_CCSO_LUT, st);
-    BlkArgs        a{};
-    a.mode = 1, a.src = s.dev(), a.dst = d.dev(), a.lut = l.dev(), a.src_stride = src_y_stride;
+    Carver                 c;
+    const Region<uint16_t> s(c, src_y, lo, hi), d(c, dst_yuv, x, (ptrdiff_t)(y_end - 1) * dst_stride + x + x_end);
+    const Region<int8_t>   l(c, filter_offset, 0, SVTGPU_CCSO_LUT);
+    const Region<uint8_t>  k0(c, src_cls0, clo, chi), k1(c, src_cls1, clo, chi);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    s.up(sg, st), d.up(sg, st), l.up(sg, st);
+    BlkArgs a{};
+    a.mode = 1, a.src = s.dev(sg), a.dst = d.dev(sg), a.lut = l.dev(sg), a.src_stride = src_y_stride;
     a.dst_stride = dst_stride, a.cls_stride = ccso_stride, a.x = x, a.y_end = y_end, a.x_end = x_end;
     a.hs = y_uv_hscale, a.vs = y_uv_vscale, a.maxv = max_val, a.shift = shift_bits, a.bo = ccso_bo_only;
-    if (!ccso_bo_only) { // band-offset-only: the class buffers are not read (EbCcso.c:24-30)
-        Span<uint8_t> k0(src_cls0, clo, chi, st), k1(src_cls1, clo, chi, st);
-        a.cls0 = k0.dev(), a.cls1 = k1.dev();
-        run_block(a, st);
-        d.back(dst_yuv, st);
-        HIP_OR_DIE(hipStreamSynchronize(st));
-        return;
+    if (!ccso_bo_only) { // band-offset-only: the class buffers are not read (EbCcso.c:24-30), nor uploaded
+        k0.up(sg, st), k1.up(sg, st);
+        a.cls0 = k0.dev(sg), a.cls1 = k1.dev(sg);
     }
     run_block(a, st);
-    d.back(dst_yuv, st);
+    d.back(sg, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }
 
@@ -892,15 +895,18 @@ extern "C" void svtgpu_ccso_filter_block_hbd_wo_buf(const uint16_t *src_y, uint1
     hipStream_t st = svtgpu_shim_stream();
     ptrdiff_t   lo, hi;
     src_span(src_loc, !ccso_bo_only, src_y_stride, x, y_end, x_end, y_uv_hscale, y_uv_vscale, &lo, &hi);
-    Span<uint16_t> s(src_y, lo, hi, st), d(dst_yuv, x, (ptrdiff_t)(y_end - 1) * dst_stride + x + x_end, st);
-    Span<int8_t>   l(offset_buf, 0, SVTGPU_CCSO_LUT, st);
-    Span<int32_t>  k(src_cls, 0, 2, st);
-    BlkArgs        a{};
-    a.mode = 2, a.src = s.dev(), a.dst = d.dev(), a.lut = l.dev(), a.last_cls = k.dev(), a.src_stride = src_y_stride;
+    Carver                 c;
+    const Region<uint16_t> s(c, src_y, lo, hi), d(c, dst_yuv, x, (ptrdiff_t)(y_end - 1) * dst_stride + x + x_end);
+    const Region<int8_t>   l(c, offset_buf, 0, SVTGPU_CCSO_LUT);
+    const Region<int32_t>  k(c, src_cls, 0, 2);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    s.up(sg, st), d.up(sg, st), l.up(sg, st), k.up(sg, st);
+    BlkArgs a{};
+    a.mode = 2, a.src = s.dev(sg), a.dst = d.dev(sg), a.lut = l.dev(sg), a.last_cls = k.dev(sg), a.src_stride = src_y_stride;
     a.dst_stride = dst_stride, a.x = x, a.y_end = y_end, a.x_end = x_end, a.hs = y_uv_hscale, a.vs = y_uv_vscale;
     a.q = (uint8_t)thr, a.nq = neg_thr, a.loc0 = ccso_bo_only ? 0 : src_loc[0], a.loc1 = ccso_bo_only ? 0 : src_loc[1];
     a.maxv = max_val, a.shift = shift_bits, a.bo = ccso_bo_only, a.single = isSingleBand, a.clf = edge_clf;
     run_block(a, st);
-    d.back(dst_yuv, st), k.back(src_cls, st);
+    d.back(sg, st), k.back(sg, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }

@@ -6,25 +6,6 @@
 
 #include "cdef_common.h"
 
-namespace {
-struct DevBuf { // grow-only device scratch for the shims (one per thread)
-    void  *p = nullptr;
-    size_t n = 0;
-    void  *get(size_t bytes) {
-        if (bytes > n) {
-            if (p) (void)hipFree(p);
-            HIP_OR_DIE(hipMalloc(&p, bytes));
-            n = bytes;
-        }
-        return p;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-thread_local DevBuf g_scratch;
-} // namespace
-
 // ---------------------------------------------------------------------------------------------
 // direction: svt_aom_cdef_find_dir_c (EbCdef.c:150-210), one lane per 8x8 block
 // ---------------------------------------------------------------------------------------------
@@ -77,14 +58,17 @@ __global__ void cdef_find_dir_kernel(const uint16_t *img, int n, int cs, uint8_t
 }
 
 static void find_dir_batch(const uint16_t *const *imgs, int stride, int n, int cs, uint8_t *dirs, int32_t *vars) {
-    hipStream_t           st = svtgpu_shim_stream();
-    std::vector<uint16_t> h((size_t)n * 64);
+    hipStream_t  st = svtgpu_shim_stream();
+    Carver       c;
+    const size_t o_img = c((size_t)n * 128), o_dir = c(n), o_var = c((size_t)n * 4);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint16_t    *h = sg.host<uint16_t>(o_img);
     for (int b = 0; b < n; b++)
         for (int i = 0; i < 8; i++) memcpy(&h[(size_t)b * 64 + i * 8], imgs[b] + (size_t)i * stride, 16);
-    char *d = (char *)g_scratch.get((size_t)n * (128 + 1 + 4) + 64);
-    HIP_OR_DIE(hipMemcpyAsync(d, h.data(), (size_t)n * 128, hipMemcpyHostToDevice, st));
-    uint8_t *dd = (uint8_t *)(d + (size_t)n * 128);
-    int32_t *dv = (int32_t *)(d + (size_t)n * 128 + ((n + 3) & ~3));
+    uint8_t *d = sg.d + o_img;
+    HIP_OR_DIE(hipMemcpyAsync(d, h, (size_t)n * 128, hipMemcpyHostToDevice, st));
+    uint8_t *dd = sg.d + o_dir;
+    int32_t *dv = sg.dev<int32_t>(o_var);
     hipLaunchKernelGGL(cdef_find_dir_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const uint16_t *)d, n, cs, dd, dv);
     HIP_OR_DIE(hipGetLastError());
     HIP_OR_DIE(hipMemcpyAsync(dirs, dd, n, hipMemcpyDeviceToHost, st));
@@ -129,13 +113,16 @@ extern "C" void svtgpu_cdef_filter_block(uint8_t *dst8, uint16_t *dst16, int32_t
     const int bw = (bsize == SVTGPU_BLOCK_8X8 || bsize == SVTGPU_BLOCK_8X4) ? 8 : 4;
     const int ws = bw + 2 * CDEF_BORDER, wh = bh + 2 * CDEF_BORDER;
     const int ss = subsampling_factor ? subsampling_factor : 1;
-    std::vector<uint16_t> win((size_t)ws * wh);
+    hipStream_t  st = svtgpu_shim_stream();
+    Carver       c;
+    const size_t wbytes = (size_t)ws * wh * 2, o_win = c(wbytes), o_out = c(128);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint16_t    *win = sg.host<uint16_t>(o_win);
     for (int r = 0; r < wh; r++) // exactly the samples the reference reads (rows/cols -2..+1 past the block)
         memcpy(&win[(size_t)r * ws], in + (long)(r - CDEF_BORDER) * 144 - CDEF_BORDER, (size_t)ws * 2);
-    hipStream_t st = svtgpu_shim_stream();
-    char       *d  = (char *)g_scratch.get(win.size() * 2 + 256);
-    uint16_t   *dout = (uint16_t *)(d + ((win.size() * 2 + 15) & ~(size_t)15));
-    HIP_OR_DIE(hipMemcpyAsync(d, win.data(), win.size() * 2, hipMemcpyHostToDevice, st));
+    uint8_t     *d    = sg.d + o_win;
+    uint16_t    *dout = sg.dev<uint16_t>(o_out);
+    HIP_OR_DIE(hipMemcpyAsync(d, win, wbytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(cdef_filter_block_kernel, dim3(1), dim3(64), 0, st, (const uint16_t *)d, ws, bh, bw, pri_strength,
                        sec_strength, dir, pri_damping, sec_damping, coeff_shift, ss, dout);
     HIP_OR_DIE(hipGetLastError());
@@ -198,20 +185,20 @@ static uint64_t cdef_dist_host(const T *dst, int32_t dstride, const T *src, cons
         maxc = std::max(maxc, (dlist[i].bx + 1) << lbw);
     }
     // source region actually read: rows [0, maxr), cols [0, maxc) at stride `dstride`
-    std::vector<T> org((size_t)maxr * maxc);
-    for (int r = 0; r < maxr; r++) memcpy(&org[(size_t)r * maxc], dst + (long)r * dstride, (size_t)maxc * sizeof(T));
-    const size_t fbytes = ((size_t)n << (lbh + lbw)) * sizeof(T);
-    const size_t o1 = (org.size() * sizeof(T) + 255) & ~(size_t)255;
-    const size_t o2 = o1 + ((fbytes + 255) & ~(size_t)255);
-    const size_t o3 = o2 + (((size_t)n * 2 + 255) & ~(size_t)255);
-    char        *d  = (char *)g_scratch.get(o3 + 64);
+    const size_t obytes = (size_t)maxr * maxc * sizeof(T), fbytes = ((size_t)n << (lbh + lbw)) * sizeof(T);
+    Carver       c;
+    const size_t o0 = c(obytes), o1 = c(fbytes), o2 = c((size_t)n * 2), o3 = c(8);
     hipStream_t  st = svtgpu_shim_stream();
-    HIP_OR_DIE(hipMemcpyAsync(d, org.data(), org.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    T           *org = sg.host<T>(o0);
+    for (int r = 0; r < maxr; r++) memcpy(&org[(size_t)r * maxc], dst + (long)r * dstride, (size_t)maxc * sizeof(T));
+    uint8_t     *d = sg.d;
+    HIP_OR_DIE(hipMemcpyAsync(d + o0, org, obytes, hipMemcpyHostToDevice, st));
     HIP_OR_DIE(hipMemcpyAsync(d + o1, src, fbytes, hipMemcpyHostToDevice, st));
     HIP_OR_DIE(hipMemcpyAsync(d + o2, dlist, (size_t)n * 2, hipMemcpyHostToDevice, st));
     HIP_OR_DIE(hipMemsetAsync(d + o3, 0, 8, st));
     const int luma_ssim = bsize == SVTGPU_BLOCK_8X8 && pli == 0;
-    hipLaunchKernelGGL(cdef_dist_kernel<T>, dim3((n + 63) / 64), dim3(64), 0, st, (const T *)d, maxc,
+    hipLaunchKernelGGL(cdef_dist_kernel<T>, dim3((n + 63) / 64), dim3(64), 0, st, (const T *)(d + o0), maxc,
                        (const T *)(d + o1), (const SvtGpuCdefList *)(d + o2), n, bh, bw, luma_ssim, cs,
                        ss ? ss : 1, (unsigned long long *)(d + o3));
     HIP_OR_DIE(hipGetLastError());
@@ -242,18 +229,21 @@ extern "C" void svtgpu_cdef_filter_block_8xn_16(const uint16_t *const in, const 
     const int bh = (height + 2 * ss - 1) / (2 * ss) * (2 * ss); // the AVX2 loop writes row pairs
     if (bh * 8 > 1024) return;
     const int ws = 8 + 2 * CDEF_BORDER, wh = bh + 2 * CDEF_BORDER;
-    std::vector<uint16_t> win((size_t)ws * wh);
+    hipStream_t  st = svtgpu_shim_stream();
+    Carver       c;
+    const size_t wbytes = (size_t)ws * wh * 2, o_win = c(wbytes), o_out = c((size_t)bh * 16);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint16_t    *win = sg.host<uint16_t>(o_win);
     for (int r = 0; r < wh; r++)
         memcpy(&win[(size_t)r * ws], in + (long)(r - CDEF_BORDER) * 144 - CDEF_BORDER, (size_t)ws * 2);
-    hipStream_t st   = svtgpu_shim_stream();
-    char       *d    = (char *)g_scratch.get(win.size() * 2 + 2 * 1024 + 256);
-    uint16_t   *dout = (uint16_t *)(d + ((win.size() * 2 + 15) & ~(size_t)15));
-    HIP_OR_DIE(hipMemcpyAsync(d, win.data(), win.size() * 2, hipMemcpyHostToDevice, st));
+    uint8_t     *d    = sg.d + o_win;
+    uint16_t    *dout = sg.dev<uint16_t>(o_out);
+    HIP_OR_DIE(hipMemcpyAsync(d, win, wbytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(cdef_filter_block_kernel, dim3(1), dim3(bh * 8), 0, st, (const uint16_t *)d, ws, bh, 8,
                        pri_strength, sec_strength, dir, pri_damping, sec_damping, coeff_shift, ss, dout);
     HIP_OR_DIE(hipGetLastError());
-    std::vector<uint16_t> out((size_t)bh * 8);
-    HIP_OR_DIE(hipMemcpyAsync(out.data(), dout, out.size() * 2, hipMemcpyDeviceToHost, st));
+    const uint16_t *out = sg.host<uint16_t>(o_out);
+    HIP_OR_DIE(hipMemcpyAsync(sg.h + o_out, dout, (size_t)bh * 16, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     for (int i = 0; i < bh; i += ss) memcpy(dst + (long)i * dstride, &out[(size_t)i * 8], 16);
 }
@@ -266,17 +256,18 @@ __global__ void copy_rect8_kernel(uint16_t *dst, const uint8_t *src, int n) {
 extern "C" void svtgpu_aom_copy_rect8_8bit_to_16bit(uint16_t *dst, int32_t dstride, const uint8_t *src, int32_t sstride,
                                                     int32_t v, int32_t h) {
     if (v <= 0 || h <= 0) return;
-    std::vector<uint8_t> hs((size_t)v * h);
+    hipStream_t  st = svtgpu_shim_stream();
+    Carver       c;
+    const size_t n = (size_t)v * h, o_src = c(n), o_dst = c(n * 2);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t     *hs = sg.h + o_src, *d = sg.d + o_src;
     for (int r = 0; r < v; r++) memcpy(&hs[(size_t)r * h], src + (long)r * sstride, (size_t)h);
-    hipStream_t st = svtgpu_shim_stream();
-    char       *d  = (char *)g_scratch.get(hs.size() * 3 + 64);
-    uint16_t   *d16 = (uint16_t *)(d + ((hs.size() + 15) & ~(size_t)15));
-    HIP_OR_DIE(hipMemcpyAsync(d, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(copy_rect8_kernel, dim3((unsigned)((hs.size() + 255) / 256)), dim3(256), 0, st, d16,
-                       (const uint8_t *)d, (int)hs.size());
+    uint16_t    *d16 = sg.dev<uint16_t>(o_dst);
+    HIP_OR_DIE(hipMemcpyAsync(d, hs, n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(copy_rect8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d16, (const uint8_t *)d, (int)n);
     HIP_OR_DIE(hipGetLastError());
-    std::vector<uint16_t> out(hs.size());
-    HIP_OR_DIE(hipMemcpyAsync(out.data(), d16, out.size() * 2, hipMemcpyDeviceToHost, st));
+    const uint16_t *out = sg.host<uint16_t>(o_dst);
+    HIP_OR_DIE(hipMemcpyAsync(sg.h + o_dst, d16, n * 2, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     for (int r = 0; r < v; r++) memcpy(dst + (long)r * dstride, &out[(size_t)r * h], (size_t)h * 2);
 }
@@ -331,8 +322,11 @@ __global__ void sod_argmin_kernel(const uint64_t *tot, int start, int end, uint6
 
 extern "C" uint64_t svtgpu_search_one_dual(int *lev0, int *lev1, int nb_strengths, uint64_t **mse[2], int sb_count,
                                            int start_gi, int end_gi) {
-    hipStream_t           st = svtgpu_shim_stream();
-    std::vector<uint64_t> h((size_t)std::max(sb_count, 1) * 128);
+    hipStream_t  st = svtgpu_shim_stream();
+    Carver       c;
+    const size_t mbytes = (size_t)std::max(sb_count, 1) * 1024, o0 = c(mbytes), o1 = c(128), o2 = c(4096 * 8), o3 = c(16);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint64_t    *h = sg.host<uint64_t>(o0);
     for (int fb = 0; fb < sb_count; fb++) {
         memcpy(&h[(size_t)fb * 128], mse[0][fb], 64 * 8);
         memcpy(&h[(size_t)fb * 128 + 64], mse[1][fb], 64 * 8);
@@ -342,11 +336,10 @@ extern "C" uint64_t svtgpu_search_one_dual(int *lev0, int *lev1, int nb_strength
         lev[g]      = lev0[g];
         lev[16 + g] = lev1[g];
     }
-    const size_t o1 = h.size() * 8, o2 = o1 + 128, o3 = o2 + 4096 * 8;
-    char        *d  = (char *)g_scratch.get(o3 + 16);
-    HIP_OR_DIE(hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+    uint8_t *d = sg.d;
+    HIP_OR_DIE(hipMemcpyAsync(d + o0, h, mbytes, hipMemcpyHostToDevice, st));
     HIP_OR_DIE(hipMemcpyAsync(d + o1, lev, sizeof lev, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sod_tot_kernel, dim3(16), dim3(256), 0, st, (const uint64_t *)d, sb_count, (const int32_t *)(d + o1),
+    hipLaunchKernelGGL(sod_tot_kernel, dim3(16), dim3(256), 0, st, (const uint64_t *)(d + o0), sb_count, (const int32_t *)(d + o1),
                        nb_strengths, (uint64_t *)(d + o2));
     hipLaunchKernelGGL(sod_argmin_kernel, dim3(1), dim3(256), 0, st, (const uint64_t *)(d + o2), start_gi, end_gi,
                        (uint64_t *)(d + o3));

@@ -139,28 +139,6 @@ __global__ __launch_bounds__(64) void jnt_block_kernel(const JntArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct ThreadStage { // the calling thread's staging buffers: grown, never freed per call
-    uint8_t             *d   = nullptr;
-    size_t               cap = 0;
-    std::vector<uint8_t> h;
-};
-thread_local ThreadStage t_stage;
-
-uint8_t *stage_reserve(size_t need, hipStream_t st) {
-    ThreadStage &t = t_stage;
-    if (need > t.cap) {
-        if (t.d) {
-            HIP_OR_DIE(hipStreamSynchronize(st));
-            (void)hipFree(t.d);
-        }
-        need = (need + (need >> 1) + 0xfff) & ~(size_t)0xfff;
-        HIP_OR_DIE(hipMalloc(&t.d, need));
-        t.cap = need;
-    }
-    if (t.h.size() < t.cap) t.h.resize(t.cap);
-    return t.d;
-}
-
 template <typename T>
 void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, int w, int h, const int16_t *fx, const int16_t *fy,
               int round_0, int round_1, uint16_t *conv_dst, int conv_dst_stride, int do_average, int use_jnt_comp_avg,
@@ -170,11 +148,13 @@ void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, in
         round_1 < 0 || round_1 > 7 || conv_dst_stride < w)
         svtgpu_fatal("svtgpu compound convolve shim: bad arguments");
     const int    ws = w + 7, hs = h + 7;
-    const size_t win = align16((size_t)ws * hs * sizeof(T)), conv = (size_t)w * h * sizeof(uint16_t), out = (size_t)w * h * sizeof(T);
-    const size_t o_taps = win, o_conv = o_taps + 32, o_out = o_conv + align16(conv);
+    const size_t conv = (size_t)w * h * sizeof(uint16_t), out = (size_t)w * h * sizeof(T);
+    Carver       c; // the window at 0, then the taps, conv_dst and the pixels
+    c((size_t)ws * hs * sizeof(T));
+    const size_t o_taps = c(32), o_conv = c(conv), o_out = c(out);
     hipStream_t  st = svtgpu_shim_stream();
-    uint8_t     *hb;
-    uint8_t     *d  = svtgpu_compound_stage_reserve(o_out + out, st, &hb);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t *const hb = sg.h, *const d = sg.d;
     T           *hw = (T *)hb;
     // what the reference's C reads of src, and nothing else (as the single-reference shims)
     memset(hb, 0, o_conv);
@@ -211,12 +191,6 @@ void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, in
 }
 
 } // namespace
-
-uint8_t *svtgpu_compound_stage_reserve(size_t need, hipStream_t st, uint8_t **host) {
-    uint8_t *d = stage_reserve(need, st);
-    *host      = t_stage.h.data();
-    return d;
-}
 
 extern "C" int svtgpu_dist_wtd_weights(int32_t d0, int32_t d1, int32_t order_idx, int32_t *fwd_offset, int32_t *bck_offset) {
     return compound_weights::select(d0, d1, order_idx, fwd_offset, bck_offset) ? SVTGPU_OK : SVTGPU_ERR_INVALID_ARG;

@@ -21,10 +21,13 @@
 #include <cstring>
 #include <vector>
 
+#include "conv_device.h"
 #include "interp_tables.h"
 #include "svtgpu_internal.h"
 
 namespace compound_tile {
+
+using namespace conv_device;
 
 constexpr int kMaxRefs = 26; // as svtgpu_tf_predict_frame
 constexpr int kTile    = 32;
@@ -44,13 +47,6 @@ struct Rounds {
     int32_t r0, r1, bd;
 };
 
-__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ __forceinline__ int round_shift(int v, int n) { return (v + ((1 << n) >> 1)) >> n; } // ROUND_POWER_OF_TWO
-__device__ __forceinline__ void wave_lds_sync() { // the wave's LDS stores before its LDS loads (in order within a wave)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ void load_taps(const int16_t *p, int f[8]) { // a 16-byte aligned row of eight taps
     const i16x8 v = *(const i16x8 *)p;
 #pragma unroll
@@ -240,7 +236,3 @@ struct ItemBuilder { // tiles -> wave items; small tiles of one shape gathered, 
 };
 
 } // namespace compound_tile
-
-// The calling thread's staging buffers of the two-reference shims (compound.hip): grown, never freed per call.  Returns
-// the device buffer of at least `need` bytes and, in *host, the host buffer of the same size.
-uint8_t *svtgpu_compound_stage_reserve(size_t need, hipStream_t st, uint8_t **host);

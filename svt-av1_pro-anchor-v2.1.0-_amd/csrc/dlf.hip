@@ -1355,6 +1355,8 @@ extern "C" int svtgpu_plane_sse(const SvtGpuFrame *a, const SvtGpuFrame *b, int3
         a->bytes_per_sample != b->bytes_per_sample)
         return SVTGPU_ERR_INVALID_ARG;
     hipStream_t st = pick_stream(a->ctx, stream);
+    // not the shims' stage (svtgpu_stage_reserve): a frame-level entry on the caller's context and stream that reports
+    // errors by return code, so it keeps a result slot of its own
     static thread_local unsigned long long *d = nullptr; // per-thread result slot
     if (!d) HIP_TRY(hipMalloc((void **)&d, sizeof *d));
     HIP_TRY(hipMemsetAsync(d, 0, sizeof *d, st));
@@ -1386,8 +1388,8 @@ void lpf_shim(T *s, int32_t pitch, int vertical, int len, const uint8_t *blimit,
     for (int l = 0; l < 4; l++) // only the samples the reference function touches
         for (int k = -h; k < h; k++) lines[l * 16 + 8 + k] = s[l * adv + k * step];
     hipStream_t st = svtgpu_shim_stream();
-    static thread_local uint16_t *d = nullptr;
-    if (!d) HIP_OR_DIE(hipMalloc(&d, sizeof lines));
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(sizeof lines, st);
+    uint16_t   *d = sg.dev<uint16_t>(0);
     HIP_OR_DIE(hipMemcpyAsync(d, lines, sizeof lines, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lpf_lines_kernel, dim3(1), dim3(64), 0, st, d, len, (int)*blimit, (int)*limit, (int)*thresh, bd);
     HIP_OR_DIE(hipGetLastError());

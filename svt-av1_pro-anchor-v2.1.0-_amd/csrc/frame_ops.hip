@@ -122,12 +122,6 @@ int extend_dev(void *data, int bits, int stride, int w, int h, int bh, int bv, h
     return SVTGPU_OK;
 }
 
-// host staging of a strided region [first byte, last byte] for the synchronous shims
-struct HostSpan {
-    uint8_t *d = nullptr;
-    ~HostSpan() { (void)hipFree(d); }
-};
-
 } // namespace
 
 // ---- device-pointer entry points ----
@@ -165,17 +159,34 @@ extern "C" int svtgpu_frame_convert(const SvtGpuFrame *src, SvtGpuFrame *dst, vo
     return SVTGPU_OK;
 }
 
-// ---- RTCD-compatible shims (synchronous, host pointers) ----
+// ---- RTCD-compatible shims (synchronous, host pointers): the touched span of the caller's buffer goes to the thread's
+// stage as it lies in memory, the device-pointer function runs on it, the span comes back ----
 namespace {
-template <typename T>
-T *stage_in(hipStream_t st, HostSpan &sp, const T *h, size_t first, size_t n_elems) { // [h + first, + n_elems)
-    HIP_OR_DIE(hipMalloc(&sp.d, n_elems * sizeof(T)));
-    HIP_OR_DIE(hipMemcpyAsync(sp.d, h + first, n_elems * sizeof(T), hipMemcpyHostToDevice, st));
-    return (T *)sp.d;
+void must(int rc) {
+    if (rc) svtgpu_fatal("svtgpu frame-buffer shim: the device call failed");
 }
-template <typename T>
-void stage_out(hipStream_t st, T *h, size_t first, const HostSpan &sp, size_t n_elems) {
-    HIP_OR_DIE(hipMemcpyAsync(h + first, sp.d, n_elems * sizeof(T), hipMemcpyDeviceToHost, st));
+// one buffer of n elements filtered in place
+template <typename T, typename Fn>
+void shim_in_place(T *h, size_t n, Fn &&run) {
+    hipStream_t            st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(n * sizeof(T), st);
+    sg.up(0, h, n * sizeof(T), st);
+    must(run(sg.dev<T>(0), st));
+    sg.down(h, 0, n * sizeof(T), st);
+    HIP_OR_DIE(hipStreamSynchronize(st));
+}
+template <typename S, typename D>
+void shim_convert(const S *src, uint32_t src_stride, D *dst, uint32_t dst_stride, uint32_t width, uint32_t height) {
+    if (!width || !height) return;
+    hipStream_t  st = svtgpu_shim_stream();
+    const size_t ns = ((size_t)(height - 1) * src_stride + width) * sizeof(S), nd = ((size_t)(height - 1) * dst_stride + width) * sizeof(D);
+    Carver       c;
+    const size_t o_s = c(ns), o_d = c(nd);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    sg.up(o_s, src, ns, st);
+    sg.up(o_d, dst, nd, st); // the samples between rows stay as they were
+    must(convert_dev(sg.d + o_s, 8 * sizeof(S), (int)src_stride, sg.d + o_d, 8 * sizeof(D), (int)dst_stride, (int)width, (int)height, st));
+    sg.down(dst, o_d, nd, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }
 } // namespace
@@ -183,29 +194,13 @@ void stage_out(hipStream_t st, T *h, size_t first, const HostSpan &sp, size_t n_
 // svt_convert_8bit_to_16bit (common_dsp_rtcd.h:154)
 extern "C" void svtgpu_convert_8bit_to_16bit(uint8_t *src, uint32_t src_stride, uint16_t *dst, uint32_t dst_stride,
                                              uint32_t width, uint32_t height) {
-    if (!width || !height) return;
-    hipStream_t st = svtgpu_shim_stream();
-    HostSpan    a, b;
-    const size_t ns = (size_t)(height - 1) * src_stride + width, nd = (size_t)(height - 1) * dst_stride + width;
-    uint8_t     *ds = stage_in(st, a, src, 0, ns);
-    uint16_t    *dd = stage_in(st, b, dst, 0, nd); // the samples between rows stay as they were
-    HIP_OR_DIE(convert_dev(ds, 8, (int)src_stride, dd, 16, (int)dst_stride, (int)width, (int)height, st) ? hipErrorUnknown
-                                                                                                         : hipSuccess);
-    stage_out(st, dst, 0, b, nd);
+    shim_convert(src, src_stride, dst, dst_stride, width, height);
 }
 
 // svt_convert_16bit_to_8bit (common_dsp_rtcd.h:156)
 extern "C" void svtgpu_convert_16bit_to_8bit(uint16_t *src, uint32_t src_stride, uint8_t *dst, uint32_t dst_stride,
                                              uint32_t width, uint32_t height) {
-    if (!width || !height) return;
-    hipStream_t st = svtgpu_shim_stream();
-    HostSpan    a, b;
-    const size_t ns = (size_t)(height - 1) * src_stride + width, nd = (size_t)(height - 1) * dst_stride + width;
-    uint16_t    *ds = stage_in(st, a, src, 0, ns);
-    uint8_t     *dd = stage_in(st, b, dst, 0, nd);
-    HIP_OR_DIE(convert_dev(ds, 16, (int)src_stride, dd, 8, (int)dst_stride, (int)width, (int)height, st) ? hipErrorUnknown
-                                                                                                         : hipSuccess);
-    stage_out(st, dst, 0, b, nd);
+    shim_convert(src, src_stride, dst, dst_stride, width, height);
 }
 
 // svt_aom_generate_padding (EbMcp.h:46): the buffer holds (h + 2 ph) rows of `stride` samples
@@ -213,52 +208,35 @@ extern "C" void svtgpu_aom_generate_padding(uint8_t *src_pic, uint32_t src_strid
                                             uint32_t original_src_height, uint32_t padding_width,
                                             uint32_t padding_height) {
     if (!src_pic) return;
-    hipStream_t  st = svtgpu_shim_stream();
-    HostSpan     a;
-    const size_t n  = (size_t)(original_src_height + 2 * padding_height) * src_stride;
-    uint8_t     *d  = stage_in(st, a, src_pic, 0, n);
-    HIP_OR_DIE(pad_dev(d, 8, (int)src_stride, (int)original_src_width, (int)original_src_height, (int)padding_width,
-                       (int)padding_height, st)
-                   ? hipErrorUnknown
-                   : hipSuccess);
-    stage_out(st, src_pic, 0, a, n);
+    shim_in_place(src_pic, (size_t)(original_src_height + 2 * padding_height) * src_stride, [&](uint8_t *d, hipStream_t st) {
+        return pad_dev(d, 8, (int)src_stride, (int)original_src_width, (int)original_src_height, (int)padding_width,
+                       (int)padding_height, st);
+    });
 }
 
 // svt_aom_generate_padding16_bit (EbMcp.h:49)
 extern "C" void svtgpu_aom_generate_padding16_bit(uint16_t *src_pic, uint32_t src_stride, uint32_t original_src_width,
                                                   uint32_t original_src_height, uint32_t padding_width,
                                                   uint32_t padding_height) {
-    hipStream_t  st = svtgpu_shim_stream();
-    HostSpan     a;
-    const size_t n  = (size_t)(original_src_height + 2 * padding_height) * src_stride;
-    uint16_t    *d  = stage_in(st, a, src_pic, 0, n);
-    HIP_OR_DIE(pad_dev(d, 16, (int)src_stride, (int)original_src_width, (int)original_src_height, (int)padding_width,
-                       (int)padding_height, st)
-                   ? hipErrorUnknown
-                   : hipSuccess);
-    stage_out(st, src_pic, 0, a, n);
+    shim_in_place(src_pic, (size_t)(original_src_height + 2 * padding_height) * src_stride, [&](uint16_t *d, hipStream_t st) {
+        return pad_dev(d, 16, (int)src_stride, (int)original_src_width, (int)original_src_height, (int)padding_width,
+                       (int)padding_height, st);
+    });
 }
 
 // svt_extend_frame (EbRestoration.c:197; highbd data is a CONVERT_TO_BYTEPTR pointer)
 extern "C" void svtgpu_extend_frame(uint8_t *data, int32_t width, int32_t height, int32_t stride, int32_t border_horz,
                                     int32_t border_vert, int32_t highbd) {
-    hipStream_t st    = svtgpu_shim_stream();
     const size_t rows = (size_t)height + 2 * border_vert;
     // the touched span: from (-bv, -bh) to (h + bv - 1, w + bh - 1)
     const ptrdiff_t first = -(ptrdiff_t)border_vert * stride - border_horz;
     const size_t    n     = (rows - 1) * (size_t)stride + (size_t)(width + 2 * border_horz);
-    HostSpan        a;
-    if (highbd) {
-        uint16_t *h = (uint16_t *)((uintptr_t)data << 1) + first; // CONVERT_TO_SHORTPTR
-        uint16_t *d = stage_in(st, a, h, 0, n);
-        HIP_OR_DIE(extend_dev(d - first, 16, stride, width, height, border_horz, border_vert, st) ? hipErrorUnknown
-                                                                                                   : hipSuccess);
-        stage_out(st, h, 0, a, n);
-    } else {
-        uint8_t *h = data + first;
-        uint8_t *d = stage_in(st, a, h, 0, n);
-        HIP_OR_DIE(extend_dev(d - first, 8, stride, width, height, border_horz, border_vert, st) ? hipErrorUnknown
-                                                                                                  : hipSuccess);
-        stage_out(st, h, 0, a, n);
-    }
+    if (highbd)
+        shim_in_place((uint16_t *)short_ptr(data) + first, n, [&](uint16_t *d, hipStream_t st) {
+            return extend_dev(d - first, 16, stride, width, height, border_horz, border_vert, st);
+        });
+    else
+        shim_in_place(data + first, n, [&](uint8_t *d, hipStream_t st) {
+            return extend_dev(d - first, 8, stride, width, height, border_horz, border_vert, st);
+        });
 }

@@ -21,18 +21,21 @@
 // 1 << (1 - ss), cast to int16 as the reference's MV struct does, clamped to [edge - ((4 + b) << 4), edge + ((4 + b) << 4)
 // - 16] in 1/16 sample of the plane; phase = & 15, integer part = >> 4 (arithmetic).
 //
-// Bounds: every reference read goes through clamp_coord into [-border, size + border - 1] of the plane, which the entry's
+// Bounds: every reference read goes through clamp_i into [-border, size + border - 1] of the plane, which the entry's
 // contract makes readable; predictor writes cover the 64-aligned area the entry checks the strides against; the motion
 // index r * nblk + b < n_refs * nblk; LDS indices are below (rh + 7) * (rw + 7) <= 39 * 39 and (rh + 7) * rw <= 39 * 32.
 #include <cstring>
 #include <vector>
 
+#include "conv_device.h"
 #include "interp_tables.h"
 #include "svtgpu_internal.h"
 
 static_assert(sizeof(SvtGpuTfMotion) == 368 && sizeof(SvtGpuTfMotion) % 16 == 0, "SvtGpuTfMotion is 368 bytes");
 
 namespace {
+
+using namespace conv_device;
 
 constexpr int kMaxRefs = 26; // as svtgpu_tf_filter_frame
 constexpr int kTile    = 32; // the largest region of one wave
@@ -48,19 +51,6 @@ template <typename T> struct WaveLds {
     int16_t im[kWin * kTile];
 };
 
-__device__ __forceinline__ int clamp_coord(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ __forceinline__ int clip_bd(int v, int bd) {
-    const int m = (1 << bd) - 1;
-    return v < 0 ? 0 : v > m ? m : v;
-}
-__device__ __forceinline__ int round_shift(int v, int n) { return (v + ((1 << n) >> 1)) >> n; } // ROUND_POWER_OF_TWO
-// the wave's LDS stores before its LDS loads: in order within a wave, the compiler must keep them so
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // One wave, one rw x rh region (powers of two, at most 32) whose top-left sample reads the reference at (sx, sy) of a
 // pw x ph plane readable bx / by samples beyond each side.  fx / fy: wave-uniform pointers to the two 8-tap rows.
 template <typename T>
@@ -71,7 +61,7 @@ __device__ __forceinline__ void wave_region(const T *__restrict__ ref, int strid
     if (mode == kCopy) {
         for (int i = lane; i < n; i += 64) {
             const int y = i >> lw, x = i & (rw - 1);
-            const int gx = clamp_coord(sx + x, -bx, pw + bx - 1), gy = clamp_coord(sy + y, -by, ph + by - 1);
+            const int gx = clamp_i(sx + x, -bx, pw + bx - 1), gy = clamp_i(sy + y, -by, ph + by - 1);
             dst[(size_t)y * dstride + x] = ref[(ptrdiff_t)gy * stride + gx];
         }
         return;
@@ -81,7 +71,7 @@ __device__ __forceinline__ void wave_region(const T *__restrict__ ref, int strid
     const int recip = (1 << 20) / ww + 1;
     for (int i = lane; i < ww * wh; i += 64) {
         const int y = (i * recip) >> 20, x = i - y * ww;
-        const int gx = clamp_coord(sx - 3 + x, -bx, pw + bx - 1), gy = clamp_coord(sy - 3 + y, -by, ph + by - 1);
+        const int gx = clamp_i(sx - 3 + x, -bx, pw + bx - 1), gy = clamp_i(sy - 3 + y, -by, ph + by - 1);
         lds->win[i] = ref[(ptrdiff_t)gy * stride + gx];
     }
     wave_lds_sync();
@@ -159,7 +149,7 @@ __device__ __forceinline__ void predict_block(const PredArgs &a, const PredPlane
         const int spel = (4 + bp) << 4;
         const int lo_x = -(px * 8) * (1 << sc) - spel, hi_x = ((a.width - b - px) * 8) * (1 << sc) + spel - 16;
         const int lo_y = -(py * 8) * (1 << sc) - spel, hi_y = ((a.height - b - py) * 8) * (1 << sc) + spel - 16;
-        qx = (int16_t)clamp_coord(qx, lo_x, hi_x), qy = (int16_t)clamp_coord(qy, lo_y, hi_y);
+        qx = (int16_t)clamp_i(qx, lo_x, hi_x), qy = (int16_t)clamp_i(qy, lo_y, hi_y);
         const int phx = qx & 15, phy = qy & 15;
         const int sx = (px >> ss) + (qx >> 4) + (ox >> ss), sy = (py >> ss) + (qy >> 4) + (oy >> ss);
         const int tab = bp <= 4 ? kInterpRegular4 : kInterpSharp; // MULTITAP_SHARP: the 4-tap table from w <= 4 / h <= 4
@@ -222,28 +212,6 @@ __global__ __launch_bounds__(64) void interp_block_kernel(const BlockArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct ThreadStage { // the calling thread's staging buffers: grown, never freed per call
-    uint8_t             *d   = nullptr;
-    size_t               cap = 0;
-    std::vector<uint8_t> h;
-};
-thread_local ThreadStage t_stage;
-
-uint8_t *stage_reserve(size_t need, hipStream_t st) {
-    ThreadStage &t = t_stage;
-    if (need > t.cap) {
-        if (t.d) {
-            HIP_OR_DIE(hipStreamSynchronize(st));
-            (void)hipFree(t.d);
-        }
-        need = (need + (need >> 1) + 0xfff) & ~(size_t)0xfff;
-        HIP_OR_DIE(hipMalloc(&t.d, need));
-        t.cap = need;
-    }
-    if (t.h.size() < t.cap) t.h.resize(t.cap);
-    return t.d;
-}
-
 bool size_ok(int v) { return v >= 2 && v <= 128 && !(v & (v - 1)); }
 
 template <typename T>
@@ -254,28 +222,30 @@ void shim_convolve(int mode, const T *src, int src_stride, T *dst, int dst_strid
         (mode == k2d && (round_0 + round_1 > 14 || bd + 14 - round_0 - round_1 < 1)))
         svtgpu_fatal("svtgpu interpolation shim: bad arguments");
     const int    ws = w + 7, hs = h + 7;
-    const size_t win = ((size_t)ws * hs * sizeof(T) + 15) & ~(size_t)15, out = (size_t)w * h * sizeof(T);
+    Carver       c;
+    const size_t out = (size_t)w * h * sizeof(T), o_win = c((size_t)ws * hs * sizeof(T)), o_out = c(out);
     hipStream_t  st = svtgpu_shim_stream();
-    uint8_t     *d  = stage_reserve(win + out, st);
-    T           *hw = (T *)t_stage.h.data();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t     *d  = sg.d;
+    T           *hw = sg.host<T>(o_win);
     // what the reference's C reads of src, and nothing else: rows -3 .. h + 3 when it filters vertically (the y-only form
     // one more), columns -3 .. w + 4 when horizontally
-    memset(hw, 0, win);
+    memset(hw, 0, o_out - o_win);
     const int y0 = (mode & kVert) ? -3 : 0, y1 = (mode & kVert) ? h + 4 : h, x0 = (mode & kHorz) ? -3 : 0,
               x1 = (mode & kHorz) ? w + 4 : w;
     for (int y = y0; y < y1; y++)
         memcpy(hw + (size_t)(y + 3) * ws + x0 + 3, src + (ptrdiff_t)y * src_stride + x0, (size_t)(x1 - x0) * sizeof(T));
-    HIP_OR_DIE(hipMemcpyAsync(d, hw, win, hipMemcpyHostToDevice, st));
+    HIP_OR_DIE(hipMemcpyAsync(d + o_win, hw, o_out - o_win, hipMemcpyHostToDevice, st));
     BlockArgs a;
     memset(&a, 0, sizeof a);
-    a.src = d, a.dst = d + win, a.w = w, a.h = h, a.mode = mode, a.cr = {round_0, round_1, bd};
+    a.src = d + o_win, a.dst = d + o_out, a.w = w, a.h = h, a.mode = mode, a.cr = {round_0, round_1, bd};
     if (fx) memcpy(a.fx, fx, sizeof a.fx);
     if (fy) memcpy(a.fy, fy, sizeof a.fy);
     const dim3 grid((unsigned)((w + kTile - 1) / kTile), (unsigned)((h + kTile - 1) / kTile));
     hipLaunchKernelGGL(interp_block_kernel<T>, grid, dim3(64), 0, st, a);
     HIP_OR_DIE(hipGetLastError());
-    uint8_t *ho = t_stage.h.data() + win;
-    HIP_OR_DIE(hipMemcpyAsync(ho, d + win, out, hipMemcpyDeviceToHost, st));
+    uint8_t *ho = sg.h + o_out;
+    HIP_OR_DIE(hipMemcpyAsync(ho, d + o_out, out, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     for (int y = 0; y < h; y++) memcpy(dst + (ptrdiff_t)y * dst_stride, (const T *)ho + (size_t)y * w, (size_t)w * sizeof(T));
 }

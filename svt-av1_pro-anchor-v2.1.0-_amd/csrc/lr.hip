@@ -504,20 +504,6 @@ extern "C" int svtgpu_lr_apply_frame(SvtGpuLrState *s, const SvtGpuFrame *debloc
 // shims
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct ShimBuf {
-    void  *p = nullptr;
-    size_t n = 0;
-    void  *get(size_t b) {
-        if (b > n) {
-            if (p) (void)hipFree(p);
-            HIP_OR_DIE(hipMalloc(&p, b));
-            n = b;
-        }
-        return p;
-    }
-};
-thread_local ShimBuf g_lr_buf;
-
 const int kHostSgrR[16][2] = {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1},
                               {2, 1}, {2, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 1}, {2, 0}, {2, 0}};
 inline bool c_host_r0(int eps) { return kHostSgrR[eps][0] > 0; }
@@ -527,23 +513,23 @@ template <typename T>
 void wiener_shim(const T *src, ptrdiff_t ss, T *dst, ptrdiff_t ds, const int16_t *fx, const int16_t *fy, int w, int h,
                  int r0, int r1, int bd) {
     if (w <= 0 || h <= 0 || w > 64 || h > 64) svtgpu_fatal("wiener shim: block larger than 64x64");
-    const int             is = w + 8;
-    std::vector<uint16_t> in((size_t)(h + 8) * is);
+    const int    is = w + 8;
+    const size_t nin = (size_t)(h + 8) * is * 2, nout = (size_t)w * h * 2;
+    Carver       c;
+    const size_t o_in = c(nin), o_taps = c(32), o_out = c(nout);
+    hipStream_t  st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint16_t    *in = sg.host<uint16_t>(o_in);
     for (int y = -3; y < h + 5; y++)
         for (int x = -3; x < w + 5; x++) in[(size_t)(y + 3) * is + x + 3] = src[y * ss + x];
-    int16_t taps[16];
-    std::memcpy(taps, fx, 16);
-    std::memcpy(taps + 8, fy, 16);
-    uint8_t  *d    = (uint8_t *)g_lr_buf.get(in.size() * 2 + (size_t)w * h * 2 + 64);
-    uint16_t *di   = (uint16_t *)d, *dout = (uint16_t *)(d + in.size() * 2);
-    int16_t  *dt   = (int16_t *)(d + in.size() * 2 + (size_t)w * h * 2);
-    hipStream_t st = svtgpu_shim_stream();
-    HIP_OR_DIE(hipMemcpyAsync(di, in.data(), in.size() * 2, hipMemcpyHostToDevice, st));
-    HIP_OR_DIE(hipMemcpyAsync(dt, taps, 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(wiener_shim_kernel, dim3(1), dim3(NTHR), 0, st, di, is, dout, w, h, dt, bd, r0, r1);
+    std::memcpy(sg.h + o_taps, fx, 16);
+    std::memcpy(sg.h + o_taps + 16, fy, 16);
+    uint16_t *di = sg.dev<uint16_t>(o_in), *dout = sg.dev<uint16_t>(o_out);
+    HIP_OR_DIE(hipMemcpyAsync(di, in, o_taps + 32 - o_in, hipMemcpyHostToDevice, st)); // the window and the taps
+    hipLaunchKernelGGL(wiener_shim_kernel, dim3(1), dim3(NTHR), 0, st, di, is, dout, w, h, sg.dev<int16_t>(o_taps), bd, r0, r1);
     HIP_OR_DIE(hipGetLastError());
-    std::vector<uint16_t> res((size_t)w * h);
-    HIP_OR_DIE(hipMemcpyAsync(res.data(), dout, res.size() * 2, hipMemcpyDeviceToHost, st));
+    const uint16_t *res = sg.host<uint16_t>(o_out);
+    HIP_OR_DIE(hipMemcpyAsync(sg.h + o_out, dout, nout, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++) dst[y * ds + x] = (T)res[(size_t)y * w + x];
@@ -553,27 +539,27 @@ template <typename T>
 void sgr_shim(const T *src, int stride, int w, int h, int eps, const int32_t *xqd, int bd, int mode, int32_t *flt0,
               int32_t *flt1, int fstride, T *dst, int dstride) {
     if (w <= 0 || h <= 0 || w > 64 || h > 64 || eps < 0 || eps > 15) svtgpu_fatal("sgr shim: bad block");
-    const int             is = w + 6;
-    std::vector<uint16_t> in((size_t)(h + 6) * is);
+    const int    is = w + 6;
+    const size_t nb = (size_t)(h + 6) * is * 2, no = (size_t)w * h;
+    Carver       c;
+    const size_t o_in = c(nb), o_f0 = c(no * 4), o_f1 = c(no * 4), o_out = c(no * 2);
+    hipStream_t  st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint16_t    *in = sg.host<uint16_t>(o_in);
     for (int y = -3; y < h + 3; y++)
         for (int x = -3; x < w + 3; x++) in[(size_t)(y + 3) * is + x + 3] = src[y * stride + x];
-    const size_t nb = in.size() * 2, no = (size_t)w * h;
-    uint8_t     *d  = (uint8_t *)g_lr_buf.get(nb + no * 10 + 64);
-    uint16_t    *di = (uint16_t *)d;
-    int32_t     *f0 = (int32_t *)(d + ((nb + 15) & ~15)), *f1 = f0 + no;
-    uint16_t    *dout = (uint16_t *)(f1 + no);
-    hipStream_t  st   = svtgpu_shim_stream();
-    HIP_OR_DIE(hipMemcpyAsync(di, in.data(), nb, hipMemcpyHostToDevice, st));
+    uint16_t    *di = sg.dev<uint16_t>(o_in), *dout = sg.dev<uint16_t>(o_out);
+    int32_t     *f0 = sg.dev<int32_t>(o_f0), *f1 = sg.dev<int32_t>(o_f1);
+    HIP_OR_DIE(hipMemcpyAsync(di, in, nb, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(sgr_shim_kernel, dim3(1), dim3(NTHR), 0, st, di, is, w, h, eps, bd, xqd ? xqd[0] : 0,
                        xqd ? xqd[1] : 0, mode, f0, f1, dout);
     HIP_OR_DIE(hipGetLastError());
-    std::vector<int32_t>  r0(no), r1(no);
-    std::vector<uint16_t> ro(no);
-    if (mode == 0) {
-        HIP_OR_DIE(hipMemcpyAsync(r0.data(), f0, no * 4, hipMemcpyDeviceToHost, st));
-        HIP_OR_DIE(hipMemcpyAsync(r1.data(), f1, no * 4, hipMemcpyDeviceToHost, st));
-    } else
-        HIP_OR_DIE(hipMemcpyAsync(ro.data(), dout, no * 2, hipMemcpyDeviceToHost, st));
+    const int32_t  *r0 = sg.host<int32_t>(o_f0), *r1 = sg.host<int32_t>(o_f1);
+    const uint16_t *ro = sg.host<uint16_t>(o_out);
+    if (mode == 0)
+        HIP_OR_DIE(hipMemcpyAsync(sg.h + o_f0, f0, o_f1 + no * 4 - o_f0, hipMemcpyDeviceToHost, st)); // both filters
+    else
+        HIP_OR_DIE(hipMemcpyAsync(sg.h + o_out, dout, no * 2, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++) {

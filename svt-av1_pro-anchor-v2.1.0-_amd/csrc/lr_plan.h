@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/svtgpu.h"
+#include "stage_layout.h"
 
 #ifdef __HIPCC__
 #define LR_HD __host__ __device__
@@ -96,15 +97,6 @@ struct SrItem {
 constexpr int FIN_K1 = 63; // r = 1 / 2 masks: bit k < 63 = the unit k + 1 back as the reference, bit 63 = the default
 constexpr int FIN_CH = 64; // the walks: units per chunk (a lane per unit; the switchable tables staged in LDS)
 constexpr int FIN_OUT = 8; // device result words: frame types [3], search status, sequence
-
-struct Carver {
-    size_t off = 0;
-    size_t operator()(size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
 
 // The environment knobs of the search, read once per process (lr_knobs): measurements and tests set them.
 struct LrKnobs {

@@ -2400,16 +2400,9 @@ int stats_unit_mfma(int win, const T *dgd, const T *src, int h_start, int h_end,
     Carver      c;
     const size_t o_d = c(sizeof(T) * fd.size()), o_s = c(sizeof(T) * fs.size()), o_t = c(sizeof(Tile) * nt),
                  o_u = c(sizeof(URect)), o_t0 = c(8), o_sum = c(8), o_part = c(8 * (size_t)nt * nval);
-    static thread_local void  *buf = nullptr;
-    static thread_local size_t cap = 0;
-    if (c.off > cap) {
-        if (buf) (void)hipFree(buf);
-        buf = nullptr, cap = 0;
-        HIP_TRY(hipMalloc(&buf, c.off));
-        cap = c.off;
-    }
-    uint8_t    *d  = (uint8_t *)buf;
     hipStream_t st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st); // fatal on failure, as every shim's callers make it
+    uint8_t    *d  = sg.d;
     const int32_t t0[2] = {0, nt};
     HIP_TRY(hipMemcpyAsync(d + o_d, fd.data(), sizeof(T) * fd.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d + o_s, fs.data(), sizeof(T) * fs.size(), hipMemcpyHostToDevice, st));
@@ -2428,8 +2421,8 @@ int stats_unit_mfma(int win, const T *dgd, const T *src, int h_start, int h_end,
                            (const unsigned long long *)(d + o_sum), (long long *)(d + o_part), nullptr);
     });
     HIP_TRY(hipGetLastError());
-    std::vector<long long> part((size_t)nt * nval);
-    HIP_TRY(hipMemcpyAsync(part.data(), d + o_part, 8 * part.size(), hipMemcpyDeviceToHost, st));
+    const long long *part = sg.host<long long>(o_part);
+    HIP_TRY(hipMemcpyAsync(sg.h + o_part, d + o_part, 8 * (size_t)nt * nval, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<long long> blk(nval, 0);
     for (int t = 0; t < nt; t++)

@@ -19,22 +19,6 @@
 namespace {
 constexpr int kRstBits = 4, kPrjBits = 7; // SGRPROJ_RST_BITS, SGRPROJ_PRJ_BITS (EbRestoration.h:94-96)
 
-struct DevBuf { // per-thread grow-only device staging
-    void  *p   = nullptr;
-    size_t cap = 0;
-    void  *get(size_t n) {
-        if (n > cap) {
-            if (p) (void)hipFree(p);
-            HIP_OR_DIE(hipMalloc(&p, n));
-            cap = n;
-        }
-        return p;
-    }
-};
-thread_local DevBuf g_lr_scratch;
-
-inline const uint16_t *short_ptr(const uint8_t *p) { return (const uint16_t *)((uintptr_t)p << 1); }
-
 template <typename T>
 __global__ __launch_bounds__(256) void lr_sum_kernel(const T *a, int stride, int w, int h, unsigned long long *out) {
     unsigned long long s = 0;
@@ -73,16 +57,17 @@ void compute_stats(int32_t win, const T *dgd, const T *src, int32_t h_start, int
                    int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H, int div) {
     const int half = win >> 1, w = h_end - h_start, h = v_end - v_start, win2 = win * win;
     const int dw = w + 2 * half, dh = h + 2 * half;
-    std::vector<T> hd((size_t)dw * dh), hs((size_t)w * h);
+    const size_t nd = sizeof(T) * dw * dh, ns = sizeof(T) * w * h;
+    Carver       c;
+    const size_t od = c(nd), os = c(ns), osum = c(8), om = c(8 * 64), oh = c((size_t)8 * win2 * win2);
+    hipStream_t  st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    T *hd = sg.host<T>(od), *hs = sg.host<T>(os);
+    uint8_t *d = sg.d;
     for (int r = 0; r < dh; r++)
         memcpy(&hd[(size_t)r * dw], dgd + (long)(v_start - half + r) * dgd_stride + h_start - half, sizeof(T) * dw);
     for (int r = 0; r < h; r++) memcpy(&hs[(size_t)r * w], src + (long)(v_start + r) * src_stride + h_start, sizeof(T) * w);
-    const size_t od = 0, os = (hd.size() * sizeof(T) + 255) & ~(size_t)255, osum = os + ((hs.size() * sizeof(T) + 255) & ~(size_t)255);
-    const size_t om = osum + 256, oh = om + 8 * 64;
-    char        *d = (char *)g_lr_scratch.get(oh + (size_t)8 * win2 * win2);
-    hipStream_t  st = svtgpu_shim_stream();
-    HIP_OR_DIE(hipMemcpyAsync(d + od, hd.data(), hd.size() * sizeof(T), hipMemcpyHostToDevice, st));
-    HIP_OR_DIE(hipMemcpyAsync(d + os, hs.data(), hs.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_OR_DIE(hipMemcpyAsync(d + od, hd, os + ns - od, hipMemcpyHostToDevice, st)); // both, with the padding between
     HIP_OR_DIE(hipMemsetAsync(d + osum, 0, 8, st));
     const T *dd = (const T *)(d + od) + (size_t)half * dw + half;
     hipLaunchKernelGGL(lr_sum_kernel<T>, dim3(64), dim3(256), 0, st, dd, dw, w, h, (unsigned long long *)(d + osum));
@@ -143,31 +128,33 @@ __global__ __launch_bounds__(256) void proj_sub_shim_kernel(const T *src, const 
     }
 }
 
+// the four packed w x h planes of a projection shim and its result words, on the thread's stage: one upload
 template <typename T>
 struct ProjStage {
-    const T       *src, *dat;
-    const int32_t *f0, *f1;
-    char          *d;
+    Carver                 c;
+    const size_t           npx, o_src, o_dat, o_f0, o_f1, o_res;
+    const SvtGpuStageLease sg;
+    ProjStage(const T *src, int sst, const T *dat, int dst, const int32_t *flt0, int f0s, const int32_t *flt1, int f1s, int w,
+              int h, bool use0, bool use1, hipStream_t st)
+        : npx((size_t)w * h), o_src(c(npx * sizeof(T))), o_dat(c(npx * sizeof(T))), o_f0(c(npx * 4)), o_f1(c(npx * 4)),
+          o_res(c(64)), sg(svtgpu_stage_reserve(c.off, st)) {
+        auto put = [&](size_t off, const void *base, int stride, size_t es) {
+            for (int r = 0; r < h; r++)
+                memcpy(sg.h + off + (size_t)r * w * es, (const char *)base + (size_t)r * stride * es, (size_t)w * es);
+        };
+        put(o_src, src, sst, sizeof(T));
+        put(o_dat, dat, dst, sizeof(T));
+        if (use0) put(o_f0, flt0, f0s, 4);
+        if (use1) put(o_f1, flt1, f1s, 4);
+        memset(sg.h + o_res, 0, 64);
+        HIP_OR_DIE(hipMemcpyAsync(sg.d + o_src, sg.h + o_src, c.off - o_src, hipMemcpyHostToDevice, st));
+    }
+    const T            *src() const { return sg.dev<const T>(o_src); }
+    const T            *dat() const { return sg.dev<const T>(o_dat); }
+    const int32_t      *f0() const { return sg.dev<const int32_t>(o_f0); }
+    const int32_t      *f1() const { return sg.dev<const int32_t>(o_f1); }
+    unsigned long long *res() const { return sg.dev<unsigned long long>(o_res); }
 };
-template <typename T>
-ProjStage<T> stage_proj(const T *src, int sst, const T *dat, int dst, const int32_t *flt0, int f0s, const int32_t *flt1,
-                        int f1s, int w, int h, bool use0, bool use1, hipStream_t st) {
-    const size_t npx = (size_t)w * h, ot = (npx * sizeof(T) + 255) & ~(size_t)255, of = (npx * 4 + 255) & ~(size_t)255;
-    char        *d = (char *)g_lr_scratch.get(2 * ot + 2 * of + 256);
-    std::vector<char> buf(std::max(ot, of));
-    auto put = [&](size_t off, const void *base, int stride, size_t es) {
-        for (int r = 0; r < h; r++) memcpy(buf.data() + (size_t)r * w * es, (const char *)base + (size_t)r * stride * es, (size_t)w * es);
-        HIP_OR_DIE(hipMemcpyAsync(d + off, buf.data(), npx * es, hipMemcpyHostToDevice, st));
-        HIP_OR_DIE(hipStreamSynchronize(st)); // buf is reused
-    };
-    put(0, src, sst, sizeof(T));
-    put(ot, dat, dst, sizeof(T));
-    if (use0) put(2 * ot, flt0, f0s, 4);
-    if (use1) put(2 * ot + of, flt1, f1s, 4);
-    HIP_OR_DIE(hipMemsetAsync(d + 2 * ot + 2 * of, 0, 64, st));
-    return {(const T *)d, (const T *)(d + ot), (const int32_t *)(d + 2 * ot), (const int32_t *)(d + 2 * ot + of),
-            d + 2 * ot + 2 * of};
-}
 
 template <typename T, bool HBD>
 int64_t pixel_proj_error(const T *src, int32_t width, int32_t height, int32_t src_stride, const T *dat,
@@ -176,13 +163,12 @@ int64_t pixel_proj_error(const T *src, int32_t width, int32_t height, int32_t sr
     const bool  use0 = params->r[0] > 0, use1 = params->r[1] > 0;
     const int   mode = use0 && use1 ? 0 : use0 ? 1 : use1 ? 2 : 3;
     hipStream_t st   = svtgpu_shim_stream();
-    auto        S    = stage_proj<T>(src, src_stride, dat, dat_stride, flt0, flt0_stride, flt1, flt1_stride, width,
-                                     height, use0, use1, st);
-    hipLaunchKernelGGL((proj_err_shim_kernel<T, HBD>), dim3(32), dim3(256), 0, st, S.src, S.dat, S.f0, S.f1, width,
-                       height, xq[0], xq[1], mode, (unsigned long long *)S.d);
+    const ProjStage<T> S(src, src_stride, dat, dat_stride, flt0, flt0_stride, flt1, flt1_stride, width, height, use0, use1, st);
+    hipLaunchKernelGGL((proj_err_shim_kernel<T, HBD>), dim3(32), dim3(256), 0, st, S.src(), S.dat(), S.f0(), S.f1(), width,
+                       height, xq[0], xq[1], mode, S.res());
     HIP_OR_DIE(hipGetLastError());
     unsigned long long r;
-    HIP_OR_DIE(hipMemcpyAsync(&r, S.d, 8, hipMemcpyDeviceToHost, st));
+    HIP_OR_DIE(hipMemcpyAsync(&r, S.res(), 8, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     return (int64_t)r;
 }
@@ -238,17 +224,17 @@ extern "C" void svtgpu_get_proj_subspace(const uint8_t *src8, int width, int hei
     hipStream_t        st   = svtgpu_shim_stream();
     unsigned long long r[5];
     if (use_highbitdepth) {
-        auto S = stage_proj<uint16_t>(short_ptr(src8), src_stride, short_ptr(dat8), dat_stride, flt0, flt0_stride, flt1,
+        const ProjStage<uint16_t> S(short_ptr(src8), src_stride, short_ptr(dat8), dat_stride, flt0, flt0_stride, flt1,
                                       flt1_stride, width, height, use0, use1, st);
-        hipLaunchKernelGGL(proj_sub_shim_kernel<uint16_t>, dim3(32), dim3(256), 0, st, S.src, S.dat, S.f0, S.f1, width,
-                           height, (int)use0, (int)use1, (unsigned long long *)S.d);
-        HIP_OR_DIE(hipMemcpyAsync(r, S.d, sizeof r, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(proj_sub_shim_kernel<uint16_t>, dim3(32), dim3(256), 0, st, S.src(), S.dat(), S.f0(), S.f1(), width,
+                           height, (int)use0, (int)use1, S.res());
+        HIP_OR_DIE(hipMemcpyAsync(r, S.res(), sizeof r, hipMemcpyDeviceToHost, st));
     } else {
-        auto S = stage_proj<uint8_t>(src8, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, width,
+        const ProjStage<uint8_t> S(src8, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, width,
                                      height, use0, use1, st);
-        hipLaunchKernelGGL(proj_sub_shim_kernel<uint8_t>, dim3(32), dim3(256), 0, st, S.src, S.dat, S.f0, S.f1, width,
-                           height, (int)use0, (int)use1, (unsigned long long *)S.d);
-        HIP_OR_DIE(hipMemcpyAsync(r, S.d, sizeof r, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(proj_sub_shim_kernel<uint8_t>, dim3(32), dim3(256), 0, st, S.src(), S.dat(), S.f0(), S.f1(), width,
+                           height, (int)use0, (int)use1, S.res());
+        HIP_OR_DIE(hipMemcpyAsync(r, S.res(), sizeof r, hipMemcpyDeviceToHost, st));
     }
     HIP_OR_DIE(hipGetLastError());
     HIP_OR_DIE(hipStreamSynchronize(st));

@@ -211,10 +211,13 @@ void shim_mask(uint8_t *mask, int mask_type, const uint16_t *src0, int src0_stri
     if (!mask || !src0 || !src1 || !size_ok(w) || !size_ok(h) || src0_stride < w || src1_stride < w || mask_type < 0 ||
         mask_type > 1 || (bd != 8 && bd != 10 && bd != 12) || !rounds_ok(round_0, round_1))
         svtgpu_fatal("svtgpu diffwtd mask shim: bad arguments");
-    const size_t  blk = (size_t)w * h * 2, o1 = align16(blk), om = o1 + align16(blk);
+    const size_t  blk = (size_t)w * h * 2;
+    Carver        c; // src0 at 0, src1, the mask
+    c(blk);
+    const size_t  o1 = c(blk), om = c((size_t)w * h);
     hipStream_t   st = svtgpu_shim_stream();
-    uint8_t      *hb;
-    uint8_t      *d = svtgpu_compound_stage_reserve(om + (size_t)w * h, st, &hb);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t *const hb = sg.h, *const d = sg.d;
     pack_rows(hb, src0, (size_t)src0_stride * 2, (size_t)w * 2, h);
     pack_rows(hb + o1, src1, (size_t)src1_stride * 2, (size_t)w * 2, h);
     HIP_OR_DIE(hipMemcpyAsync(d, hb, om, hipMemcpyHostToDevice, st));
@@ -237,11 +240,13 @@ void shim_blend(T *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0
         (sizeof(T) == 1 ? bd != 8 : (bd != 8 && bd != 10 && bd != 12)) || !rounds_ok(round_0, round_1))
         svtgpu_fatal("svtgpu blend_a64_d16_mask shim: bad arguments");
     const int    mw = w << subw, mh = h << subh;
-    const size_t blk = (size_t)w * h * 2, o1 = align16(blk), om = o1 + align16(blk), oo = om + align16((size_t)mw * mh);
-    const size_t out = (size_t)w * h * sizeof(T);
+    const size_t blk = (size_t)w * h * 2, out = (size_t)w * h * sizeof(T);
+    Carver       c; // src0 at 0, src1, the mask, the pixels
+    c(blk);
+    const size_t o1 = c(blk), om = c((size_t)mw * mh), oo = c(out);
     hipStream_t  st = svtgpu_shim_stream();
-    uint8_t     *hb;
-    uint8_t     *d = svtgpu_compound_stage_reserve(oo + out, st, &hb);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t *const hb = sg.h, *const d = sg.d;
     // src0 / src1 may be dst itself in the reference's contract: everything is read before anything is written
     pack_rows(hb, src0, (size_t)src0_stride * 2, (size_t)w * 2, h);
     pack_rows(hb + o1, src1, (size_t)src1_stride * 2, (size_t)w * 2, h);

@@ -250,27 +250,22 @@ struct Stats {
 template <typename T>
 void block_stats(const T *a, int as, const T *const *b, int bs, int nblk, int w, int h, Stats *out) {
     const int             n = w * h;
-    std::vector<uint16_t> ha((size_t)n * nblk), hb((size_t)n * nblk);
+    const size_t half = (size_t)n * nblk * sizeof(uint16_t);
+    Carver       c;
+    const size_t o_a = c(half), o_b = c(half), o_r = c(sizeof(unsigned long long) * 3 * 4);
+    hipStream_t  st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint16_t *ha = sg.host<uint16_t>(o_a), *hb = sg.host<uint16_t>(o_b);
     for (int k = 0; k < nblk; k++)
         for (int y = 0; y < h; y++)
             for (int x = 0; x < w; x++) {
                 ha[(size_t)k * n + y * w + x] = a[(size_t)y * as + x];
                 hb[(size_t)k * n + y * w + x] = b[k][(size_t)y * bs + x];
             }
-    static thread_local uint16_t *d = nullptr;
-    static thread_local size_t    cap = 0;
-    static thread_local unsigned long long *dr = nullptr;
-    const size_t need = (size_t)2 * n * nblk * sizeof(uint16_t);
-    if (need > cap) {
-        if (d) (void)hipFree(d);
-        HIP_OR_DIE(hipMalloc(&d, need));
-        cap = need;
-    }
-    if (!dr) HIP_OR_DIE(hipMalloc(&dr, sizeof(unsigned long long) * 3 * 4));
-    hipStream_t st = svtgpu_shim_stream();
-    HIP_OR_DIE(hipMemcpyAsync(d, ha.data(), need / 2, hipMemcpyHostToDevice, st));
-    HIP_OR_DIE(hipMemcpyAsync(d + (size_t)n * nblk, hb.data(), need / 2, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(block_stats_kernel, dim3(nblk), dim3(256), 0, st, d, d + (size_t)n * nblk, n, dr);
+    unsigned long long *dr = sg.dev<unsigned long long>(o_r);
+    HIP_OR_DIE(hipMemcpyAsync(sg.d + o_a, ha, o_b + half, hipMemcpyHostToDevice, st)); // both, with the padding between
+    hipLaunchKernelGGL(block_stats_kernel, dim3(nblk), dim3(256), 0, st, sg.dev<const uint16_t>(o_a), sg.dev<const uint16_t>(o_b), n,
+                       dr);
     HIP_OR_DIE(hipGetLastError());
     unsigned long long r[12];
     HIP_OR_DIE(hipMemcpyAsync(r, dr, sizeof(unsigned long long) * 3 * nblk, hipMemcpyDeviceToHost, st));
@@ -288,7 +283,6 @@ uint32_t var10(const Stats &s, int n, unsigned int *sse) { // svt_aom_highbd_10_
     const int64_t v     = (int64_t)*sse - ((int64_t)rsum * rsum) / n;
     return v >= 0 ? (uint32_t)v : 0u;
 }
-inline const uint16_t *short_ptr(const uint8_t *p) { return (const uint16_t *)((uintptr_t)p << 1); }
 
 } // namespace
 
@@ -454,16 +448,17 @@ __global__ __launch_bounds__(256) void subpel_var_kernel(const uint8_t *a, int a
 uint32_t subpel_var(const uint8_t *a, int a_stride, int xoff, int yoff, const uint8_t *b, int b_stride, int w, int h,
                     uint32_t *sse) {
     // the first pass reads (h + 1) rows and w + 1 columns of a (the second tap multiplies by 0 at offset 0)
-    std::vector<uint8_t> ha((size_t)(h + 1) * (w + 1)), hb((size_t)h * w);
+    const size_t na = (size_t)(h + 1) * (w + 1), nb = (size_t)h * w;
+    Carver       c;
+    const size_t o_a = c(na), o_b = c(nb), o_r = c(2 * sizeof(unsigned long long));
+    hipStream_t  st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t *ha = sg.h + o_a, *hb = sg.h + o_b;
     for (int r = 0; r <= h; r++) memcpy(&ha[(size_t)r * (w + 1)], a + (long)r * a_stride, (size_t)w + 1);
     for (int r = 0; r < h; r++) memcpy(&hb[(size_t)r * w], b + (long)r * b_stride, (size_t)w);
-    hipStream_t st = svtgpu_shim_stream();
-    static thread_local uint8_t *d = nullptr;
-    if (!d) HIP_OR_DIE(hipMalloc(&d, 129 * 129 + 128 * 128 + 64));
-    unsigned long long *dr = (unsigned long long *)(d + 129 * 129 + 128 * 128 + 16);
-    HIP_OR_DIE(hipMemcpyAsync(d, ha.data(), ha.size(), hipMemcpyHostToDevice, st));
-    HIP_OR_DIE(hipMemcpyAsync(d + 129 * 129, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(subpel_var_kernel, dim3(1), dim3(256), 0, st, d, w + 1, d + 129 * 129, w, h, xoff & 7, yoff & 7, dr);
+    unsigned long long *dr = sg.dev<unsigned long long>(o_r);
+    HIP_OR_DIE(hipMemcpyAsync(sg.d + o_a, ha, o_b + nb, hipMemcpyHostToDevice, st)); // both, with the padding between
+    hipLaunchKernelGGL(subpel_var_kernel, dim3(1), dim3(256), 0, st, sg.d + o_a, w + 1, sg.d + o_b, w, h, xoff & 7, yoff & 7, dr);
     HIP_OR_DIE(hipGetLastError());
     unsigned long long r[2];
     HIP_OR_DIE(hipMemcpyAsync(r, dr, sizeof r, hipMemcpyDeviceToHost, st));

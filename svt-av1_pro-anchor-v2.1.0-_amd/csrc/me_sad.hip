@@ -248,25 +248,6 @@ __global__ __launch_bounds__(256) void sad_loop_kernel(const uint8_t *src, int s
     if ((threadIdx.x & 63) == 0) atomicMin(out, best);
 }
 
-// host staging of a strided host region as one linear device span
-struct Span {
-    uint8_t *d = nullptr;
-    ~Span() { (void)hipFree(d); }
-};
-void upload_span(hipStream_t st, Span &sp, const uint8_t *h, size_t bytes) {
-    HIP_OR_DIE(hipMalloc(&sp.d, bytes ? bytes : 1));
-    HIP_OR_DIE(hipMemcpyAsync(sp.d, h, bytes, hipMemcpyHostToDevice, st));
-}
-template <typename W>
-W *upload_words(hipStream_t st, Span &sp, const W *h, size_t n) {
-    upload_span(st, sp, (const uint8_t *)h, n * sizeof(W));
-    return (W *)sp.d;
-}
-template <typename W>
-void download_words(hipStream_t st, W *h, const Span &sp, size_t n) {
-    HIP_OR_DIE(hipMemcpyAsync(h, sp.d, n * sizeof(W), hipMemcpyDeviceToHost, st));
-}
-
 } // namespace
 
 struct SvtGpuMeBatch {
@@ -362,35 +343,37 @@ extern "C" void svtgpu_ext_all_sad_calculation_8x8_16x16(uint8_t *src, uint32_t 
                                                          uint32_t *p_best_mv16x16, uint32_t p_eight_sad16x16[16][8],
                                                          uint32_t p_eight_sad8x8[64][8], Bool sub_sad) {
     (void)p_eight_sad8x8; // not written by the reference's C either (EbMotionEstimation.c:223)
-    hipStream_t st = svtgpu_shim_stream();
-    Span        s, r, b8, b16, m8, m16, e16;
-    upload_span(st, s, src, (size_t)63 * src_stride + 64);
-    upload_span(st, r, ref, (size_t)63 * ref_stride + 64 + 7);
-    uint32_t *d8 = upload_words(st, b8, p_best_sad_8x8, 64), *d16 = upload_words(st, b16, p_best_sad_16x16, 16);
-    uint32_t *dm8 = upload_words(st, m8, p_best_mv8x8, 64), *dm16 = upload_words(st, m16, p_best_mv16x16, 16);
-    uint32_t *de = upload_words(st, e16, &p_eight_sad16x16[0][0], 128);
-    hipLaunchKernelGGL(all_sad_8x8_16x16_kernel, dim3(1), dim3(64), 0, st, s.d, (int)src_stride, r.d, (int)ref_stride,
-                       mv, d8, d16, dm8, dm16, de, (int)sub_sad);
+    hipStream_t  st = svtgpu_shim_stream();
+    const size_t ns = (size_t)63 * src_stride + 64, nr = (size_t)63 * ref_stride + 64 + 7;
+    Carver       c;
+    const size_t o_s = c(ns), o_r = c(nr), o_b8 = c(256), o_b16 = c(64), o_m8 = c(256), o_m16 = c(64), o_e = c(512);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    sg.up(o_s, src, ns, st), sg.up(o_r, ref, nr, st);
+    sg.up(o_b8, p_best_sad_8x8, 256, st), sg.up(o_b16, p_best_sad_16x16, 64, st);
+    sg.up(o_m8, p_best_mv8x8, 256, st), sg.up(o_m16, p_best_mv16x16, 64, st), sg.up(o_e, p_eight_sad16x16, 512, st);
+    hipLaunchKernelGGL(all_sad_8x8_16x16_kernel, dim3(1), dim3(64), 0, st, sg.d + o_s, (int)src_stride, sg.d + o_r,
+                       (int)ref_stride, mv, sg.dev<uint32_t>(o_b8), sg.dev<uint32_t>(o_b16), sg.dev<uint32_t>(o_m8),
+                       sg.dev<uint32_t>(o_m16), sg.dev<uint32_t>(o_e), (int)sub_sad);
     HIP_OR_DIE(hipGetLastError());
-    download_words(st, p_best_sad_8x8, b8, 64), download_words(st, p_best_sad_16x16, b16, 16);
-    download_words(st, p_best_mv8x8, m8, 64), download_words(st, p_best_mv16x16, m16, 16);
-    download_words(st, &p_eight_sad16x16[0][0], e16, 128);
+    sg.down(p_best_sad_8x8, o_b8, 256, st), sg.down(p_best_sad_16x16, o_b16, 64, st);
+    sg.down(p_best_mv8x8, o_m8, 256, st), sg.down(p_best_mv16x16, o_m16, 64, st), sg.down(p_eight_sad16x16, o_e, 512, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }
 
 static void sad_32_64(const uint32_t *sad16, int npos, uint32_t *best32, uint32_t *best64, uint32_t *mv32,
                       uint32_t *mv64, uint32_t mv, uint32_t *sad32) {
-    hipStream_t st = svtgpu_shim_stream();
-    Span        a, b32, b64, m32, m64, s32;
-    uint32_t   *da = upload_words(st, a, sad16, 16 * (size_t)npos);
-    uint32_t   *d32 = upload_words(st, b32, best32, 4), *d64 = upload_words(st, b64, best64, 1);
-    uint32_t   *dm32 = upload_words(st, m32, mv32, 4), *dm64 = upload_words(st, m64, mv64, 1);
-    uint32_t   *ds = upload_words(st, s32, sad32, 4 * (size_t)npos);
-    hipLaunchKernelGGL(sad_32x32_64x64_kernel, dim3(1), dim3(64), 0, st, da, npos, d32, d64, dm32, dm64, mv, ds);
+    hipStream_t  st = svtgpu_shim_stream();
+    const size_t na = 64 * (size_t)npos, n32 = 16 * (size_t)npos;
+    Carver       c;
+    const size_t o_a = c(na), o_b32 = c(16), o_b64 = c(4), o_m32 = c(16), o_m64 = c(4), o_s = c(n32);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    sg.up(o_a, sad16, na, st), sg.up(o_b32, best32, 16, st), sg.up(o_b64, best64, 4, st);
+    sg.up(o_m32, mv32, 16, st), sg.up(o_m64, mv64, 4, st), sg.up(o_s, sad32, n32, st);
+    hipLaunchKernelGGL(sad_32x32_64x64_kernel, dim3(1), dim3(64), 0, st, sg.dev<uint32_t>(o_a), npos, sg.dev<uint32_t>(o_b32),
+                       sg.dev<uint32_t>(o_b64), sg.dev<uint32_t>(o_m32), sg.dev<uint32_t>(o_m64), mv, sg.dev<uint32_t>(o_s));
     HIP_OR_DIE(hipGetLastError());
-    download_words(st, best32, b32, 4), download_words(st, best64, b64, 1);
-    download_words(st, mv32, m32, 4), download_words(st, mv64, m64, 1);
-    download_words(st, sad32, s32, 4 * (size_t)npos);
+    sg.down(best32, o_b32, 16, st), sg.down(best64, o_b64, 4, st);
+    sg.down(mv32, o_m32, 16, st), sg.down(mv64, o_m64, 4, st), sg.down(sad32, o_s, n32, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }
 
@@ -413,19 +396,22 @@ extern "C" void svtgpu_ext_sad_calculation_8x8_16x16(uint8_t *src, uint32_t src_
                                                      uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8,
                                                      uint32_t *p_best_mv16x16, uint32_t mv, uint32_t *p_sad16x16,
                                                      uint32_t *p_sad8x8, Bool sub_sad) {
-    hipStream_t st = svtgpu_shim_stream();
-    Span        s, r, b8, b16, m8, m16, s16, s8;
-    upload_span(st, s, src, (size_t)15 * src_stride + 16);
-    upload_span(st, r, ref, (size_t)15 * ref_stride + 16);
-    uint32_t *d8 = upload_words(st, b8, p_best_sad_8x8, 4), *d16 = upload_words(st, b16, p_best_sad_16x16, 1);
-    uint32_t *dm8 = upload_words(st, m8, p_best_mv8x8, 4), *dm16 = upload_words(st, m16, p_best_mv16x16, 1);
-    uint32_t *ds16 = upload_words(st, s16, p_sad16x16, 1), *ds8 = upload_words(st, s8, p_sad8x8, 4);
-    hipLaunchKernelGGL(sad_8x8_16x16_kernel, dim3(1), dim3(64), 0, st, s.d, (int)src_stride, r.d, (int)ref_stride, d8,
-                       d16, dm8, dm16, mv, ds16, ds8, (int)sub_sad);
+    hipStream_t  st = svtgpu_shim_stream();
+    const size_t ns = (size_t)15 * src_stride + 16, nr = (size_t)15 * ref_stride + 16;
+    Carver       c;
+    const size_t o_s = c(ns), o_r = c(nr), o_b8 = c(16), o_b16 = c(4), o_m8 = c(16), o_m16 = c(4), o_s16 = c(4), o_s8 = c(16);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    sg.up(o_s, src, ns, st), sg.up(o_r, ref, nr, st);
+    sg.up(o_b8, p_best_sad_8x8, 16, st), sg.up(o_b16, p_best_sad_16x16, 4, st);
+    sg.up(o_m8, p_best_mv8x8, 16, st), sg.up(o_m16, p_best_mv16x16, 4, st);
+    sg.up(o_s16, p_sad16x16, 4, st), sg.up(o_s8, p_sad8x8, 16, st);
+    hipLaunchKernelGGL(sad_8x8_16x16_kernel, dim3(1), dim3(64), 0, st, sg.d + o_s, (int)src_stride, sg.d + o_r,
+                       (int)ref_stride, sg.dev<uint32_t>(o_b8), sg.dev<uint32_t>(o_b16), sg.dev<uint32_t>(o_m8),
+                       sg.dev<uint32_t>(o_m16), mv, sg.dev<uint32_t>(o_s16), sg.dev<uint32_t>(o_s8), (int)sub_sad);
     HIP_OR_DIE(hipGetLastError());
-    download_words(st, p_best_sad_8x8, b8, 4), download_words(st, p_best_sad_16x16, b16, 1);
-    download_words(st, p_best_mv8x8, m8, 4), download_words(st, p_best_mv16x16, m16, 1);
-    download_words(st, p_sad16x16, s16, 1), download_words(st, p_sad8x8, s8, 4);
+    sg.down(p_best_sad_8x8, o_b8, 16, st), sg.down(p_best_sad_16x16, o_b16, 4, st);
+    sg.down(p_best_mv8x8, o_m8, 16, st), sg.down(p_best_mv16x16, o_m16, 4, st);
+    sg.down(p_sad16x16, o_s16, 4, st), sg.down(p_sad8x8, o_s8, 16, st);
     HIP_OR_DIE(hipStreamSynchronize(st));
 }
 
@@ -436,18 +422,20 @@ extern "C" void svtgpu_sad_loop_kernel(uint8_t *src, uint32_t src_stride, uint8_
                                        int16_t search_area_height) {
     *best_sad = 0xffffff;
     if (search_area_width <= 0 || search_area_height <= 0 || !block_width || !block_height) return;
-    hipStream_t st = svtgpu_shim_stream();
-    Span        s, r, o;
-    upload_span(st, s, src, (size_t)(block_height - 1) * src_stride + block_width);
-    upload_span(st, r, ref,
-                (size_t)(search_area_height - 1) * src_stride_raw + (search_area_width - 1) +
-                    (size_t)(block_height - 1) * ref_stride + block_width);
+    hipStream_t  st = svtgpu_shim_stream();
+    const size_t ns = (size_t)(block_height - 1) * src_stride + block_width;
+    const size_t nr = (size_t)(search_area_height - 1) * src_stride_raw + (search_area_width - 1) +
+                      (size_t)(block_height - 1) * ref_stride + block_width;
+    Carver       c;
+    const size_t o_s = c(ns), o_r = c(nr), o_best = c(8);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
     const unsigned long long init = ~0ull;
-    unsigned long long      *d    = upload_words(st, o, &init, 1);
+    sg.up(o_s, src, ns, st), sg.up(o_r, ref, nr, st), sg.up(o_best, &init, 8, st);
+    unsigned long long *d = sg.dev<unsigned long long>(o_best);
     const int skip = block_width == 16 && block_height <= 16 && skip_search_line;
     const int n    = search_area_width * search_area_height;
-    hipLaunchKernelGGL(sad_loop_kernel, dim3(std::min(1024, (n + 255) / 256)), dim3(256), 0, st, s.d, (int)src_stride,
-                       r.d, (int)ref_stride, (int)block_height, (int)block_width, (int)src_stride_raw, skip,
+    hipLaunchKernelGGL(sad_loop_kernel, dim3(std::min(1024, (n + 255) / 256)), dim3(256), 0, st, sg.d + o_s, (int)src_stride,
+                       sg.d + o_r, (int)ref_stride, (int)block_height, (int)block_width, (int)src_stride_raw, skip,
                        (int)search_area_width, (int)search_area_height, d);
     HIP_OR_DIE(hipGetLastError());
     unsigned long long best = 0;
@@ -552,15 +540,13 @@ extern "C" void svtgpu_pme_sad_loop_kernel(const struct svt_mv_cost_param *mv_co
     a.npos = (int)pos.size(), a.start_x = search_position_start_x, a.start_y = search_position_start_y;
     a.mvx = mvx, a.mvy = mvy, a.ref_row = mc->ref_mv[0], a.ref_col = mc->ref_mv[1], a.type = mc->mv_cost_type;
     a.epb = mc->error_per_bit;
-    Span s, r, p, o, jc, rc, cc;
-    upload_span(st, s, src, (size_t)(block_height - 1) * src_stride + block_width);
-    upload_span(st, r, ref, (size_t)(maxy + block_height - 1) * ref_stride + maxx + block_width);
-    a.src = s.d, a.ref = r.d;
-    a.pos = upload_words(st, p, pos.data(), pos.size());
-    if (a.type == 0 && mc->mvcost[0] && mc->mvcost[1] && mc->mvjcost) {
+    const size_t ns = (size_t)(block_height - 1) * src_stride + block_width;
+    const size_t nr = (size_t)(maxy + block_height - 1) * ref_stride + maxx + block_width;
+    const bool   tables = a.type == 0 && mc->mvcost[0] && mc->mvcost[1] && mc->mvjcost;
+    int          rlo = INT32_MAX, rhi = INT32_MIN, clo = INT32_MAX, chi = INT32_MIN;
+    if (tables) {
         // the clipped component indices the positions can reach
         auto clip = [](int v) { return std::min(std::max(v, -(1 << 14)), 1 << 14); };
-        int rlo = INT32_MAX, rhi = INT32_MIN, clo = INT32_MAX, chi = INT32_MIN;
         for (int32_t q : pos) {
             const int16_t col = (int16_t)(mvx + (int)(uint32_t)(search_position_start_x + (q & 0xFFFF)) * 8);
             const int16_t row = (int16_t)(mvy + (int)(uint32_t)(search_position_start_y + (q >> 16)) * 8);
@@ -568,12 +554,22 @@ extern "C" void svtgpu_pme_sad_loop_kernel(const struct svt_mv_cost_param *mv_co
             rlo = std::min(rlo, rr), rhi = std::max(rhi, rr), clo = std::min(clo, cc2), chi = std::max(chi, cc2);
         }
         a.row_lo = rlo, a.col_lo = clo;
-        a.jc = upload_words(st, jc, mc->mvjcost, 4);
-        a.rc = upload_words(st, rc, mc->mvcost[0] + rlo, (size_t)(rhi - rlo + 1));
-        a.cc = upload_words(st, cc, mc->mvcost[1] + clo, (size_t)(chi - clo + 1));
+    }
+    const size_t n_rc = tables ? 4 * (size_t)(rhi - rlo + 1) : 0, n_cc = tables ? 4 * (size_t)(chi - clo + 1) : 0;
+    const size_t n_jc = tables ? 16 : 0;
+    Carver       c;
+    const size_t o_s = c(ns), o_r = c(nr), o_pos = c(4 * pos.size()), o_jc = c(n_jc), o_rc = c(n_rc), o_cc = c(n_cc), o_best = c(8);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    sg.up(o_s, src, ns, st), sg.up(o_r, ref, nr, st), sg.up(o_pos, pos.data(), 4 * pos.size(), st);
+    a.src = sg.d + o_s, a.ref = sg.d + o_r, a.pos = sg.dev<int32_t>(o_pos);
+    if (tables) {
+        sg.up(o_jc, mc->mvjcost, n_jc, st), sg.up(o_rc, mc->mvcost[0] + rlo, n_rc, st);
+        sg.up(o_cc, mc->mvcost[1] + clo, n_cc, st);
+        a.jc = sg.dev<const int>(o_jc), a.rc = sg.dev<const int>(o_rc), a.cc = sg.dev<const int>(o_cc);
     }
     const unsigned long long init = ~0ull;
-    unsigned long long      *d    = upload_words(st, o, &init, 1);
+    sg.up(o_best, &init, 8, st);
+    unsigned long long *d = sg.dev<unsigned long long>(o_best);
     hipLaunchKernelGGL(pme_kernel, dim3(std::min(256, (a.npos + 255) / 256)), dim3(256), 0, st, a, d);
     HIP_OR_DIE(hipGetLastError());
     unsigned long long best = 0;

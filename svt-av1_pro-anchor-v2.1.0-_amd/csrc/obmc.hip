@@ -88,35 +88,25 @@ struct Totals {
     uint32_t sse;
 };
 
-// stages {wsrc, mask, result, pre rows} in one growable device buffer of the calling thread (no allocation per call
-// once it has grown to the largest block seen), runs the kernel, reads the 12-byte result back
+// stages {wsrc, mask, result, pre rows} on the calling thread's stage with one copy, runs the kernel, reads the 12-byte
+// result back
 Totals obmc_block(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, int w, int h, int subpel,
                   int xoff, int yoff) {
-    static thread_local uint8_t             *d   = nullptr;
-    static thread_local size_t               cap = 0;
-    static thread_local std::vector<uint8_t> host;
     const size_t n = (size_t)w * h, pw = subpel ? w + 1 : w, ph = subpel ? h + 1 : h;
-    const size_t off_mask = n * 4, off_out = 2 * n * 4, off_pre = off_out + 16, need = off_pre + pw * ph;
-    host.resize(need);
-    memcpy(host.data(), wsrc, n * 4);
-    memcpy(host.data() + off_mask, mask, n * 4);
-    memset(host.data() + off_out, 0, 16);
-    for (size_t r = 0; r < ph; r++) memcpy(host.data() + off_pre + r * pw, pre + (ptrdiff_t)r * pre_stride, pw);
-    hipStream_t st = svtgpu_shim_stream();
-    if (need > cap) {
-        if (d) {
-            HIP_OR_DIE(hipStreamSynchronize(st));
-            (void)hipFree(d);
-        }
-        HIP_OR_DIE(hipMalloc(&d, need));
-        cap = need;
-    }
-    HIP_OR_DIE(hipMemcpyAsync(d, host.data(), need, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(obmc_block_kernel, dim3(1), dim3(256), 0, st, d + off_pre, (const int32_t *)d,
-                       (const int32_t *)(d + off_mask), w, h, subpel, xoff & 7, yoff & 7, (uint32_t *)(d + off_out));
+    Carver       c;
+    const size_t off_wsrc = c(n * 4), off_mask = c(n * 4), off_out = c(16), off_pre = c(pw * ph);
+    hipStream_t  st = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    memcpy(sg.h + off_wsrc, wsrc, n * 4);
+    memcpy(sg.h + off_mask, mask, n * 4);
+    memset(sg.h + off_out, 0, 16);
+    for (size_t r = 0; r < ph; r++) memcpy(sg.h + off_pre + r * pw, pre + (ptrdiff_t)r * pre_stride, pw);
+    HIP_OR_DIE(hipMemcpyAsync(sg.d + off_wsrc, sg.h + off_wsrc, c.off - off_wsrc, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(obmc_block_kernel, dim3(1), dim3(256), 0, st, sg.d + off_pre, sg.dev<const int32_t>(off_wsrc),
+                       sg.dev<const int32_t>(off_mask), w, h, subpel, xoff & 7, yoff & 7, sg.dev<uint32_t>(off_out));
     HIP_OR_DIE(hipGetLastError());
     uint32_t r[3];
-    HIP_OR_DIE(hipMemcpyAsync(r, d + off_out, sizeof r, hipMemcpyDeviceToHost, st));
+    HIP_OR_DIE(hipMemcpyAsync(r, sg.d + off_out, sizeof r, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     return {r[0], (int32_t)r[1], r[2]};
 }

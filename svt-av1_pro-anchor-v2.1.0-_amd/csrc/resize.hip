@@ -374,34 +374,27 @@ int resize_dev(const void *src, int bits, int src_stride, int in_w, int in_h, vo
     return SVTGPU_OK;
 }
 
-// host planes through a device buffer of the calling thread (grown, never freed per call)
+// host planes through the calling thread's stage
 template <typename T>
 SVTGPU_ERROR_T shim_plane(const T *input, int height, int width, int in_stride, T *output, int height2, int width2,
                           int out_stride, int bd) {
     constexpr SVTGPU_ERROR_T kBadParameter = (SVTGPU_ERROR_T)0x80001005u; // EB_ErrorBadParameter
-    static thread_local uint8_t *d   = nullptr;
-    static thread_local size_t   cap = 0;
     if (!input || !output || width <= 0 || height <= 0 || width2 <= 0 || height2 <= 0 || in_stride < width ||
         out_stride < width2)
         return kBadParameter;
     const size_t ss = row_stride(width), ds = row_stride(width2), bs = sizeof(T);
-    const size_t off_dst = ss * height * bs, need = off_dst + ds * height2 * bs;
+    Carver       c;
+    const size_t off_src = c(ss * height * bs), off_dst = c(ds * height2 * bs);
     Plan1D       ph, pv;
     if (!sizes_ok((int)bs * 8, (int)ss, width, height, (int)ds, width2, height2, bd, &ph, &pv)) return kBadParameter;
     hipStream_t st = svtgpu_shim_stream();
-    if (need > cap) {
-        if (d) {
-            HIP_OR_DIE(hipStreamSynchronize(st));
-            (void)hipFree(d);
-        }
-        HIP_OR_DIE(hipMalloc(&d, need));
-        cap = need;
-    }
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t *const d = sg.d + off_src;
     HIP_OR_DIE(hipMemcpy2DAsync(d, ss * bs, input, (size_t)in_stride * bs, (size_t)width * bs, height,
                                 hipMemcpyHostToDevice, st));
-    if (resize_dev(d, (int)bs * 8, (int)ss, width, height, d + off_dst, (int)ds, width2, height2, bd, st))
+    if (resize_dev(d, (int)bs * 8, (int)ss, width, height, sg.d + off_dst, (int)ds, width2, height2, bd, st))
         svtgpu_fatal("svtgpu resize shim: the device resize failed");
-    HIP_OR_DIE(hipMemcpy2DAsync(output, (size_t)out_stride * bs, d + off_dst, ds * bs, (size_t)width2 * bs, height2,
+    HIP_OR_DIE(hipMemcpy2DAsync(output, (size_t)out_stride * bs, sg.d + off_dst, ds * bs, (size_t)width2 * bs, height2,
                                 hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     return (SVTGPU_ERROR_T)0;

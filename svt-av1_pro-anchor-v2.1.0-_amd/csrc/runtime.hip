@@ -178,6 +178,38 @@ hipStream_t svtgpu_shim_stream() {
 }
 extern "C" uint64_t svtgpu_shim_calls(void) { return g_shim_calls.load(); }
 
+// the calling thread's stage (svtgpu_internal.h): grown by stage_grown_capacity, never shrunk, freed with the thread
+namespace {
+struct ThreadStage {
+    uint8_t             *d   = nullptr;
+    size_t               cap = 0;
+    std::vector<uint8_t> h;
+    bool                 leased = false;
+    ~ThreadStage() {
+        if (d) (void)hipFree(d);
+    }
+};
+thread_local ThreadStage t_stage;
+} // namespace
+SvtGpuStageLease svtgpu_stage_reserve(size_t bytes, hipStream_t st) {
+    ThreadStage &t = t_stage;
+    if (t.leased) svtgpu_fatal("svtgpu_stage_reserve: this thread's stage is already leased to a shim call");
+    const size_t cap = stage_capacity_for(t.cap, bytes);
+    if (cap != t.cap) {
+        if (t.d) {
+            HIP_OR_DIE(hipStreamSynchronize(st)); // nothing queued may still read the old buffer
+            (void)hipFree(t.d);
+            t.d = nullptr, t.cap = 0;
+        }
+        HIP_OR_DIE(hipMalloc(&t.d, cap));
+        t.cap = cap;
+        t.h.resize(cap);
+    }
+    t.leased = true;
+    return SvtGpuStageLease(t.d, t.h.data());
+}
+SvtGpuStageLease::~SvtGpuStageLease() { t_stage.leased = false; }
+
 static std::atomic<unsigned long long> g_xfer[2];
 void svtgpu_count_xfer(int d2h, size_t bytes) { g_xfer[d2h ? 1 : 0] += bytes; }
 extern "C" int svtgpu_transfer_bytes(uint64_t *h2d, uint64_t *d2h, int32_t reset) {

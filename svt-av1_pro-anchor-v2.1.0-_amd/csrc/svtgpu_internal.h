@@ -8,6 +8,7 @@
 
 #include "../../include/svtgpu.h"
 #include "cdef_pick_plan.h"
+#include "stage_layout.h"
 
 #define SVTGPU_VERSION_STR "svtgpu 0.1.0 (gfx950)"
 
@@ -167,6 +168,31 @@ int svtgpu_launch_cdef_set_params(SvtGpuCdefFrameState *s, const SvtGpuCdefParam
 hipStream_t svtgpu_default_stream();
 // the same stream, counted as one per-block shim call (svtgpu_shim_calls): used once per RTCD shim entry point only
 hipStream_t svtgpu_shim_stream();
+// The calling thread's staging buffer for the per-block shims (runtime.hip): one grow-only device buffer and a pageable
+// host mirror of the same size per thread, freed when the thread ends.  A shim reserves all it needs in one call, carves
+// its regions with Carver (stage_layout.h) and holds the lease until it returns; its pointers are good for that long.
+// A second reserve on the thread while a lease is alive would move them, so it is fatal: a shim that calls another
+// hands it a region of its own reservation.  Failures end in svtgpu_fatal.  `st`: synchronized before a grown buffer's
+// predecessor is freed.
+struct SvtGpuStageLease {
+    uint8_t *const d, *const h; // the device buffer and its host mirror, at least the reserved bytes each
+    template <typename T> T *dev(size_t off) const { return (T *)(d + off); }
+    template <typename T> T *host(size_t off) const { return (T *)(h + off); }
+    // caller memory <-> a region of the device buffer, in stream order (shims that stage spans without repacking them)
+    void up(size_t off, const void *from, size_t bytes, hipStream_t st) const {
+        HIP_OR_DIE(hipMemcpyAsync(d + off, from, bytes, hipMemcpyHostToDevice, st));
+    }
+    void down(void *to, size_t off, size_t bytes, hipStream_t st) const {
+        HIP_OR_DIE(hipMemcpyAsync(to, d + off, bytes, hipMemcpyDeviceToHost, st));
+    }
+    SvtGpuStageLease(uint8_t *dev_buf, uint8_t *host_buf) : d(dev_buf), h(host_buf) {}
+    SvtGpuStageLease(const SvtGpuStageLease &) = delete;
+    SvtGpuStageLease &operator=(const SvtGpuStageLease &) = delete;
+    ~SvtGpuStageLease();
+};
+SvtGpuStageLease svtgpu_stage_reserve(size_t bytes, hipStream_t st);
+// CONVERT_TO_SHORTPTR: the reference passes 16-bit planes as uint8_t * holding address / 2
+static inline const uint16_t *short_ptr(const uint8_t *p) { return (const uint16_t *)((uintptr_t)p << 1); }
 // svt_av1_compute_stats(_highbd) of one unit on the matrix cores (lr_search.hip; 8- and 10-bit samples)
 int svtgpu_stats_unit_mfma8(int win, const uint8_t *dgd, const uint8_t *src, int h_start, int h_end, int v_start,
                             int v_end, int dgd_stride, int src_stride, int64_t *M, int64_t *H);

@@ -401,36 +401,23 @@ bool noise_args_ok(const void *plane, int bits, int stride, int w, int h) {
     return plane && bits_ok(bits) && w > 0 && h > 0 && stride >= w && w <= 65536 && h <= 65536;
 }
 
-// the calling thread's staging buffers (grown, never freed per call) and noise slot
-struct ThreadStage {
-    uint8_t             *d   = nullptr;
-    size_t               cap = 0;
-    std::vector<uint8_t> h;
-    NoiseSlot           *slot = nullptr;
+// The noise shim's slot stays apart from the thread's stage (svtgpu_stage_reserve): tf_noise_kernel resets sum / num /
+// ticket itself and counts on finding them so at the next launch, so the slot's content must survive between calls,
+// which a carved region of the growable buffer does not promise; the frame-level svtgpu_tf_estimate_noise uses it too, on
+// a caller's stream.  One small allocation per thread, freed with it.
+struct ThreadNoiseSlot {
+    NoiseSlot *slot = nullptr;
+    ~ThreadNoiseSlot() {
+        if (slot) (void)hipFree(slot);
+    }
 };
-thread_local ThreadStage t_stage;
-
-uint8_t *stage_reserve(size_t need, hipStream_t st) {
-    ThreadStage &t = t_stage;
-    if (need > t.cap) {
-        if (t.d) {
-            HIP_OR_DIE(hipStreamSynchronize(st));
-            (void)hipFree(t.d);
-        }
-        need = (need + (need >> 1) + 0xfff) & ~(size_t)0xfff;
-        HIP_OR_DIE(hipMalloc(&t.d, need));
-        t.cap = need;
+thread_local ThreadNoiseSlot t_noise;
+NoiseSlot *thread_noise_slot() {
+    if (!t_noise.slot) {
+        HIP_OR_DIE(hipMalloc(&t_noise.slot, sizeof(NoiseSlot)));
+        HIP_OR_DIE(hipMemset(t_noise.slot, 0, sizeof(NoiseSlot)));
     }
-    if (t.h.size() < t.cap) t.h.resize(t.cap);
-    return t.d;
-}
-NoiseSlot *stage_slot(hipStream_t st) {
-    ThreadStage &t = t_stage;
-    if (!t.slot) {
-        HIP_OR_DIE(hipMalloc(&t.slot, sizeof(NoiseSlot)));
-        HIP_OR_DIE(hipMemset(t.slot, 0, sizeof(NoiseSlot)));
-    }
-    return t.slot;
+    return t_noise.slot;
 }
 
 template <typename T>
@@ -438,8 +425,9 @@ int32_t shim_noise(const T *src, int w, int h, int stride, int bits) {
     if (!src || w <= 0 || h <= 0 || stride < w) svtgpu_fatal("svtgpu noise shim: bad arguments");
     hipStream_t  st = svtgpu_shim_stream();
     const size_t ds = ((size_t)w + 15) & ~(size_t)15, bytes = ds * h * sizeof(T);
-    uint8_t     *d  = stage_reserve(bytes, st);
-    NoiseSlot   *sl = stage_slot(st);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(bytes, st);
+    uint8_t     *d  = sg.d;
+    NoiseSlot   *sl = thread_noise_slot();
     HIP_OR_DIE(hipMemcpy2DAsync(d, ds * sizeof(T), src, (size_t)stride * sizeof(T), (size_t)w * sizeof(T), h,
                                 hipMemcpyHostToDevice, st));
     if (launch_noise(d, bits, (int)ds, w, h, sl, st)) svtgpu_fatal("svtgpu noise shim: the launch failed");
@@ -466,21 +454,20 @@ void shim_block(const SvtGpuTfBlock *blk, int idx, const SvtGpuTfParams *prm, in
     a.blk = *blk, a.idx = idx, a.nplanes = prm->tf_chroma ? 3 : 1, a.bd = bd, a.zz = zz;
     memcpy(a.decay, prm->decay_factor_fp16, sizeof a.decay);
     a.thr_shr8 = tf_threshold_shr8(prm->mv_dist_th);
-    size_t off = 0;
+    Carver c;
     for (int p = 0; p < a.nplanes; p++) {
         const int w = p ? (int)bw >> ss_x : (int)bw, h = p ? (int)bh >> ss_y : (int)bh;
         if (p && (!pre[p] || !accum[p] || !count[p] || (!zz && !src[p]))) svtgpu_fatal("svtgpu temporal filter shim: bad arguments");
         const size_t n = (size_t)w * h;
         a.p[p].w = w, a.p[p].h = h;
-        a.p[p].accum = (uint32_t)off, off += 4 * n;
-        a.p[p].src = (uint32_t)off, off += 2 * n;
-        a.p[p].pre = (uint32_t)off, off += 2 * n;
-        a.p[p].count = (uint32_t)off, off += 2 * n;
-        off = (off + 15) & ~(size_t)15;
+        a.p[p].accum = (uint32_t)c(4 * n), a.p[p].src = (uint32_t)c(2 * n), a.p[p].pre = (uint32_t)c(2 * n);
+        a.p[p].count = (uint32_t)c(2 * n);
     }
-    hipStream_t st = svtgpu_shim_stream();
-    a.buf          = stage_reserve(off, st);
-    uint8_t *hb    = t_stage.h.data();
+    const size_t off = c.off;
+    hipStream_t  st  = svtgpu_shim_stream();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(off, st);
+    a.buf        = sg.d;
+    uint8_t *hb  = sg.h;
     for (int p = 0; p < a.nplanes; p++) { // accum / count live with the predictor's stride (:1110)
         const TfPlanePack &k = a.p[p];
         if (!zz) pack_plane((uint16_t *)(hb + k.src), src[p], src_stride[p], k.w, k.h);
@@ -520,8 +507,8 @@ void shim_central(int tf_chroma, int stride_y, T *const *src, uint32_t **accum, 
     }
     // device layout: accum u32 [tot], src u16 [tot], count u16 [tot]
     hipStream_t st = svtgpu_shim_stream();
-    uint8_t    *d  = stage_reserve((size_t)tot * 8, st);
-    uint8_t    *hb = t_stage.h.data();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve((size_t)tot * 8, st);
+    uint8_t *const d = sg.d, *const hb = sg.h;
     uint16_t   *hs = (uint16_t *)(hb + (size_t)tot * 4);
     for (int p = 0, o = 0; p < np; o += n[p], p++) pack_plane(hs + o, src[p], st_[p], w[p], h[p]);
     HIP_OR_DIE(hipMemcpyAsync(d + (size_t)tot * 4, hs, (size_t)tot * 2, hipMemcpyHostToDevice, st));
@@ -722,7 +709,7 @@ extern "C" int svtgpu_tf_estimate_noise(SvtGpuContext *ctx, const void *plane, i
                                         int32_t h, void *stream, int32_t *out_fp16) {
     if (!ctx || !out_fp16 || !noise_args_ok(plane, bits, stride, w, h)) return SVTGPU_ERR_INVALID_ARG;
     hipStream_t st = pick_stream(ctx, stream);
-    NoiseSlot  *sl = stage_slot(st);
+    NoiseSlot  *sl = thread_noise_slot();
     if (int rc = launch_noise(plane, bits, stride, w, h, sl, st)) return rc;
     HIP_TRY(hipMemcpyAsync(out_fp16, &sl->result, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -917,8 +904,8 @@ extern "C" void svtgpu_tf_get_final_filtered_pixels(int32_t tf_chroma, uint8_t *
     for (int p = 0; p < np; p++) n[p] = w[p] * h[p], tot += n[p];
     // device layout: accum u32 [tot], count u16 [tot], out u16 [tot]
     hipStream_t st = svtgpu_shim_stream();
-    uint8_t    *d  = stage_reserve((size_t)tot * 8, st);
-    uint8_t    *hb = t_stage.h.data();
+    const SvtGpuStageLease sg = svtgpu_stage_reserve((size_t)tot * 8, st);
+    uint8_t *const d = sg.d, *const hb = sg.h;
     for (int p = 0, o = 0; p < np; o += n[p], p++) {
         memcpy((uint32_t *)hb + o, accum[p], (size_t)n[p] * 4);
         memcpy((uint16_t *)(hb + (size_t)tot * 4) + o, count[p], (size_t)n[p] * 2);

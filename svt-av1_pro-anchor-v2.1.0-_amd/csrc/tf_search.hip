@@ -24,12 +24,13 @@
 // sum^2 / n in uint32, vf_hbd_10 = rounded sse >> 4, rounded sum >> 2 (signed), clamped at 0; the distortion shifted left
 // by sub_sampling_shift in 32 bits; the 64-vs-32 test in uint64; derive_tf_32x32_block_split_flag (:240-289) in int.
 //
-// Bounds: reference reads go through clamp_coord into [-border, size + border - 1]; the centre is read over the 64-aligned
+// Bounds: reference reads go through clamp_i into [-border, size + border - 1]; the centre is read over the 64-aligned
 // area; window columns and rows are x + off + 1 + k with off in {-1, 0} (clamped so), k < 8, x < rs: below rs + 8; the
 // intermediate holds (rs + 7) * rs <= 39 * 32 per group; record index r * nblk + block < n_refs * nblk.
 #include <cstddef>
 #include <cstring>
 
+#include "conv_device.h"
 #include "interp_tables.h"
 #include "svtgpu_internal.h"
 
@@ -40,6 +41,8 @@ static_assert(offsetof(SvtGpuTfFullpel, mv32_x) == 4 && offsetof(SvtGpuTfFullpel
               "SvtGpuTfFullpel's members are packed in declaration order");
 
 namespace {
+
+using namespace conv_device;
 
 constexpr int      kMaxRefs = 26;
 constexpr int      kWin     = 40; // 32 + 8
@@ -70,17 +73,6 @@ struct Combine { // the 64x64 search's moments and the 32x32 errors, across the 
     uint32_t err32[4];
 };
 
-__device__ __forceinline__ int clamp_coord(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ __forceinline__ int clip_bd(int v, int bd) {
-    const int m = (1 << bd) - 1;
-    return v < 0 ? 0 : v > m ? m : v;
-}
-__device__ __forceinline__ int round_shift(int v, int n) { return (v + ((1 << n) >> 1)) >> n; }
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // vf / vf_hbd_10 of n = 1 << ln samples, then << shift in 32 bits
 __device__ __forceinline__ uint32_t variance(uint64_t sse, int64_t sum, int ln, bool hbd, int shift) {
     uint32_t v;
@@ -119,15 +111,15 @@ __device__ __forceinline__ void search_step(const SearchArgs &a, const T *__rest
     const int  lo_x = -(d.px * 16) - spel, hi_x = (a.width - d.b - d.px) * 16 + spel - 16;
     const int  lo_y = -(d.py * 16) - spel, hi_y = (a.height - d.b - d.py) * 16 + spel - 16;
     // the clamped start has phase 0: the window's column 4 / row 4 is its integer position
-    const int base_x = (int16_t)clamp_coord((int16_t)(d.mvx * 2), lo_x, hi_x) >> 4;
-    const int base_y = (int16_t)clamp_coord((int16_t)(d.mvy * 2), lo_y, hi_y) >> 4;
+    const int base_x = (int16_t)clamp_i((int16_t)(d.mvx * 2), lo_x, hi_x) >> 4;
+    const int base_y = (int16_t)clamp_i((int16_t)(d.mvy * 2), lo_y, hi_y) >> 4;
     wave_lds_sync(); // the previous step's reads before this step's stores
     {
         const int recip = (1 << 20) / ww + 1; // i / ww exactly for ww in {16, 24, 40} and i < ww * ww
         for (int i = d.sub; i < ww * ww; i += d.L) {
             const int y = (i * recip) >> 20, x = i - y * ww;
-            const int gx = clamp_coord(d.ox + base_x - 4 + x, -a.border_x, a.width + a.border_x - 1);
-            const int gy = clamp_coord(d.oy + base_y - 4 + y, -a.border_y, a.height + a.border_y - 1);
+            const int gx = clamp_i(d.ox + base_x - 4 + x, -a.border_x, a.width + a.border_x - 1);
+            const int gy = clamp_i(d.oy + base_y - 4 + y, -a.border_y, a.height + a.border_y - 1);
             lds->win[d.win + i] = ref[(ptrdiff_t)gy * rstride + gx];
         }
     }
@@ -154,9 +146,9 @@ __device__ __forceinline__ void search_step(const SearchArgs &a, const T *__rest
         }
         if (!__any(active)) continue; // uniform over the wave, and over the workgroup in the 64x64 search
         const int mvx = (int16_t)(sx + dx), mvy = (int16_t)(sy + dy);
-        const int qx = (int16_t)clamp_coord((int16_t)(mvx * 2), lo_x, hi_x), qy = (int16_t)clamp_coord((int16_t)(mvy * 2), lo_y, hi_y);
+        const int qx = (int16_t)clamp_i((int16_t)(mvx * 2), lo_x, hi_x), qy = (int16_t)clamp_i((int16_t)(mvy * 2), lo_y, hi_y);
         const int phx = qx & 15, phy = qy & 15;
-        const int offx = clamp_coord((qx >> 4) - base_x, -1, 0), offy = clamp_coord((qy >> 4) - base_y, -1, 0);
+        const int offx = clamp_i((qx >> 4) - base_x, -1, 0), offy = clamp_i((qy >> 4) - base_y, -1, 0);
         int       fx[8], fy[8];
         {
             const int4 tx = *(const int4 *)kInterpFilters[d.tab][phx], ty = *(const int4 *)kInterpFilters[d.tab][phy];

@@ -34,9 +34,9 @@
 static_assert(sizeof(SvtGpuWarpBlock) == 64, "SvtGpuWarpBlock is 64 bytes");
 static_assert(offsetof(SvtGpuWarpBlock, wmmat0) == 12 && offsetof(SvtGpuWarpBlock, wmmat1) == 36, "the models sit behind 12 bytes");
 
-using compound_tile::clamp_i;
-using compound_tile::round_shift;
-using compound_tile::wave_lds_sync;
+using conv_device::clamp_i;
+using conv_device::round_shift;
+using conv_device::wave_lds_sync;
 using compound_tile::kMaxRefs;
 
 namespace {
@@ -270,11 +270,13 @@ int shim_warp(const int32_t *mat, const uint8_t *ref8, const uint8_t *ref2, int 
             x0 = a0 < x0 ? a0 : x0, x1 = a1 > x1 ? a1 : x1, y0 = b0 < y0 ? b0 : y0, y1 = b1 > y1 ? b1 : y1;
         }
     const int    sw = x1 - x0 + 1, shh = y1 - y0 + 1;
-    const size_t win = compound_tile::align16((size_t)sw * shh * sizeof(T)), conv = (size_t)p_width * p_height * 2;
-    const size_t out = (size_t)p_width * p_height * sizeof(T), o_conv = win, o_out = o_conv + compound_tile::align16(conv);
+    const size_t win = (size_t)sw * shh * sizeof(T), conv = (size_t)p_width * p_height * 2, out = (size_t)p_width * p_height * sizeof(T);
+    Carver       c; // the rectangle at 0, then conv_dst and the pixels
+    c(win);
+    const size_t o_conv = c(conv), o_out = c(out);
     hipStream_t  st = svtgpu_shim_stream();
-    uint8_t     *hb;
-    uint8_t     *d = svtgpu_compound_stage_reserve(o_out + out, st, &hb);
+    const SvtGpuStageLease sg = svtgpu_stage_reserve(c.off, st);
+    uint8_t *const hb = sg.h, *const d = sg.d;
     for (int y = 0; y < shh; y++) {
         const uint8_t *s8 = ref8 + (ptrdiff_t)(y0 + y) * stride8 + x0;
         T             *to = (T *)hb + (size_t)y * sw;

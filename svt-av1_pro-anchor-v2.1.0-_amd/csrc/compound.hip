@@ -3,8 +3,8 @@
 // blocks of a picture (svt_aom_inter_prediction with is_compound = 1, COMPOUND_AVERAGE or COMPOUND_DISTWTD, translation,
 // unscaled references; EbEncInterPrediction.c:4070) as one launch, svtgpu_compound_predict_batch.
 //
-// The tile machinery -- units, tile passes, wave items, the LDS layout -- is csrc/compound_tile.h, shared with
-// masked_compound.hip.  Here:
+// The tile machinery -- units, tile passes, one reference's pass of a block's tile -- is csrc/compound_tile.h, shared with
+// masked_compound.hip; the items, the LDS budget and the entry's checks are csrc/pred_plan.h.  Here:
 //   combine      reference 0's values stay in the lane's registers (the same lane owns the same units in both passes, at
 //                most four of them); after reference 1's pass the lane averages or distance-weights, removes the offsets,
 //                rounds, clips and stores four samples with one vector store.  CONV_BUF_TYPE never reaches global memory.
@@ -16,7 +16,7 @@
 //
 // Bounds.  Reference reads: coordinates clamped into [-border, size + border - 1] of the plane, which the entry's contract
 // makes readable.  Predictor writes: inside the block, which the entry checked against the state's picture area and the
-// strides against that.  blocks[] and refs[] indices are checked on the host.  LDS: compound_tile.h.
+// strides against that.  blocks[] and refs[] indices are checked on the host.  LDS: pred_plan.h.
 #include "compound_tile.h"
 #include "compound_weights.h"
 
@@ -25,15 +25,6 @@ static_assert(sizeof(SvtGpuCompoundBlock) == 32, "SvtGpuCompoundBlock is 32 byte
 using namespace compound_tile;
 
 namespace {
-
-// the second pass's tail, the same in all eight functions: tmp = the first pass's CONV_BUF_TYPE value
-__device__ __forceinline__ int combine(int tmp, int res, int dist_wtd, int fwd, int bck, Rounds cr) {
-    const int offset_bits = cr.bd + 14 - cr.r0, m = (1 << cr.bd) - 1;
-    tmp = dist_wtd ? (tmp * fwd + res * bck) >> compound_weights::kDistPrecisionBits : (tmp + res) >> 1;
-    tmp -= (1 << (offset_bits - cr.r1)) + (1 << (offset_bits - cr.r1 - 1));
-    const int v = round_shift(tmp, 14 - cr.r0 - cr.r1);
-    return v < 0 ? 0 : v > m ? m : v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // the frame kernel
@@ -61,13 +52,10 @@ __global__ __launch_bounds__(256) void compound_kernel(const CompArgs a) {
     uint16_t *win = lds_all + wave * kWaveLds + slot * ((th + 7) * (tw + 8));
     int16_t  *im  = (int16_t *)(lds_all + wave * kWaveLds + kWinCap) + slot * ((th + 7) * tw);
 
-    const int    p = sl.plane, ss = p > 0, sc = 1 - ss;
-    const int    bw = 1 << b.w_log2, bh = 1 << b.h_log2, pbw = bw >> ss, pbh = bh >> ss; // the block in luma and in the plane
-    const int    pw = a.width >> ss, ph = a.height >> ss, bdx = a.border_x >> ss, bdy = a.border_y >> ss;
+    const int    p = sl.plane, ss = p > 0;
     // the block's origin in the plane: chroma at ((x >> 3) << 3) / 2 (EbEncInterPrediction.c:4269)
     const int    px = ss ? ((b.x >> 3) << 3) >> 1 : b.x, py = ss ? ((b.y >> 3) << 3) >> 1 : b.y;
     const Rounds cr = {3, 7, a.bd}; // get_conv_params_no_round(is_compound = 1) at 8 and 10 bits
-    const int    fxt = filter_table(b.filter_x, pbw), fyt = filter_table(b.filter_y, pbh);
     typedef typename Vec4<T>::type V4;
     // the plane by selects, not by a lane-varying index into the kernel arguments (that would put them in scratch)
     void *const pplane  = p == 0 ? a.pred.plane[0] : p == 1 ? a.pred.plane[1] : a.pred.plane[2];
@@ -75,17 +63,7 @@ __global__ __launch_bounds__(256) void compound_kernel(const CompArgs a) {
     T          *dst = (T *)pplane + (size_t)(py + sl.oy) * pstride + px + sl.ox;
     u16x4 first[4];
     for (int r = 0; r < 2; r++) {
-        const SvtGpuTfPlanes &rp = a.refs[r ? b.ref1 : b.ref0];
-        // clamp_mv_to_umv_border_sb (:28-48) with the block's own edges, 1/16 sample of the plane
-        int       qx = (int16_t)((r ? b.mv1_x : b.mv0_x) * (1 << sc)), qy = (int16_t)((r ? b.mv1_y : b.mv0_y) * (1 << sc));
-        const int spx = (4 + pbw) << 4, spy = (4 + pbh) << 4;
-        const int lo_x = -(b.x * 8) * (1 << sc) - spx, hi_x = ((a.width - bw - b.x) * 8) * (1 << sc) + spx - 16;
-        const int lo_y = -(b.y * 8) * (1 << sc) - spy, hi_y = ((a.height - bh - b.y) * 8) * (1 << sc) + spy - 16;
-        qx = (int16_t)clamp_i(qx, lo_x, hi_x), qy = (int16_t)clamp_i(qy, lo_y, hi_y);
-        const int phx = qx & 15, phy = qy & 15, mode = (phx ? kHorz : 0) | (phy ? kVert : 0);
-        const int sx = px + (qx >> 4) + sl.ox, sy = py + (qy >> 4) + sl.oy;
-        tile_pass<T>((const T *)rp.plane[p], rp.stride[p], -bdx, pw + bdx - 1, -bdy, ph + bdy - 1, sx, sy, twl, thl, mode,
-                     kInterpFilters[fxt][phx], kInterpFilters[fyt][phy], cr, win, im, li, lps,
+        ref_pass<T>(a, b, sl, r, px, py, twl, thl, cr, win, im, li, lps,
                      [&](int i, int y, int x4, const int res[4]) __attribute__((always_inline)) {
                          if (r == 0) {
                              first[i] = (u16x4){(uint16_t)res[0], (uint16_t)res[1], (uint16_t)res[2], (uint16_t)res[3]};
@@ -93,7 +71,7 @@ __global__ __launch_bounds__(256) void compound_kernel(const CompArgs a) {
                              V4 o;
 #pragma unroll
                              for (int j = 0; j < 4; j++)
-                                 o[j] = (T)combine(first[i][j], res[j], b.dist_wtd, b.fwd_offset, b.bck_offset, cr);
+                                 o[j] = (T)compound_average(first[i][j], res[j], b.dist_wtd, b.fwd_offset, b.bck_offset, 3, 7, a.bd);
                              *(V4 *)(dst + (size_t)y * pstride + x4) = o;
                          }
                      });
@@ -130,7 +108,8 @@ __global__ __launch_bounds__(64) void jnt_block_kernel(const JntArgs a) {
                          const u16x4 f = *(const u16x4 *)c;
                          V4          o;
 #pragma unroll
-                         for (int j = 0; j < 4; j++) o[j] = (T)combine(f[j], res[j], a.dist_wtd, a.fwd, a.bck, a.cr);
+                         for (int j = 0; j < 4; j++)
+                             o[j] = (T)compound_average(f[j], res[j], a.dist_wtd, a.fwd, a.bck, a.cr.r0, a.cr.r1, a.cr.bd);
                          *(V4 *)((T *)a.dst + (size_t)(ty + y) * a.w + tx + x4) = o;
                      }
                  });
@@ -143,7 +122,7 @@ template <typename T>
 void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, int w, int h, const int16_t *fx, const int16_t *fy,
               int round_0, int round_1, uint16_t *conv_dst, int conv_dst_stride, int do_average, int use_jnt_comp_avg,
               int fwd_offset, int bck_offset, int bd) {
-    if (!src || !conv_dst || (do_average && !dst) || !size_ok(w) || !size_ok(h) || ((mode & kHorz) && !fx) ||
+    if (!src || !conv_dst || (do_average && !dst) || !size_ok(w, 4) || !size_ok(h, 4) || ((mode & kHorz) && !fx) ||
         ((mode & kVert) && !fy) || (sizeof(T) == 1 ? bd != 8 : (bd != 10 && bd != 12)) || round_0 < 0 || round_0 > 7 ||
         round_1 < 0 || round_1 > 7 || conv_dst_stride < w)
         svtgpu_fatal("svtgpu compound convolve shim: bad arguments");
@@ -166,8 +145,7 @@ void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, in
     if (fy) memcpy(hb + o_taps + 16, fy, 16);
     size_t up = o_conv;
     if (do_average) {
-        for (int y = 0; y < h; y++)
-            memcpy(hb + o_conv + (size_t)y * w * 2, conv_dst + (ptrdiff_t)y * conv_dst_stride, (size_t)w * 2);
+        pack_rows(hb + o_conv, conv_dst, (ptrdiff_t)conv_dst_stride * 2, (size_t)w * 2, h);
         up = o_conv + conv;
     }
     HIP_OR_DIE(hipMemcpyAsync(d, hb, up, hipMemcpyHostToDevice, st));
@@ -183,11 +161,9 @@ void shim_jnt(int mode, const T *src, int src_stride, T *dst, int dst_stride, in
     HIP_OR_DIE(hipMemcpyAsync(hb + o_back, d + o_back, n_back, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     if (do_average)
-        for (int y = 0; y < h; y++)
-            memcpy(dst + (ptrdiff_t)y * dst_stride, (const T *)(hb + o_out) + (size_t)y * w, (size_t)w * sizeof(T));
+        unpack_rows(dst, (ptrdiff_t)dst_stride * sizeof(T), hb + o_out, (size_t)w * sizeof(T), h);
     else
-        for (int y = 0; y < h; y++)
-            memcpy(conv_dst + (ptrdiff_t)y * conv_dst_stride, hb + o_conv + (size_t)y * w * 2, (size_t)w * 2);
+        unpack_rows(conv_dst, (ptrdiff_t)conv_dst_stride * 2, hb + o_conv, (size_t)w * 2, h);
 }
 
 } // namespace
@@ -199,57 +175,10 @@ extern "C" int svtgpu_dist_wtd_weights(int32_t d0, int32_t d1, int32_t order_idx
 extern "C" int svtgpu_compound_predict_batch(SvtGpuTfState *s, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
                                              int32_t border_y, const SvtGpuCompoundBlock *blocks, int32_t n_blocks,
                                              int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream) {
-    if (n_refs > kMaxRefs) return SVTGPU_ERR_UNSUPPORTED;
-    if (!s || !refs || !pred || n_refs < 0 || n_blocks < 0 || (n_blocks && !blocks) || (bit_depth != 8 && bit_depth != 10) ||
-        border_x < 0 || border_y < 0)
-        return SVTGPU_ERR_INVALID_ARG;
-    SvtGpuContext *ctx;
-    int32_t        width, height, blk_cols, nblk;
-    svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
-    const int bs = bit_depth > 8 ? 2 : 1, nplanes = chroma ? 3 : 1; // without chroma planes 1 and 2 are not looked at
-    for (int p = 0; p < nplanes; p++) {
-        const int ss = p > 0;
-        for (int r = 0; r < n_refs; r++)
-            if (!refs[r].plane[p] || ((uintptr_t)refs[r].plane[p] & (bs - 1)) ||
-                refs[r].stride[p] < (width >> ss) + 2 * (border_x >> ss))
-                return SVTGPU_ERR_INVALID_ARG;
-        if (!pred->plane[p] || pred->stride[p] < (width >> ss) || (((size_t)pred->stride[p] * bs) & 15) ||
-            ((uintptr_t)pred->plane[p] & 15))
-            return SVTGPU_ERR_INVALID_ARG;
-    }
-    ItemBuilder build;
-    for (int i = 0; i < n_blocks; i++) {
-        const SvtGpuCompoundBlock &b = blocks[i];
-        if (!block_size_ok(b.w_log2, b.h_log2) || b.x < 0 || b.y < 0 || (b.x & 3) || (b.y & 3) ||
-            b.x + (1 << b.w_log2) > width || b.y + (1 << b.h_log2) > height || b.ref0 >= n_refs || b.ref1 >= n_refs ||
-            b.filter_x > 3 || b.filter_y > 3 || b.dist_wtd > 1 ||
-            (b.dist_wtd && b.fwd_offset + b.bck_offset != (1 << compound_weights::kDistPrecisionBits)))
-            return SVTGPU_ERR_INVALID_ARG;
-        for (int p = 0; p < nplanes; p++) build.add_plane((uint32_t)i, p, b.w_log2, b.h_log2);
-    }
-    if (!n_blocks) return SVTGPU_OK;
-    hipStream_t  st = pick_stream(ctx, stream);
-    const size_t n_items = build.items.size();
-    const size_t o_blk = align16((size_t)n_refs * sizeof(SvtGpuTfPlanes)), o_item = o_blk + (size_t)n_blocks * sizeof(SvtGpuCompoundBlock);
-    const size_t total = o_item + n_items * sizeof(CompItem);
-    uint8_t     *hm, *dm;
-    if (int rc = svtgpu_tf_meta_begin(s, total, &hm, &dm)) return rc;
-    memcpy(hm, refs, (size_t)n_refs * sizeof(SvtGpuTfPlanes));
-    memcpy(hm + o_blk, blocks, (size_t)n_blocks * sizeof(SvtGpuCompoundBlock));
-    memcpy(hm + o_item, build.items.data(), n_items * sizeof(CompItem));
-    if (int rc = svtgpu_tf_meta_upload(s, total, st)) return rc;
-    CompArgs a;
-    memset(&a, 0, sizeof a);
-    a.refs = (const SvtGpuTfPlanes *)dm, a.blocks = (const SvtGpuCompoundBlock *)(dm + o_blk);
-    a.items = (const CompItem *)(dm + o_item), a.pred = *pred, a.n_items = (int32_t)n_items;
-    a.width = width, a.height = height, a.border_x = border_x, a.border_y = border_y, a.bd = bit_depth;
-    const dim3 grid((unsigned)((n_items + 3) / 4));
-    if (bit_depth == 8)
-        hipLaunchKernelGGL(compound_kernel<uint8_t>, grid, dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(compound_kernel<uint16_t>, grid, dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return SVTGPU_OK;
+    return tile_batch<CompArgs>(
+        s, refs, n_refs, border_x, border_y, blocks, n_blocks, bit_depth, chroma, pred, stream, compound_kernel<uint8_t>,
+        compound_kernel<uint16_t>, [](const SvtGpuCompoundBlock &b) { return dist_wtd_ok(b.dist_wtd, b.fwd_offset, b.bck_offset); },
+        [](const SvtGpuCompoundBlock &) { return false; }, [](CompArgs &, bool) { return 0; });
 }
 
 // ---------------------------------------------------------------------------------------------

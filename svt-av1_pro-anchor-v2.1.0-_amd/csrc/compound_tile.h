@@ -12,15 +12,11 @@
 //                unit's four CONV_BUF_TYPE values from 8-byte LDS reads.  Each form restates its own C function.
 //   wave item    what one wave does: one tile of 64 or more units, or 64 / units tiles of one shape side by side, lane
 //                l on tile l / units ("slot").  So four 8x8 luma blocks, or the sixteen 4x4 chroma blocks of eight 8x8
-//                blocks, fill a wave.  The host builds the item list while it checks the blocks.
+//                blocks, fill a wave.  The host builds the item list while it checks the blocks (pred_plan::ItemBuilder).
 //
-// LDS: slot s of a wave uses window [s * (th + 7) * (tw + 8), + (th + 7) * (tw + 8)) and intermediate
-// [s * (th + 7) * tw, + (th + 7) * tw); the largest are one 32x32 tile (39 * 40 = 1560, 39 * 32 = 1248) and sixteen 4x4
-// tiles (16 * 132 = 2112, 16 * 44 = 704) <= kWinCap, kImCap.
+// The constants, the items (CompItem, ItemBuilder) and the LDS budget of a wave are pred_plan.h's; here is what runs on
+// the device with them, and the upload of a batch call's metadata.
 #pragma once
-#include <cstring>
-#include <vector>
-
 #include "conv_device.h"
 #include "interp_tables.h"
 #include "svtgpu_internal.h"
@@ -28,11 +24,8 @@
 namespace compound_tile {
 
 using namespace conv_device;
+using namespace pred_plan;
 
-constexpr int kMaxRefs = 26; // as svtgpu_tf_predict_frame
-constexpr int kTile    = 32;
-constexpr int kWinCap  = 2112, kImCap = 1248, kWaveLds = kWinCap + kImCap; // 16-bit elements per wave
-constexpr int kMaxSlots = 16;
 enum { kCopy = 0, kHorz = 1, kVert = 2, k2d = 3 };
 
 typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
@@ -173,16 +166,6 @@ __device__ __forceinline__ void tile_pass(const T *__restrict__ ref, int stride,
     wave_lds_sync(); // this pass's LDS reads before the next pass's stores
 }
 
-struct CompSlot { // one tile: block, plane, the tile's origin in the block's plane (samples)
-    uint32_t blk;
-    uint8_t  plane, ox, oy, reserved;
-};
-struct CompItem { // one wave's work: nslots tiles of 2^tw_log2 x 2^th_log2 outputs
-    CompSlot slot[kMaxSlots];
-    uint8_t  tw_log2, th_log2, nslots, reserved[13];
-};
-static_assert(sizeof(CompItem) == 144 && sizeof(CompItem) % 16 == 0, "CompItem is 144 bytes");
-
 // av1_get_interp_filter_params_with_block_size: the table of filter kind `kind` for a dimension of `size` samples
 __device__ __forceinline__ int filter_table(int kind, int size) {
     if (size <= 4 && (kind == kInterpRegular || kind == kInterpSharp)) return kInterpRegular4;
@@ -190,49 +173,66 @@ __device__ __forceinline__ int filter_table(int kind, int size) {
     return kind;
 }
 
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
-inline bool   size_ok(int v) { return v >= 4 && v <= 128 && !(v & (v - 1)); }
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// the AV1 block sizes a compound may have (is_comp_ref_allowed: min(w, h) >= 8): 8x8 .. 128x128, ratio at most 4, and
-// 128 only beside 64 or 128
-inline bool block_size_ok(int wl, int hl) {
-    if (wl < 3 || wl > 7 || hl < 3 || hl > 7) return false;
-    const int d = wl > hl ? wl - hl : hl - wl;
-    return d <= 2 && !((wl == 7 || hl == 7) && d > 1);
+// One reference (r = 0 or 1) of a tile for one lane, from what both tile kernels hold after their preamble: the block b, the
+// tile's slot sl, the block's origin (px, py) in the slot's plane; `a` the kernel's arguments; emit as tile_pass.  The
+// preamble stays in each kernel: behind a shared function the masked kernel's registers change (profiles/pred_plan_refactor).
+template <typename T, typename Args, typename Block, typename Emit>
+__device__ __forceinline__ void ref_pass(const Args &a, const Block &b, const CompSlot &sl, int r, int px, int py, int twl, int thl,
+                                         Rounds cr, uint16_t *win, int16_t *im, int li, int lps, Emit emit) {
+    const int p = sl.plane, ss = p > 0;
+    const SvtGpuTfPlanes &rp = a.refs[r ? b.ref1 : b.ref0];
+    const int bw = 1 << b.w_log2, bh = 1 << b.h_log2, pbw = bw >> ss, pbh = bh >> ss; // the block in luma and in the plane
+    const int pw = a.width >> ss, ph = a.height >> ss, bdx = a.border_x >> ss, bdy = a.border_y >> ss;
+    const int fxt = filter_table(b.filter_x, pbw), fyt = filter_table(b.filter_y, pbh);
+    const int qx = clamped_mv(r ? b.mv1_x : b.mv0_x, b.x, bw, a.width, ss);
+    const int qy = clamped_mv(r ? b.mv1_y : b.mv0_y, b.y, bh, a.height, ss);
+    const int phx = qx & 15, phy = qy & 15, mode = (phx ? kHorz : 0) | (phy ? kVert : 0);
+    const int sx = px + (qx >> 4) + sl.ox, sy = py + (qy >> 4) + sl.oy;
+    tile_pass<T>((const T *)rp.plane[p], rp.stride[p], -bdx, pw + bdx - 1, -bdy, ph + bdy - 1, sx, sy, twl, thl, mode,
+                 kInterpFilters[fxt][phx], kInterpFilters[fyt][phy], cr, win, im, li, lps, emit);
 }
 
-struct ItemBuilder { // tiles -> wave items; small tiles of one shape gathered, up to 64 / units to an item
-    std::vector<CompItem> items;
-    int                   open[3][3]; // the item still taking slots for tile shape (tw_log2 - 2, th_log2 - 2), or -1
-    ItemBuilder() {
-        for (auto &row : open)
-            for (int &v : row) v = -1;
+// The host side of a tile kernel's batch entry (Args: refs, blocks, items, pred, n_items, width, height, border_x, border_y,
+// bd): the shared checks, the item lists, the metadata, the launches.  block_ok(b): the entry's own clauses.  later(b): the
+// block's chroma tiles go to a second list, launched behind the first in the same stream.  prepare(a, has_later): the
+// entry's own kernel arguments; 0 or an error code.
+template <typename Args, typename Block, typename Ok, typename Later, typename Prepare>
+int tile_batch(SvtGpuTfState *s, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x, int32_t border_y, const Block *blocks,
+               int32_t n_blocks, int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream, void (*k8)(Args),
+               void (*k16)(Args), Ok block_ok, Later later, Prepare prepare) {
+    if (n_refs > kMaxRefs) return SVTGPU_ERR_UNSUPPORTED;
+    if (!batch_args_ok(s, refs, n_refs, blocks, n_blocks, bit_depth, pred, border_x, border_y)) return SVTGPU_ERR_INVALID_ARG;
+    SvtGpuContext *ctx;
+    int32_t        width, height, blk_cols, nblk;
+    svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
+    const int nplanes = chroma ? 3 : 1;
+    if (!check_planes(refs, n_refs, pred, width, border_x, bit_depth, nplanes)) return SVTGPU_ERR_INVALID_ARG;
+    ItemBuilder list[2];
+    for (int i = 0; i < n_blocks; i++) {
+        const Block &b = blocks[i]; // ref0 .. filter_y: what ref_pass reads of either block type
+        if (!check_block_rect(b.x, b.y, b.w_log2, b.h_log2, 4, width, height) || b.ref0 >= n_refs || b.ref1 >= n_refs ||
+            b.filter_x > 3 || b.filter_y > 3 || !block_ok(b))
+            return SVTGPU_ERR_INVALID_ARG;
+        for (int p = 0; p < nplanes; p++) list[p && later(b)].add_plane((uint32_t)i, p, b.w_log2, b.h_log2);
     }
-    void add(uint32_t blk, int plane, int ox, int oy, int twl, int thl) {
-        const int units = 1 << (twl + thl - 2), cap = units >= 64 ? 1 : 64 / units;
-        int      *slot_of = cap > 1 && twl <= 4 && thl <= 4 ? &open[twl - 2][thl - 2] : nullptr; // cap > 1 only for shapes up to 16x4 / 8x8 / 4x16
-        int       k = slot_of ? *slot_of : -1;
-        if (k < 0) {
-            CompItem it;
-            memset(&it, 0, sizeof it);
-            it.tw_log2 = (uint8_t)twl, it.th_log2 = (uint8_t)thl;
-            items.push_back(it);
-            k = (int)items.size() - 1;
-        }
-        CompItem &it = items[k];
-        CompSlot &s  = it.slot[it.nslots++];
-        s.blk = blk, s.plane = (uint8_t)plane, s.ox = (uint8_t)ox, s.oy = (uint8_t)oy;
-        if (slot_of) *slot_of = it.nslots < cap ? k : -1;
+    if (!n_blocks) return SVTGPU_OK;
+    Args a;
+    memset(&a, 0, sizeof a);
+    if (int rc = prepare(a, !list[1].items.empty())) return rc;
+    hipStream_t      st = pick_stream(ctx, stream);
+    const size_t     n[2] = {list[0].items.size(), list[1].items.size()};
+    const MetaLayout lay((size_t)n_refs, (size_t)n_blocks, sizeof(Block), n[0] + n[1], sizeof(CompItem));
+    uint8_t         *dm;
+    if (int rc = meta_upload(s, lay, refs, blocks, st, &dm, list[0].items.data(), n[0] * sizeof(CompItem), list[1].items.data()))
+        return rc;
+    a.refs = (const SvtGpuTfPlanes *)dm, a.blocks = (const Block *)(dm + lay.o_blk), a.pred = *pred;
+    a.width = width, a.height = height, a.border_x = border_x, a.border_y = border_y, a.bd = bit_depth;
+    for (int pass = 0; pass < 2; pass++) {
+        if (!n[pass]) continue;
+        a.items = (const CompItem *)(dm + lay.o_item) + (pass ? n[0] : 0), a.n_items = (int32_t)n[pass];
+        if (int rc = launch_by_depth(bit_depth, k8, k16, dim3((unsigned)((n[pass] + 3) / 4)), dim3(256), st, a)) return rc;
     }
-    // every tile (at most 32 x 32) of plane `plane` of a block of luma size 2^wl x 2^hl
-    void add_plane(uint32_t blk, int plane, int wl, int hl) {
-        const int pwl = wl - (plane > 0), phl = hl - (plane > 0), twl = pwl < 5 ? pwl : 5, thl = phl < 5 ? phl : 5;
-        for (int oy = 0; oy < (1 << phl); oy += 1 << thl)
-            for (int ox = 0; ox < (1 << pwl); ox += 1 << twl) add(blk, plane, ox, oy, twl, thl);
-    }
-};
+    return SVTGPU_OK;
+}
 
 } // namespace compound_tile

@@ -7,8 +7,7 @@
 
 namespace compound_weights {
 
-constexpr int kMaxFrameDistance  = 31; // MAX_FRAME_DISTANCE
-constexpr int kDistPrecisionBits = 4;  // DIST_PRECISION_BITS: the two offsets sum to 1 << 4
+constexpr int kMaxFrameDistance = 31; // MAX_FRAME_DISTANCE; the two offsets sum to 1 << DIST_PRECISION_BITS (pred_plan.h)
 
 constexpr int kQuantDistWeight[4][2]         = {{2, 3}, {2, 5}, {2, 7}, {1, kMaxFrameDistance}};
 constexpr int kQuantDistLookupTable[2][4][2] = {

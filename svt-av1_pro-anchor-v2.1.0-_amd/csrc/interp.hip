@@ -16,17 +16,12 @@
 //                      blocks with the same MV.  The motion record is read with a wave-uniform index (scalar loads).
 //   interp_block_kernel  the shims' kernel: one wave per 32x32 tile of the block, the same wave_region.
 //
-// MV handling restates compute_subpel_params' identity-scale branch (EbEncInterPrediction.c:3166-3177) with
-// clamp_mv_to_umv_border_sb (:28-48) and the edges of tf_*_inter_prediction (:2285-2297): the MV in 1/8 luma sample times
-// 1 << (1 - ss), cast to int16 as the reference's MV struct does, clamped to [edge - ((4 + b) << 4), edge + ((4 + b) << 4)
-// - 16] in 1/16 sample of the plane; phase = & 15, integer part = >> 4 (arithmetic).
+// MV handling restates compute_subpel_params' identity-scale branch (EbEncInterPrediction.c:3166-3177) with the edges of
+// tf_*_inter_prediction (:2285-2297); the clamp is pred_plan::clamped_mv.
 //
 // Bounds: every reference read goes through clamp_i into [-border, size + border - 1] of the plane, which the entry's
 // contract makes readable; predictor writes cover the 64-aligned area the entry checks the strides against; the motion
 // index r * nblk + b < n_refs * nblk; LDS indices are below (rh + 7) * (rw + 7) <= 39 * 39 and (rh + 7) * rw <= 39 * 32.
-#include <cstring>
-#include <vector>
-
 #include "conv_device.h"
 #include "interp_tables.h"
 #include "svtgpu_internal.h"
@@ -36,10 +31,9 @@ static_assert(sizeof(SvtGpuTfMotion) == 368 && sizeof(SvtGpuTfMotion) % 16 == 0,
 namespace {
 
 using namespace conv_device;
+using namespace pred_plan;
 
-constexpr int kMaxRefs = 26; // as svtgpu_tf_filter_frame
-constexpr int kTile    = 32; // the largest region of one wave
-constexpr int kWin     = kTile + 7;
+constexpr int kWin = kTile + 7;
 enum { kCopy = 0, kHorz = 1, kVert = 2, k2d = 3 };
 
 struct ConvRound {
@@ -143,13 +137,8 @@ __device__ __forceinline__ void predict_block(const PredArgs &a, const PredPlane
     const ConvRound cr = {3, 11, a.bd};
     const int       nplanes = a.tf_chroma ? 3 : 1;
     for (int p = 0; p < nplanes; p++) {
-        const int ss = p > 0, bp = b >> ss, sc = 1 - ss;
-        // clamp_mv_to_umv_border_sb: 1/16 sample of the plane
-        int       qx = (int16_t)(mvx * (1 << sc)), qy = (int16_t)(mvy * (1 << sc));
-        const int spel = (4 + bp) << 4;
-        const int lo_x = -(px * 8) * (1 << sc) - spel, hi_x = ((a.width - b - px) * 8) * (1 << sc) + spel - 16;
-        const int lo_y = -(py * 8) * (1 << sc) - spel, hi_y = ((a.height - b - py) * 8) * (1 << sc) + spel - 16;
-        qx = (int16_t)clamp_i(qx, lo_x, hi_x), qy = (int16_t)clamp_i(qy, lo_y, hi_y);
+        const int ss = p > 0, bp = b >> ss;
+        const int qx = clamped_mv(mvx, px, b, a.width, ss), qy = clamped_mv(mvy, py, b, a.height, ss);
         const int phx = qx & 15, phy = qy & 15;
         const int sx = (px >> ss) + (qx >> 4) + (ox >> ss), sy = (py >> ss) + (qy >> 4) + (oy >> ss);
         const int tab = bp <= 4 ? kInterpRegular4 : kInterpSharp; // MULTITAP_SHARP: the 4-tap table from w <= 4 / h <= 4
@@ -212,12 +201,10 @@ __global__ __launch_bounds__(64) void interp_block_kernel(const BlockArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-bool size_ok(int v) { return v >= 2 && v <= 128 && !(v & (v - 1)); }
-
 template <typename T>
 void shim_convolve(int mode, const T *src, int src_stride, T *dst, int dst_stride, int w, int h, const int16_t *fx,
                    const int16_t *fy, int round_0, int round_1, int bd) {
-    if (!src || !dst || !size_ok(w) || !size_ok(h) || ((mode & kHorz) && !fx) || ((mode & kVert) && !fy) ||
+    if (!src || !dst || !size_ok(w, 2) || !size_ok(h, 2) || ((mode & kHorz) && !fx) || ((mode & kVert) && !fy) ||
         (sizeof(T) == 1 ? bd != 8 : (bd != 10 && bd != 12)) || round_0 < 0 || round_0 > 7 || round_1 < 0 ||
         (mode == k2d && (round_0 + round_1 > 14 || bd + 14 - round_0 - round_1 < 1)))
         svtgpu_fatal("svtgpu interpolation shim: bad arguments");
@@ -247,7 +234,7 @@ void shim_convolve(int mode, const T *src, int src_stride, T *dst, int dst_strid
     uint8_t *ho = sg.h + o_out;
     HIP_OR_DIE(hipMemcpyAsync(ho, d + o_out, out, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
-    for (int y = 0; y < h; y++) memcpy(dst + (ptrdiff_t)y * dst_stride, (const T *)ho + (size_t)y * w, (size_t)w * sizeof(T));
+    unpack_rows(dst, (ptrdiff_t)dst_stride * sizeof(T), ho, (size_t)w * sizeof(T), h);
 }
 
 } // namespace
@@ -268,18 +255,10 @@ extern "C" int svtgpu_tf_predict_frame(SvtGpuTfState *s, const SvtGpuTfPlanes *r
     SvtGpuContext *ctx;
     int32_t        width, height, blk_cols, nblk;
     svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
-    const int bs = bit_depth > 8 ? 2 : 1, aw = blk_cols * 64;
     const int nplanes = tf_chroma ? 3 : 1; // without tf_chroma the chroma planes are neither checked nor touched
-    for (int r = 0; r < n_refs; r++)
-        for (int p = 0; p < nplanes; p++) {
-            const int ss = p > 0;
-            if (!refs[r].plane[p] || ((uintptr_t)refs[r].plane[p] & (bs - 1)) ||
-                refs[r].stride[p] < (width >> ss) + 2 * (border_x >> ss))
-                return SVTGPU_ERR_INVALID_ARG;
-            if (!pred[r].plane[p] || pred[r].stride[p] < (aw >> ss) || (((size_t)pred[r].stride[p] * bs) & 15) ||
-                ((uintptr_t)pred[r].plane[p] & 15))
-                return SVTGPU_ERR_INVALID_ARG;
-        }
+    if (!ref_planes_ok(refs, n_refs, width, border_x, bit_depth, nplanes)) return SVTGPU_ERR_INVALID_ARG;
+    for (int r = 0; r < n_refs; r++) // one predictor per reference, over the 64-aligned area
+        if (!pred_planes_ok(pred[r], blk_cols * 64, bit_depth, nplanes)) return SVTGPU_ERR_INVALID_ARG;
     if (!n_refs) return SVTGPU_OK;
     hipStream_t  st  = pick_stream(ctx, stream);
     const size_t off = (size_t)n_refs * sizeof(PredPlanes), nb = (size_t)n_refs * nblk * sizeof(SvtGpuTfMotion);
@@ -311,13 +290,8 @@ int svtgpu_tf_predict_launch(SvtGpuTfState *s, const void *d_desc, const SvtGpuT
     a.planes = (const PredPlanes *)d_desc, a.motion = d_motion;
     a.blk_cols = blk_cols, a.nblk = nblk, a.width = width, a.height = height;
     a.border_x = border_x, a.border_y = border_y, a.bd = bit_depth, a.tf_chroma = tf_chroma;
-    const dim3 grid((unsigned)(n_refs * nblk));
-    if (bit_depth == 8)
-        hipLaunchKernelGGL(tf_predict_kernel<uint8_t>, grid, dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(tf_predict_kernel<uint16_t>, grid, dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return SVTGPU_OK;
+    return launch_by_depth(bit_depth, tf_predict_kernel<uint8_t>, tf_predict_kernel<uint16_t>, dim3((unsigned)(n_refs * nblk)),
+                           dim3(256), st, a);
 }
 
 // ---------------------------------------------------------------------------------------------

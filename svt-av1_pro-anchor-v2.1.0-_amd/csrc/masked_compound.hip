@@ -5,7 +5,8 @@
 // (svt_aom_inter_prediction with a masked compound type: reference 1 through av1_make_masked_scaled_inter_predictor,
 // EbEncInterPrediction.c:50-164) as svtgpu_masked_compound_predict_batch.
 //
-// The two reference passes of a tile are compound.hip's (csrc/compound_tile.h): reference 0's CONV_BUF_TYPE values stay
+// The two reference passes of a tile are compound.hip's (ref_pass and tile_pass of csrc/compound_tile.h; the items and
+// the entry's checks are csrc/pred_plan.h): reference 0's CONV_BUF_TYPE values stay
 // in the lane's registers, and after reference 1's pass the lane blends its four samples by a 6-bit mask instead of
 // averaging them.  Where the four mask values of a unit come from:
 //   wedge, luma      wedge_masks::plan_value at the unit's four positions in the block: arithmetic on constants.
@@ -46,11 +47,7 @@ __device__ __forceinline__ int diffwtd_mask(int a, int b, int inverse, Rounds cr
 }
 // blend_a64_d16_mask's sample
 __device__ __forceinline__ int blend(int m, int s0, int s1, Rounds cr) {
-    const int offset_bits = cr.bd + 14 - cr.r0, top = (1 << cr.bd) - 1;
-    int       res = (m * s0 + (kMaxAlpha - m) * s1) >> 6; // AOM_BLEND_A64_ROUND_BITS
-    res -= (1 << (offset_bits - cr.r1)) + (1 << (offset_bits - cr.r1 - 1));
-    const int v = round_shift(res, 14 - cr.r0 - cr.r1);
-    return v < 0 ? 0 : v > top ? top : v;
+    return compound_finish((m * s0 + (kMaxAlpha - m) * s1) >> 6 /* AOM_BLEND_A64_ROUND_BITS */, cr.r0, cr.r1, cr.bd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -80,13 +77,10 @@ __global__ __launch_bounds__(256) void masked_compound_kernel(const MaskedArgs a
     uint16_t *win = lds_all + wave * kWaveLds + slot * ((th + 7) * (tw + 8));
     int16_t  *im  = (int16_t *)(lds_all + wave * kWaveLds + kWinCap) + slot * ((th + 7) * tw);
 
-    const int    p = sl.plane, ss = p > 0, sc = 1 - ss;
-    const int    bw = 1 << b.w_log2, bh = 1 << b.h_log2, pbw = bw >> ss, pbh = bh >> ss; // the block in luma and in the plane
-    const int    pw = a.width >> ss, ph = a.height >> ss, bdx = a.border_x >> ss, bdy = a.border_y >> ss;
+    const int    p = sl.plane, ss = p > 0;
     // the block's origin in the plane: chroma at ((x >> 3) << 3) / 2 (EbEncInterPrediction.c:4269)
     const int    px = ss ? ((b.x >> 3) << 3) >> 1 : b.x, py = ss ? ((b.y >> 3) << 3) >> 1 : b.y;
     const Rounds cr = {3, 7, a.bd}; // get_conv_params_no_round(is_compound = 1) at 8 and 10 bits
-    const int    fxt = filter_table(b.filter_x, pbw), fyt = filter_table(b.filter_y, pbh);
     typedef typename Vec4<T>::type V4;
     // the plane by selects, not by a lane-varying index into the kernel arguments (that would put them in scratch)
     void *const pplane  = p == 0 ? a.pred.plane[0] : p == 1 ? a.pred.plane[1] : a.pred.plane[2];
@@ -97,17 +91,7 @@ __global__ __launch_bounds__(256) void masked_compound_kernel(const MaskedArgs a
     u16x4 conv[2][4]; // the lane's CONV_BUF_TYPE values of both references: at most four units
 #pragma unroll
     for (int r = 0; r < 2; r++) {
-        const SvtGpuTfPlanes &rp = a.refs[r ? b.ref1 : b.ref0];
-        // clamp_mv_to_umv_border_sb (:28-48) with the block's own edges, 1/16 sample of the plane
-        int       qx = (int16_t)((r ? b.mv1_x : b.mv0_x) * (1 << sc)), qy = (int16_t)((r ? b.mv1_y : b.mv0_y) * (1 << sc));
-        const int spx = (4 + pbw) << 4, spy = (4 + pbh) << 4;
-        const int lo_x = -(b.x * 8) * (1 << sc) - spx, hi_x = ((a.width - bw - b.x) * 8) * (1 << sc) + spx - 16;
-        const int lo_y = -(b.y * 8) * (1 << sc) - spy, hi_y = ((a.height - bh - b.y) * 8) * (1 << sc) + spy - 16;
-        qx = (int16_t)clamp_i(qx, lo_x, hi_x), qy = (int16_t)clamp_i(qy, lo_y, hi_y);
-        const int phx = qx & 15, phy = qy & 15, mode = (phx ? kHorz : 0) | (phy ? kVert : 0);
-        const int sx = px + (qx >> 4) + sl.ox, sy = py + (qy >> 4) + sl.oy;
-        tile_pass<T>((const T *)rp.plane[p], rp.stride[p], -bdx, pw + bdx - 1, -bdy, ph + bdy - 1, sx, sy, twl, thl, mode,
-                     kInterpFilters[fxt][phx], kInterpFilters[fyt][phy], cr, win, im, li, lps,
+        ref_pass<T>(a, b, sl, r, px, py, twl, thl, cr, win, im, li, lps,
                      [&](int i, int, int, const int res[4]) __attribute__((always_inline)) {
                          conv[r][i] = (u16x4){(uint16_t)res[0], (uint16_t)res[1], (uint16_t)res[2], (uint16_t)res[3]};
                      });
@@ -196,19 +180,9 @@ __global__ __launch_bounds__(256) void blend_d16_kernel(const BlendArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-bool rounds_ok(int r0, int r1) { return r0 >= 0 && r0 <= 7 && r1 >= 0 && r1 <= 7 && 14 - r0 - r1 >= 0; }
-int  log2_of(int v) {
-    int l = 0;
-    while ((1 << l) < v) l++;
-    return l;
-}
-void pack_rows(uint8_t *to, const void *from, size_t from_stride_bytes, size_t row_bytes, int rows) {
-    for (int y = 0; y < rows; y++) memcpy(to + (size_t)y * row_bytes, (const uint8_t *)from + (size_t)y * from_stride_bytes, row_bytes);
-}
-
 void shim_mask(uint8_t *mask, int mask_type, const uint16_t *src0, int src0_stride, const uint16_t *src1, int src1_stride, int h,
                int w, int round_0, int round_1, int bd) {
-    if (!mask || !src0 || !src1 || !size_ok(w) || !size_ok(h) || src0_stride < w || src1_stride < w || mask_type < 0 ||
+    if (!mask || !src0 || !src1 || !size_ok(w, 4) || !size_ok(h, 4) || src0_stride < w || src1_stride < w || mask_type < 0 ||
         mask_type > 1 || (bd != 8 && bd != 10 && bd != 12) || !rounds_ok(round_0, round_1))
         svtgpu_fatal("svtgpu diffwtd mask shim: bad arguments");
     const size_t  blk = (size_t)w * h * 2;
@@ -235,7 +209,7 @@ void shim_mask(uint8_t *mask, int mask_type, const uint16_t *src0, int src0_stri
 template <typename T>
 void shim_blend(T *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride, const uint16_t *src1, uint32_t src1_stride,
                 const uint8_t *mask, uint32_t mask_stride, int w, int h, int subw, int subh, int round_0, int round_1, int bd) {
-    if (!dst || !src0 || !src1 || !mask || !size_ok(w) || !size_ok(h) || subw < 0 || subw > 1 || subh < 0 || subh > 1 ||
+    if (!dst || !src0 || !src1 || !mask || !size_ok(w, 4) || !size_ok(h, 4) || subw < 0 || subw > 1 || subh < 0 || subh > 1 ||
         dst_stride < (uint32_t)w || src0_stride < (uint32_t)w || src1_stride < (uint32_t)w || mask_stride < (uint32_t)(w << subw) ||
         (sizeof(T) == 1 ? bd != 8 : (bd != 8 && bd != 10 && bd != 12)) || !rounds_ok(round_0, round_1))
         svtgpu_fatal("svtgpu blend_a64_d16_mask shim: bad arguments");
@@ -260,7 +234,7 @@ void shim_blend(T *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0
     HIP_OR_DIE(hipGetLastError());
     HIP_OR_DIE(hipMemcpyAsync(hb + oo, d + oo, out, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
-    for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * dst_stride, hb + oo + (size_t)y * w * sizeof(T), (size_t)w * sizeof(T));
+    unpack_rows(dst, (ptrdiff_t)dst_stride * sizeof(T), hb + oo, (size_t)w * sizeof(T), h);
 }
 
 } // namespace
@@ -278,69 +252,17 @@ extern "C" int svtgpu_wedge_mask(int32_t w, int32_t h, int32_t wedge_index, int3
 extern "C" int svtgpu_masked_compound_predict_batch(SvtGpuTfState *s, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
                                                     int32_t border_y, const SvtGpuMaskedCompoundBlock *blocks, int32_t n_blocks,
                                                     int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream) {
-    if (n_refs > kMaxRefs) return SVTGPU_ERR_UNSUPPORTED;
-    if (!s || !refs || !pred || n_refs < 0 || n_blocks < 0 || (n_blocks && !blocks) || (bit_depth != 8 && bit_depth != 10) ||
-        border_x < 0 || border_y < 0)
-        return SVTGPU_ERR_INVALID_ARG;
-    SvtGpuContext *ctx;
-    int32_t        width, height, blk_cols, nblk;
-    svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
-    const int bs = bit_depth > 8 ? 2 : 1, nplanes = chroma ? 3 : 1; // without chroma planes 1 and 2 are not looked at
-    for (int p = 0; p < nplanes; p++) {
-        const int ss = p > 0;
-        for (int r = 0; r < n_refs; r++)
-            if (!refs[r].plane[p] || ((uintptr_t)refs[r].plane[p] & (bs - 1)) ||
-                refs[r].stride[p] < (width >> ss) + 2 * (border_x >> ss))
-                return SVTGPU_ERR_INVALID_ARG;
-        if (!pred->plane[p] || pred->stride[p] < (width >> ss) || (((size_t)pred->stride[p] * bs) & 15) ||
-            ((uintptr_t)pred->plane[p] & 15))
-            return SVTGPU_ERR_INVALID_ARG;
-    }
-    // first: every wedge tile and the DIFFWTD luma tiles; second: the DIFFWTD chroma tiles, which read the first's masks
-    ItemBuilder first, second;
-    for (int i = 0; i < n_blocks; i++) {
-        const SvtGpuMaskedCompoundBlock &b = blocks[i];
-        if (!block_size_ok(b.w_log2, b.h_log2) || b.x < 0 || b.y < 0 || (b.x & 3) || (b.y & 3) ||
-            b.x + (1 << b.w_log2) > width || b.y + (1 << b.h_log2) > height || b.ref0 >= n_refs || b.ref1 >= n_refs ||
-            b.filter_x > 3 || b.filter_y > 3 || b.comp_type > 1 || b.wedge_index >= wedge_masks::kIndices || b.wedge_sign > 1 ||
-            b.mask_type > 1 || (b.comp_type == kWedge && !wedge_masks::bits(b.w_log2, b.h_log2)))
-            return SVTGPU_ERR_INVALID_ARG;
+    auto block_ok = [](const SvtGpuMaskedCompoundBlock &b) {
         for (uint8_t v : b.reserved)
-            if (v) return SVTGPU_ERR_INVALID_ARG;
-        for (int p = 0; p < nplanes; p++) (p && b.comp_type == kDiffWtd ? second : first).add_plane((uint32_t)i, p, b.w_log2, b.h_log2);
-    }
-    if (!n_blocks) return SVTGPU_OK;
-    uint8_t *mask = nullptr;
-    if (!second.items.empty())
-        if (int rc = svtgpu_tf_mask_reserve(s, &mask)) return rc;
-    hipStream_t  st = pick_stream(ctx, stream);
-    const size_t n1 = first.items.size(), n2 = second.items.size();
-    const size_t o_blk = align16((size_t)n_refs * sizeof(SvtGpuTfPlanes)), o_item = o_blk + (size_t)n_blocks * sizeof(SvtGpuMaskedCompoundBlock);
-    const size_t total = o_item + (n1 + n2) * sizeof(CompItem);
-    uint8_t     *hm, *dm;
-    if (int rc = svtgpu_tf_meta_begin(s, total, &hm, &dm)) return rc;
-    memcpy(hm, refs, (size_t)n_refs * sizeof(SvtGpuTfPlanes));
-    memcpy(hm + o_blk, blocks, (size_t)n_blocks * sizeof(SvtGpuMaskedCompoundBlock));
-    memcpy(hm + o_item, first.items.data(), n1 * sizeof(CompItem));
-    if (n2) memcpy(hm + o_item + n1 * sizeof(CompItem), second.items.data(), n2 * sizeof(CompItem));
-    if (int rc = svtgpu_tf_meta_upload(s, total, st)) return rc;
-    MaskedArgs a;
-    memset(&a, 0, sizeof a);
-    a.refs = (const SvtGpuTfPlanes *)dm, a.blocks = (const SvtGpuMaskedCompoundBlock *)(dm + o_blk), a.mask = mask, a.pred = *pred;
-    a.width = width, a.height = height, a.border_x = border_x, a.border_y = border_y, a.bd = bit_depth;
-    const CompItem *d_items = (const CompItem *)(dm + o_item);
-    for (int pass = 0; pass < 2; pass++) {
-        const size_t n = pass ? n2 : n1;
-        if (!n) continue;
-        a.items = d_items + (pass ? n1 : 0), a.n_items = (int32_t)n;
-        const dim3 grid((unsigned)((n + 3) / 4));
-        if (bit_depth == 8)
-            hipLaunchKernelGGL(masked_compound_kernel<uint8_t>, grid, dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL(masked_compound_kernel<uint16_t>, grid, dim3(256), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return SVTGPU_OK;
+            if (v) return false;
+        return b.comp_type <= 1 && b.wedge_index < wedge_masks::kIndices && b.wedge_sign <= 1 && b.mask_type <= 1 &&
+               (b.comp_type != kWedge || wedge_masks::bits(b.w_log2, b.h_log2));
+    };
+    // the DIFFWTD chroma tiles read the masks that the luma tiles of the first launch write
+    return tile_batch<MaskedArgs>(
+        s, refs, n_refs, border_x, border_y, blocks, n_blocks, bit_depth, chroma, pred, stream, masked_compound_kernel<uint8_t>,
+        masked_compound_kernel<uint16_t>, block_ok, [](const SvtGpuMaskedCompoundBlock &b) { return b.comp_type == kDiffWtd; },
+        [&](MaskedArgs &a, bool has_later) { return has_later ? svtgpu_tf_mask_reserve(s, &a.mask) : 0; });
 }
 
 // ---------------------------------------------------------------------------------------------

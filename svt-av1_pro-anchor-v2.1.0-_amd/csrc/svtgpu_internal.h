@@ -5,9 +5,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../../include/svtgpu.h"
 #include "cdef_pick_plan.h"
+#include "pred_plan.h"
 #include "stage_layout.h"
 
 #define SVTGPU_VERSION_STR "svtgpu 0.1.0 (gfx950)"
@@ -191,6 +193,21 @@ struct SvtGpuStageLease {
     ~SvtGpuStageLease();
 };
 SvtGpuStageLease svtgpu_stage_reserve(size_t bytes, hipStream_t st);
+// `rows` rows of row_bytes each between caller memory of stride_bytes a row and a packed region of a stage's host mirror
+static inline void pack_rows(void *to, const void *from, ptrdiff_t stride_bytes, size_t row_bytes, int rows) {
+    for (int y = 0; y < rows; y++) memcpy((uint8_t *)to + y * row_bytes, (const uint8_t *)from + y * stride_bytes, row_bytes);
+}
+static inline void unpack_rows(void *to, ptrdiff_t stride_bytes, const void *from, size_t row_bytes, int rows) {
+    for (int y = 0; y < rows; y++) memcpy((uint8_t *)to + y * stride_bytes, (const uint8_t *)from + y * row_bytes, row_bytes);
+}
+// a kernel that exists once per sample type, by the bit depth
+template <typename Args>
+static inline int launch_by_depth(int bit_depth, void (*k8)(Args), void (*k16)(Args), dim3 grid, dim3 block, hipStream_t st,
+                                  const Args &a) {
+    hipLaunchKernelGGL(bit_depth == 8 ? k8 : k16, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return SVTGPU_OK;
+}
 // CONVERT_TO_SHORTPTR: the reference passes 16-bit planes as uint8_t * holding address / 2
 static inline const uint16_t *short_ptr(const uint8_t *p) { return (const uint16_t *)((uintptr_t)p << 1); }
 // svt_av1_compute_stats(_highbd) of one unit on the matrix cores (lr_search.hip; 8- and 10-bit samples)
@@ -246,6 +263,18 @@ int    svtgpu_tf_err64_launch(SvtGpuTfState *s, const SvtGpuTfPlanes *centre, co
 int    svtgpu_tf_records_reserve(SvtGpuTfState *s, int n_refs, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks);
 void   svtgpu_tf_records_commit(SvtGpuTfState *s, int n_refs); // the count _get reports: set once a search is queued
 int    svtgpu_tf_records_get(SvtGpuTfState *s, SvtGpuTfMotion **motion, SvtGpuTfBlock **blocks); // the last search's n_refs
+// A prediction batch call's metadata into that buffer by `lay` (pred_plan.h) and onto the device in stream order; a second
+// item list goes behind the first.  *dev: the buffer on the device (references at 0, blocks at lay.o_blk, items at lay.o_item).
+static inline int meta_upload(SvtGpuTfState *s, const pred_plan::MetaLayout &lay, const SvtGpuTfPlanes *refs, const void *blocks,
+                              hipStream_t st, uint8_t **dev, const void *items, size_t items_bytes, const void *more = nullptr) {
+    uint8_t *hm;
+    if (int rc = svtgpu_tf_meta_begin(s, lay.total, &hm, dev)) return rc;
+    memcpy(hm, refs, lay.ref_bytes);
+    memcpy(hm + lay.o_blk, blocks, lay.blk_bytes);
+    memcpy(hm + lay.o_item, items, items_bytes);
+    if (lay.item_bytes > items_bytes) memcpy(hm + lay.o_item + items_bytes, more, lay.item_bytes - items_bytes);
+    return svtgpu_tf_meta_upload(s, lay.total, st);
+}
 // the state's DIFFWTD mask plane (width x height bytes, stride width) for masked_compound.hip; allocated on first use
 int    svtgpu_tf_mask_reserve(SvtGpuTfState *s, uint8_t **mask);
 

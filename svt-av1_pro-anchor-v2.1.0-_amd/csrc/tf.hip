@@ -35,7 +35,7 @@
 
 namespace {
 
-constexpr int      kMaxRefs   = 26;
+using pred_plan::kMaxRefs;
 constexpr uint32_t kTfWeight  = 1000; // TF_WEIGHT_SCALE, TF_PLANEWISE_FILTER_WEIGHT_SCALE
 constexpr int      kExpfLast  = 7 * 16;
 

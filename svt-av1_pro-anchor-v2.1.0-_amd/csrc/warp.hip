@@ -1,7 +1,8 @@
 // warp.hip — AV1 warped-motion (affine) inter prediction on gfx950: svt_av1_warp_affine_c / svt_av1_highbd_warp_affine_c
 // (EbWarpedMotion.c:570, :822) behind two RTCD shims, and the warped blocks of a picture (svt_aom_warped_motion_prediction,
 // EbEncInterPrediction.c:2747, through plane_warped_motion_prediction, :2051, with no masked compound) as one launch,
-// svtgpu_warp_predict_batch.  The tables and the shear parameters are csrc/warp_params.h.
+// svtgpu_warp_predict_batch.  The tables and the shear parameters are csrc/warp_params.h; the item list and the entry's
+// checks are csrc/pred_plan.h.
 //
 //   unit         the 8x8 outputs of one plane of one block that share a projected origin: the work of one wave, lane
 //                (k, l) = (lane / 8, lane % 8) owning output row k, column l.  The origin (ix4, iy4) and the two fractional
@@ -34,10 +35,8 @@
 static_assert(sizeof(SvtGpuWarpBlock) == 64, "SvtGpuWarpBlock is 64 bytes");
 static_assert(offsetof(SvtGpuWarpBlock, wmmat0) == 12 && offsetof(SvtGpuWarpBlock, wmmat1) == 36, "the models sit behind 12 bytes");
 
-using conv_device::clamp_i;
-using conv_device::round_shift;
-using conv_device::wave_lds_sync;
-using compound_tile::kMaxRefs;
+using namespace conv_device;
+using namespace pred_plan;
 
 namespace {
 
@@ -119,16 +118,9 @@ __device__ __forceinline__ int warp_unit(const T *__restrict__ ref, int stride, 
     return sum;
 }
 
-// the three ways a sum becomes a value (the tail of the C's vertical loop)
+// how a sum becomes a value without a second reference (the tail of the C's vertical loop; with one: compound_average)
 __device__ __forceinline__ int single_pixel(int sum, const Shifts sh) { // not compound
     const int top = (1 << sh.bd) - 1, v = round_shift(sum, 14 - sh.rbh) - (1 << (sh.bd - 1)) - (1 << sh.bd);
-    return v < 0 ? 0 : v > top ? top : v;
-}
-__device__ __forceinline__ int average_pixel(int first, int second, int dist_wtd, int fwd, int bck, const Shifts sh) {
-    const int offset_bits = sh.bd + 14 - sh.r0, top = (1 << sh.bd) - 1;
-    int       t = dist_wtd ? (first * fwd + second * bck) >> compound_weights::kDistPrecisionBits : (first + second) >> 1;
-    t -= (1 << (offset_bits - sh.r1)) + (1 << (offset_bits - sh.r1 - 1));
-    const int v = round_shift(t, 14 - sh.r0 - sh.r1);
     return v < 0 ? 0 : v > top ? top : v;
 }
 
@@ -141,10 +133,6 @@ struct DevBlock { // what the kernel needs of a SvtGpuWarpBlock, with the host's
     Model   m[2];
 };
 static_assert(sizeof(DevBlock) == 76, "DevBlock is 76 bytes");
-struct WarpItem { // one workgroup: `n` units of one plane of one block, wave v on unit (ux + v % gw, uy + v / gw)
-    uint32_t blk;
-    uint8_t  plane, ux, uy, shape; // shape: gw - 1 in bit 0, n << 4
-};
 struct WarpArgs {
     const SvtGpuTfPlanes *refs;   // [n_refs]
     const DevBlock       *blocks; // [n_blocks]
@@ -160,7 +148,8 @@ __global__ __launch_bounds__(256) void warp_kernel(const WarpArgs a) {
     load_table(tab);
     const int      lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const WarpItem it = a.items[blockIdx.x];
-    const int      gw = (it.shape & 1) + 1, n = it.shape >> 4;
+    int            gw, n;
+    warp_shape_decode(it.shape, &gw, &n);
     if (wave >= n) return;
     const DevBlock &b = a.blocks[it.blk];
     const int       p = it.plane, ss = p > 0;
@@ -187,7 +176,8 @@ __global__ __launch_bounds__(256) void warp_kernel(const WarpArgs a) {
     const int sum1 = warp_unit<T>((const T *)(p == 0 ? r1.plane[0] : p == 1 ? r1.plane[1] : r1.plane[2]),
                                   p == 0 ? r1.stride[0] : p == 1 ? r1.stride[1] : r1.stride[2], pw, ph, b.m[1], ss, ss, j, i, sh, tab,
                                   patch, im, lane);
-    *dst = (T)average_pixel(first, round_shift(sum1, sh.r1), b.dist_wtd, b.fwd_offset, b.bck_offset, sh);
+    *dst = (T)compound_average(first, round_shift(sum1, sh.r1), b.dist_wtd, b.fwd_offset, b.bck_offset, sh.r0, sh.r1,
+                               sh.bd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -222,7 +212,8 @@ __global__ __launch_bounds__(256) void warp_block_kernel(const ShimArgs a) {
     else if (!a.do_average)
         a.conv[at] = (uint16_t)round_shift(sum, a.sh.r1);
     else
-        ((T *)a.dst)[at] = (T)average_pixel(a.conv[at], round_shift(sum, a.sh.r1), a.dist_wtd, a.fwd, a.bck, a.sh);
+        ((T *)a.dst)[at] = (T)compound_average(a.conv[at], round_shift(sum, a.sh.r1), a.dist_wtd, a.fwd, a.bck, a.sh.r0, a.sh.r1,
+                                               a.sh.bd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -289,8 +280,7 @@ int shim_warp(const int32_t *mat, const uint8_t *ref8, const uint8_t *ref2, int 
     }
     size_t up = win;
     if (is_compound && do_average) {
-        for (int y = 0; y < p_height; y++)
-            memcpy(hb + o_conv + (size_t)y * p_width * 2, conv_dst + (ptrdiff_t)y * conv_dst_stride, (size_t)p_width * 2);
+        pack_rows(hb + o_conv, conv_dst, (ptrdiff_t)conv_dst_stride * 2, (size_t)p_width * 2, p_height);
         up = o_conv + conv;
     }
     HIP_OR_DIE(hipMemcpyAsync(d, hb, up, hipMemcpyHostToDevice, st));
@@ -310,11 +300,9 @@ int shim_warp(const int32_t *mat, const uint8_t *ref8, const uint8_t *ref2, int 
     HIP_OR_DIE(hipMemcpyAsync(hb + o_back, d + o_back, n_back, hipMemcpyDeviceToHost, st));
     HIP_OR_DIE(hipStreamSynchronize(st));
     if (writes_pred)
-        for (int y = 0; y < p_height; y++)
-            memcpy(pred + (ptrdiff_t)y * p_stride, (const T *)(hb + o_out) + (size_t)y * p_width, (size_t)p_width * sizeof(T));
+        unpack_rows(pred, (ptrdiff_t)p_stride * sizeof(T), hb + o_out, (size_t)p_width * sizeof(T), p_height);
     else
-        for (int y = 0; y < p_height; y++)
-            memcpy(conv_dst + (ptrdiff_t)y * conv_dst_stride, hb + o_conv + (size_t)y * p_width * 2, (size_t)p_width * 2);
+        unpack_rows(conv_dst, (ptrdiff_t)conv_dst_stride * 2, hb + o_conv, (size_t)p_width * 2, p_height);
     return SVTGPU_OK;
 }
 
@@ -335,29 +323,19 @@ extern "C" int svtgpu_warp_predict_batch(SvtGpuTfState *s, const SvtGpuTfPlanes 
                                          int32_t n_blocks, int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred,
                                          void *stream) {
     if (n_refs > kMaxRefs) return SVTGPU_ERR_UNSUPPORTED;
-    if (!s || !refs || !pred || n_refs < 0 || n_blocks < 0 || (n_blocks && !blocks) || (bit_depth != 8 && bit_depth != 10))
-        return SVTGPU_ERR_INVALID_ARG;
+    if (!batch_args_ok(s, refs, n_refs, blocks, n_blocks, bit_depth, pred)) return SVTGPU_ERR_INVALID_ARG;
     SvtGpuContext *ctx;
     int32_t        width, height, blk_cols, nblk;
     svtgpu_tf_state_geometry(s, &ctx, &width, &height, &blk_cols, &nblk);
-    const int bs = bit_depth > 8 ? 2 : 1, nplanes = chroma ? 3 : 1; // without chroma planes 1 and 2 are not looked at
-    for (int p = 0; p < nplanes; p++) {
-        const int ss = p > 0;
-        for (int r = 0; r < n_refs; r++)
-            if (!refs[r].plane[p] || ((uintptr_t)refs[r].plane[p] & (bs - 1)) || refs[r].stride[p] < (width >> ss))
-                return SVTGPU_ERR_INVALID_ARG;
-        if (!pred->plane[p] || pred->stride[p] < (width >> ss) || (((size_t)pred->stride[p] * bs) & 15) ||
-            ((uintptr_t)pred->plane[p] & 15))
-            return SVTGPU_ERR_INVALID_ARG;
-    }
+    // the kernel clamps every read into the picture: no border
+    if (!check_planes(refs, n_refs, pred, width, 0, bit_depth, chroma ? 3 : 1)) return SVTGPU_ERR_INVALID_ARG;
     std::vector<DevBlock> dev((size_t)n_blocks);
     std::vector<WarpItem> items;
     for (int i = 0; i < n_blocks; i++) {
         const SvtGpuWarpBlock &b = blocks[i];
         const bool             two = b.ref1 != kNoRef;
-        if (!compound_tile::block_size_ok(b.w_log2, b.h_log2) || b.x < 0 || b.y < 0 || (b.x & 7) || (b.y & 7) || b.x + (1 << b.w_log2) > width ||
-            b.y + (1 << b.h_log2) > height || b.ref0 >= n_refs || (two && b.ref1 >= n_refs) ||
-            (two && (b.dist_wtd > 1 || (b.dist_wtd && b.fwd_offset + b.bck_offset != (1 << compound_weights::kDistPrecisionBits)))))
+        if (!check_block_rect(b.x, b.y, b.w_log2, b.h_log2, 8, width, height) || b.ref0 >= n_refs ||
+            (two && (b.ref1 >= n_refs || !dist_wtd_ok(b.dist_wtd, b.fwd_offset, b.bck_offset))))
             return SVTGPU_ERR_INVALID_ARG;
         DevBlock &d = dev[(size_t)i];
         memset(&d, 0, sizeof d);
@@ -374,38 +352,19 @@ extern "C" int svtgpu_warp_predict_batch(SvtGpuTfState *s, const SvtGpuTfPlanes 
                 if (!project(mat, 0, 0, b.x + ((c & 1) ? bw - 8 : 0), b.y + ((c & 2) ? bh - 8 : 0), &dx, &dy)) return SVTGPU_ERR_INVALID_ARG;
             }
         }
-        // chroma is warped for blocks of at least 16 x 16 (EbEncInterPrediction.c:2849); smaller ones get luma only
-        const int np = (nplanes == 3 && bw >= 16 && bh >= 16) ? 3 : 1;
-        for (int p = 0; p < np; p++) {
-            const int uw = (bw >> (p > 0)) >> 3, uh = (bh >> (p > 0)) >> 3, gw = uw >= 2 ? 2 : 1, gh = 4 / gw;
-            for (int uy = 0; uy < uh; uy += gh)
-                for (int ux = 0; ux < uw; ux += gw) {
-                    const int rows = uh - uy < gh ? uh - uy : gh;
-                    items.push_back({(uint32_t)i, (uint8_t)p, (uint8_t)ux, (uint8_t)uy, (uint8_t)((gw - 1) | ((rows * gw) << 4))});
-                }
-        }
+        warp_items((uint32_t)i, b.w_log2, b.h_log2, chroma != 0, [&](const WarpItem &it) { items.push_back(it); });
     }
     if (!n_blocks) return SVTGPU_OK;
-    hipStream_t  st = pick_stream(ctx, stream);
-    const size_t n_items = items.size();
-    const size_t o_blk = compound_tile::align16((size_t)n_refs * sizeof(SvtGpuTfPlanes)), o_item = o_blk + (size_t)n_blocks * sizeof(DevBlock);
-    const size_t total = o_item + n_items * sizeof(WarpItem);
-    uint8_t     *hm, *dm;
-    if (int rc = svtgpu_tf_meta_begin(s, total, &hm, &dm)) return rc;
-    memcpy(hm, refs, (size_t)n_refs * sizeof(SvtGpuTfPlanes));
-    memcpy(hm + o_blk, dev.data(), (size_t)n_blocks * sizeof(DevBlock));
-    memcpy(hm + o_item, items.data(), n_items * sizeof(WarpItem));
-    if (int rc = svtgpu_tf_meta_upload(s, total, st)) return rc;
+    hipStream_t      st = pick_stream(ctx, stream);
+    const MetaLayout lay((size_t)n_refs, (size_t)n_blocks, sizeof(DevBlock), items.size(), sizeof(WarpItem));
+    uint8_t         *dm;
+    if (int rc = meta_upload(s, lay, refs, dev.data(), st, &dm, items.data(), lay.item_bytes)) return rc;
     WarpArgs a;
     memset(&a, 0, sizeof a);
-    a.refs = (const SvtGpuTfPlanes *)dm, a.blocks = (const DevBlock *)(dm + o_blk), a.items = (const WarpItem *)(dm + o_item);
+    a.refs = (const SvtGpuTfPlanes *)dm, a.blocks = (const DevBlock *)(dm + lay.o_blk), a.items = (const WarpItem *)(dm + lay.o_item);
     a.pred = *pred, a.width = width, a.height = height, a.bd = bit_depth;
-    if (bit_depth == 8)
-        hipLaunchKernelGGL(warp_kernel<uint8_t>, dim3((unsigned)n_items), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(warp_kernel<uint16_t>, dim3((unsigned)n_items), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return SVTGPU_OK;
+    return launch_by_depth(bit_depth, warp_kernel<uint8_t>, warp_kernel<uint16_t>, dim3((unsigned)items.size()), dim3(256), st,
+                           a);
 }
 
 // ---------------------------------------------------------------------------------------------

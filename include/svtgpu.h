@@ -119,10 +119,12 @@ const char *svtgpu_version(void);
  * svtgpu_av1_build_compound_diffwtd_mask_d16 / svtgpu_aom_(lowbd|highbd)_blend_a64_d16_mask, svtgpu_wedge_mask,
  * SvtGpuMaskedCompoundBlock and svtgpu_masked_compound_predict_batch; 18: warped motion: the two shims
  * svtgpu_av1_warp_affine / svtgpu_av1_highbd_warp_affine, svtgpu_warp_shear_params, svtgpu_warp_filter_table, SvtGpuWarpBlock
- * and svtgpu_warp_predict_batch).
+ * and svtgpu_warp_predict_batch; 19: OBMC prediction: svtgpu_obmc_mask, SvtGpuObmcNeighbour / SvtGpuObmcBlock and
+ * svtgpu_obmc_predict_batch, the six svtgpu_aom_(highbd_)blend_a64_{v,h}mask shims,
+ * svtgpu_obmc_weighted_src_batch and svtgpu_obmc_set_items_device_wm).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
-#define SVTGPU_ABI_VERSION 18
+#define SVTGPU_ABI_VERSION 19
 int32_t     svtgpu_abi_version(void);
 const char *svtgpu_error_string(int code);
 
@@ -961,6 +963,12 @@ void svtgpu_obmc_batch_destroy(SvtGpuObmcBatch *b);
  * and uploads the list and the pools; synchronous */
 int  svtgpu_obmc_set_items(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems, const int32_t *wm_pool,
                            int32_t wm_count, const int32_t *cost_pool, int32_t cost_count, void *stream);
+/* svtgpu_obmc_set_items without the pool upload: checks and uploads the items and the costs as that entry does (the same
+ * refusals, but no pool pointer), sizes the batch's device pool to wm_count entries and returns its address in *wm_dev for
+ * svtgpu_obmc_weighted_src_batch to fill.  The address holds until a later call asks for a larger pool.  Queue the fill and
+ * svtgpu_obmc_search on one stream.  The batch type is declared above this entry's section; SvtGpuObmcBlock further down. */
+int svtgpu_obmc_set_items_device_wm(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems, int32_t wm_count,
+                                    const int32_t *cost_pool, int32_t cost_count, int32_t **wm_dev, void *stream);
 /* items [item_begin, item_end) of the current list against refs[nref] (8-bit frames of the batch's size) */
 int  svtgpu_obmc_search(SvtGpuObmcBatch *b, const SvtGpuFrame *const *refs, int32_t item_begin, int32_t item_end,
                         void *stream);
@@ -1332,7 +1340,7 @@ int svtgpu_tf_compensate_filter_frame(SvtGpuTfState *state, const SvtGpuTfPlanes
  * svt_aom_convolveHbd[][][1] tables hold), the frame-distance weights of COMPOUND_DISTWTD
  * (svt_av1_dist_wtd_comp_weight_assign, :276-318), and svt_aom_inter_prediction (EbEncInterPrediction.c:4070) with
  * is_compound = 1 for a list of blocks in one launch, bit-exact with the reference's C.  The masked compounds
- * (COMPOUND_WEDGE, COMPOUND_DIFFWTD) are the next section's; inter-intra, OBMC blending, warped and scaled references,
+ * (COMPOUND_WEDGE, COMPOUND_DIFFWTD) are the next section's; inter-intra, warped and scaled references (OBMC blending: the OBMC section),
  * intrabc and 12-bit pictures at frame level (the shims handle 12 bits) stay on the host.
  * ========================================================================================= */
 /* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
@@ -1429,7 +1437,7 @@ int svtgpu_compound_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *re
  * blends svt_aom_lowbd_blend_a64_d16_mask / svt_aom_highbd_blend_a64_d16_mask (EbBlend_a64_mask.c:34-195), the wedge masks
  * of svt_av1_init_wedge_masks (EbInterPrediction.c:1445-2132), and svt_aom_inter_prediction with a masked compound type
  * (reference 1 through av1_make_masked_scaled_inter_predictor, EbEncInterPrediction.c:50-164) for a list of blocks,
- * bit-exact with the reference's C.  Inter-intra (it needs intra prediction), OBMC blending, warped and scaled
+ * bit-exact with the reference's C.  Inter-intra (it needs intra prediction), warped and scaled
  * references, the encoder's wedge / DIFFWTD search (pick_wedge, svt_av1_wedge_sse_from_residuals) and 12-bit pictures at
  * frame level stay on the host.
  * ========================================================================================= */
@@ -1495,7 +1503,7 @@ int svtgpu_masked_compound_predict_batch(SvtGpuTfState *state, const SvtGpuTfPla
  * (EbEncInterPrediction.c:2747) for a list of blocks, bit-exact with the reference's C.  What stays on the host: finding the
  * model (svt_find_projection, svt_aom_select_samples, the global motion search), the chroma of blocks below 16 in a
  * dimension (chroma_plane_warped_motion_prediction_sub8x8, a translation), masked compounds over warped predictors
- * (av1_make_masked_warp_inter_predictor), inter-intra, OBMC blending, scaled references, and 12-bit pictures at frame level.
+ * (av1_make_masked_warp_inter_predictor), inter-intra, scaled references, and 12-bit pictures at frame level.
  * ========================================================================================= */
 /* svt_get_shear_params on the six model values wmmat (as svt_warp_plane passes them): 1 and abgd = {alpha, beta, gamma,
  * delta} when the model is valid (wmmat[2] > 0) and 4 |alpha| + 7 |beta| < 65536, 4 |gamma| + 4 |delta| < 65536; 0
@@ -1558,6 +1566,101 @@ typedef struct SvtGpuWarpBlock {          /* one warped block; 64 bytes */
  * the block's corner units, leaves int32. */
 int svtgpu_warp_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, const SvtGpuWarpBlock *blocks,
                               int32_t n_blocks, int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
+
+/* =========================================================================================
+ * AV1 OBMC (overlapped block motion compensation) prediction: the neighbour predictors of build_prediction_by_{above,left}_preds
+ * and the blend of av1_build_obmc_inter_prediction (EbEncInterPrediction.c:1144-1590) behind svt_aom_inter_prediction with
+ * motion_mode = OBMC_CAUSAL, for a list of single-reference blocks, bit-exact with the reference's C; 8- and 10-bit, 4:2:0,
+ * translation, unscaled references.  With empty neighbour lists it is the general single-reference batch predictor (the
+ * eight convolve_*_sr forms).  With them: the six per-block blends svt_aom_(highbd_)blend_a64_{v,h}mask as RTCD shims, and the
+ * weighted source and mask of svt_aom_precompute_obmc_data (calc_target_weighted_pred, :1767-1827) written on the device into
+ * the pool that svtgpu_obmc_search reads.  What stays on the host: the mode-info walk that finds the neighbours
+ * (foreach_overlappable_nb_*), the hbd_md weighted sources (10-bit strips unpacked to 8), an
+ * svt_av1_calc_target_weighted_pred_* RTCD adapter, OBMC over scaled references, inter-intra and 12-bit pictures at frame level.
+ * ========================================================================================= */
+/* RTCD shims of svt_aom_blend_a64_vmask / _hmask (EbBlend_a64_mask.c:302, :350), svt_aom_highbd_blend_a64_vmask_16bit / _hmask_16bit
+ * (C_DEFAULT/EbBlend_a64_mask_c.c:15, EbInterPrediction.c:2383) and the two _8bit forms (the same arithmetic on 16-bit samples behind
+ * a uint8_t * that is cast back, not shifted, as this encoder's C does): dst = (m * src0 + (64 - m) * src1 + 32) >> 6 with m = mask[row] (vmask) or mask[column] (hmask).
+ * Host pointers, synchronous, staged through the calling thread's buffer with one reservation.  w, h powers of two from 1 to
+ * 128; strides in elements, at least w; the mask has h (v) or w (h) bytes in 0 .. 64; bd 8, 10 or 12 (not otherwise used).
+ * src0 / src1 may alias dst: every read happens before any write.  Bad arguments are fatal, as for the other void shims. */
+void svtgpu_aom_blend_a64_vmask(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1,
+                                uint32_t src1_stride, const uint8_t *mask, int32_t w, int32_t h);
+void svtgpu_aom_blend_a64_hmask(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1,
+                                uint32_t src1_stride, const uint8_t *mask, int32_t w, int32_t h);
+void svtgpu_aom_highbd_blend_a64_vmask_16bit(uint16_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride,
+                                             const uint16_t *src1, uint32_t src1_stride, const uint8_t *mask, int32_t w, int32_t h,
+                                             int32_t bd);
+void svtgpu_aom_highbd_blend_a64_hmask_16bit(uint16_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride,
+                                             const uint16_t *src1, uint32_t src1_stride, const uint8_t *mask, int32_t w, int32_t h,
+                                             int32_t bd);
+void svtgpu_aom_highbd_blend_a64_vmask_8bit(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride,
+                                            const uint8_t *src1, uint32_t src1_stride, const uint8_t *mask, int32_t w, int32_t h,
+                                            int32_t bd);
+void svtgpu_aom_highbd_blend_a64_hmask_8bit(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride,
+                                            const uint8_t *src1, uint32_t src1_stride, const uint8_t *mask, int32_t w, int32_t h,
+                                            int32_t bd);
+/* svt_av1_get_obmc_mask: *mask points at the `length` weights of the block's own prediction, static storage; length 1, 2,
+ * 4, 8, 16 or 32.  Host only.  SVTGPU_ERR_INVALID_ARG: any other length, a null pointer. */
+int svtgpu_obmc_mask(int32_t length, const uint8_t **mask);
+typedef struct SvtGpuObmcNeighbour {      /* one overlappable neighbour span; 8 bytes */
+    uint8_t rel, size;                     /* offset along the shared edge and length, in units of 4 luma samples */
+    uint8_t ref;                           /* index into refs[]: the neighbour's ref_frame[0] */
+    uint8_t filters;                       /* filter_x | filter_y << 4, kinds as SvtGpuCompoundBlock */
+    int16_t mv_x, mv_y;                    /* the neighbour's mv[0], 1/8 luma sample */
+} SvtGpuObmcNeighbour;
+typedef struct SvtGpuObmcBlock {          /* one single-reference block with its neighbour lists; 96 bytes */
+    int16_t x, y;                          /* luma position, multiples of 8 */
+    uint8_t w_log2, h_log2;                /* luma size 8 .. 128, one of the seventeen sizes of SvtGpuCompoundBlock */
+    uint8_t ref, filter_x, filter_y;       /* the block's own reference (index into refs[]) and dual filter */
+    uint8_t n_above, n_left, reserved0;    /* spans in nb[0 .. n_above) and nb[4 .. 4 + n_left) */
+    int16_t mv_x, mv_y;                    /* the block's own MV, 1/8 luma sample */
+    int32_t wm_offset;                     /* svtgpu_obmc_weighted_src_batch: where the block's wsrc / mask go; ignored by predict */
+    uint8_t reserved[12];                  /* must be zero */
+    SvtGpuObmcNeighbour nb[8];             /* above: nb[0 .. n_above); left: nb[4 .. 4 + n_left) */
+} SvtGpuObmcBlock;
+/* The OBMC_CAUSAL blocks of one picture in one launch: for every block of blocks[n_blocks] (host memory, copied before the
+ * call returns) what svt_aom_inter_prediction writes with is_compound = 0, motion_mode = OBMC_CAUSAL and
+ * use_precomputed_obmc = 0, luma and -- with chroma != 0 -- the two 4:2:0 chroma planes at (x / 2, y / 2): the block's own
+ * prediction from refs[ref] (the convolve_*_sr form by which phases are non-zero, its MV clamp, the 4-tap tables where a
+ * dimension of the plane's block is <= 4), blended by the vertical OBMC masks with the predictions of the above spans and
+ * then by the horizontal masks with those of the left spans, each blend AOM_BLEND_A64 with its own rounding; the corner
+ * takes both, above first.  A span's prediction uses the neighbour's reference, MV and filter kinds at the block's own
+ * position; its 4-tap choice and MV clamp are those of the strip the reference predicts (along the edge the span, across it
+ * clamp(side >> (ss + 1), 4, 64 >> (ss + 1)) samples of the plane), of which only the blended (min(side, 64) >> 1) >> ss
+ * rows or columns are computed.  The chroma of a block whose chroma plane is 4x4, 8x4 or 4x8 takes no above blend
+ * (svt_av1_skip_u4x4_pred_in_obmc).  The caller walks its mode-info grid as foreach_overlappable_nb_above / _left do and
+ * lists what the walk visited: rel and size of each span (a pair of 4-wide neighbours is one span of size 2 with the
+ * second one's motion; a neighbour wider than the block has size = the block's; at most 64 luma samples per span), a compound
+ * neighbour with its first reference.  Columns or rows under no listed span keep the block's own prediction.
+ * n_above = n_left = 0 is the plain single-reference predictor of the block.
+ * `state`, refs, pred, the border and the read clamp, chroma == 0, stream order, n_blocks == 0 and overlapping blocks are
+ * svtgpu_compound_predict_batch's, word for word.
+ * SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any launch, pred untouched: a null pointer, n_refs < 0,
+ * n_blocks < 0, a bit depth other than 8 or 10, a negative border, a misaligned or too narrow plane, a block that leaves the
+ * picture area or is not at a multiple of 8, a size outside the rule, a ref index (the block's or a span's) >= n_refs, a
+ * filter kind above 3, a non-zero reserved byte, a neighbour list that is not: sizes powers of two from 2 to 16, rel even,
+ * spans ascending without overlap, rel + size <= side / 4, at most max_neighbor_obmc = {1, 2, 3, 4, 4} spans for a side of
+ * {8, 16, 32, 64, 128}, no above list at y == 0 and no left list at x == 0. */
+int svtgpu_obmc_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                              int32_t border_y, const SvtGpuObmcBlock *blocks, int32_t n_blocks, int32_t bit_depth,
+                              int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
+
+/* wsrc and mask of calc_target_weighted_pred for every block of blocks[n_blocks], 8-bit luma, on the device: wsrc to
+ * wm_dev[wm_offset .. + w * h) and mask to wm_dev[wm_offset + w * h .. + 2 * w * h), compact rows of w, the layout
+ * svtgpu_obmc_search reads through SvtGpuObmcItem::wm_offset.  Start from wsrc = 0, mask = 64; under every above span, over the
+ * blended rows, wsrc = (64 - m) * P and mask = m; both times 64; under every left span, over the blended columns, wsrc =
+ * (wsrc >> 6) * m + (P << 6) * (64 - m) and mask = (mask >> 6) * m; finally wsrc = src * 4096 - wsrc.  P are the neighbour
+ * luma strips of svtgpu_obmc_predict_batch; the block's own ref, mv and filters are not looked at.  src_luma: an 8-bit device
+ * plane at sample (0, 0) of the source picture, src_stride >= width.  wm_dev: device memory, 16-byte aligned, wm_count entries
+ * (svtgpu_obmc_set_items_device_wm hands one out).  All seventeen sizes, 8 bits only, like the OBMC distortion family; the
+ * hbd_md path stays on the host.  state, refs, border, stream order and n_blocks == 0 as svtgpu_obmc_predict_batch.
+ * SVTGPU_ERR_INVALID_ARG before any launch: that entry's refusals that do not concern the block's own ref and filters or pred,
+ * a null src_luma or wm_dev, a src_stride below the width, a wm_offset that is negative, no multiple of 4, or whose 2 * w * h
+ * entries leave wm_count. */
+int svtgpu_obmc_weighted_src_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                                   int32_t border_y, const void *src_luma, int32_t src_stride, const SvtGpuObmcBlock *blocks,
+                                   int32_t n_blocks, int32_t *wm_dev, int32_t wm_count, void *stream);
 
 /* =========================================================================================
  * Loop restoration

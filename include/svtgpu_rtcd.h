@@ -15,6 +15,7 @@
  *         svtgpu_install_resize_rtcd();                   // svt_av1_resize_plane / svt_av1_highbd_resize_plane
  *         svtgpu_install_tf_rtcd();                       // the temporal filter's nine pointers (define
  *                                                         //   SVTGPU_RTCD_WITH_TF before including this header)
+ *         svtgpu_install_obmc_blend_rtcd();               // the six OBMC blends (define SVTGPU_RTCD_WITH_OBMC_BLEND)
  *         svtgpu_install_masked_compound_rtcd();          // the DIFFWTD mask and the two blend_a64_d16_mask (define
  *                                                         // SVTGPU_RTCD_WITH_MASKED_COMPOUND first)
  *         svtgpu_install_warp_rtcd();                     // svt_av1_warp_affine / svt_av1_highbd_warp_affine (define
@@ -573,6 +574,50 @@ static inline int svtgpu_masked_compound_rtcd_bound(int i) {
     }
 }
 #endif /* SVTGPU_RTCD_WITH_MASKED_COMPOUND */
+/* The OBMC blends (common_dsp_rtcd.h: svt_aom_blend_a64_vmask / _hmask, svt_aom_highbd_blend_a64_vmask_16bit / _hmask_16bit,
+ * svt_aom_highbd_blend_a64_vmask_8bit / _hmask_8bit): six pointers, what build_obmc_inter_pred_above / _left call per
+ * neighbour and plane (the _8bit forms serve the inter-intra smooth masks).  Kept apart from svtgpu_install_obmc_rtcd(), the
+ * OBMC distortion family.  Opt-in: define SVTGPU_RTCD_WITH_OBMC_BLEND before including this header.  Install after the RTCD
+ * setup; nothing copies these pointers.  An encoder whose reference pictures are on the device does not need them: it calls
+ * svtgpu_obmc_predict_batch instead. */
+#ifdef SVTGPU_RTCD_WITH_OBMC_BLEND
+#define SVTGPU_ADAPT_BLEND8(name)                                                                                              \
+    static void svtgpu_adapt_##name(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride,              \
+                                    const uint8_t *src1, uint32_t src1_stride, const uint8_t *mask, int w, int h) {            \
+        svtgpu_aom_##name(dst, dst_stride, src0, src0_stride, src1, src1_stride, mask, w, h);                                  \
+    }
+#define SVTGPU_ADAPT_BLEND_BD(name, T)                                                                                         \
+    static void svtgpu_adapt_##name(T *dst, uint32_t dst_stride, const T *src0, uint32_t src0_stride, const T *src1,           \
+                                    uint32_t src1_stride, const uint8_t *mask, int w, int h, int bd) {                         \
+        svtgpu_aom_##name(dst, dst_stride, src0, src0_stride, src1, src1_stride, mask, w, h, bd);                              \
+    }
+SVTGPU_ADAPT_BLEND8(blend_a64_vmask)
+SVTGPU_ADAPT_BLEND8(blend_a64_hmask)
+SVTGPU_ADAPT_BLEND_BD(highbd_blend_a64_vmask_16bit, uint16_t)
+SVTGPU_ADAPT_BLEND_BD(highbd_blend_a64_hmask_16bit, uint16_t)
+SVTGPU_ADAPT_BLEND_BD(highbd_blend_a64_vmask_8bit, uint8_t)
+SVTGPU_ADAPT_BLEND_BD(highbd_blend_a64_hmask_8bit, uint8_t)
+static inline void svtgpu_install_obmc_blend_rtcd(void) {
+    svt_aom_blend_a64_vmask              = svtgpu_adapt_blend_a64_vmask;
+    svt_aom_blend_a64_hmask              = svtgpu_adapt_blend_a64_hmask;
+    svt_aom_highbd_blend_a64_vmask_16bit = svtgpu_adapt_highbd_blend_a64_vmask_16bit;
+    svt_aom_highbd_blend_a64_hmask_16bit = svtgpu_adapt_highbd_blend_a64_hmask_16bit;
+    svt_aom_highbd_blend_a64_vmask_8bit  = svtgpu_adapt_highbd_blend_a64_vmask_8bit;
+    svt_aom_highbd_blend_a64_hmask_8bit  = svtgpu_adapt_highbd_blend_a64_hmask_8bit;
+}
+/* 1 when pointer i (0..5, the order above) is the library's: the adapters are private to the installing unit */
+static inline int svtgpu_obmc_blend_rtcd_bound(int i) {
+    switch (i) {
+    case 0: return svt_aom_blend_a64_vmask == svtgpu_adapt_blend_a64_vmask;
+    case 1: return svt_aom_blend_a64_hmask == svtgpu_adapt_blend_a64_hmask;
+    case 2: return svt_aom_highbd_blend_a64_vmask_16bit == svtgpu_adapt_highbd_blend_a64_vmask_16bit;
+    case 3: return svt_aom_highbd_blend_a64_hmask_16bit == svtgpu_adapt_highbd_blend_a64_hmask_16bit;
+    case 4: return svt_aom_highbd_blend_a64_vmask_8bit == svtgpu_adapt_highbd_blend_a64_vmask_8bit;
+    case 5: return svt_aom_highbd_blend_a64_hmask_8bit == svtgpu_adapt_highbd_blend_a64_hmask_8bit;
+    default: return 0;
+    }
+}
+#endif /* SVTGPU_RTCD_WITH_OBMC_BLEND */
 /* Warped motion (common_dsp_rtcd.h: svt_av1_warp_affine, svt_av1_highbd_warp_affine): two pointers, what svt_warp_plane /
  * svt_highbd_warp_plane call.  The adapters spell the ConvolveParams out; the shims refuse what the C cannot do (a p_width
  * or p_height that is no multiple of 8, a projection that leaves int32) with a code, which a void pointer cannot carry, so

@@ -52,9 +52,9 @@ __device__ __forceinline__ void load_taps(const int16_t *p, int f[8]) { // a 16-
 template <typename T>
 __device__ __forceinline__ void stage_window(const T *__restrict__ ref, int stride, int x_lo, int x_hi, int y_lo, int y_hi,
                                              int sx, int sy, int tw, int th, int mode, uint16_t *win, int li, int lps) {
-    const int ws = tw + 8, g = ws >> 2; // g in {3, 4, 6, 10}
+    const int ws = tw + 8, g = ws >> 2; // g in {3, 4, 6, 10} for a tile; 3 .. 10 for obmc_pred.hip's rectangles (tw a multiple of 4 up to 32)
     const int r_first = (mode & kVert) ? 0 : 3, r_cnt = (mode & kVert) ? th + 7 : th;
-    const int recip = (1 << 20) / g + 1; // u / g, exact for u < 39 * 10 (the error is below u / 2^20 < 1 / g)
+    const int recip = (1 << 20) / g + 1; // u / g, exact for u < 39 * 10 and every g up to 10 (the error is below u / 2^20 < 1 / g)
     for (int u = li; u < r_cnt * g; u += lps) {
         const int rr = (u * recip) >> 20, cg = u - rr * g, row = r_first + rr;
         const int gy = clamp_i(sy - 3 + row, y_lo, y_hi), gx = sx - 4 + 4 * cg;

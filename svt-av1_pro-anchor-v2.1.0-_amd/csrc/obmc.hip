@@ -381,10 +381,11 @@ extern "C" void svtgpu_obmc_batch_destroy(SvtGpuObmcBatch *b) {
     delete b;
 }
 
-extern "C" int svtgpu_obmc_set_items(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems,
-                                     const int32_t *wm_pool, int32_t wm_count, const int32_t *cost_pool,
-                                     int32_t cost_count, void *stream) {
-    if (!b || nitems < 0 || nitems > b->max_items || (nitems && (!items || !wm_pool)) || wm_count < 0 ||
+// svtgpu_obmc_set_items, and svtgpu_obmc_set_items_device_wm when wm_dev is set: then the pool is sized and its address handed
+// out, but nothing is uploaded into it (svtgpu_obmc_weighted_src_batch fills it on the device)
+static int set_items(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems, const int32_t *wm_pool, int32_t wm_count,
+                     const int32_t *cost_pool, int32_t cost_count, int32_t **wm_dev, void *stream) {
+    if (!b || nitems < 0 || nitems > b->max_items || (nitems && (!items || (!wm_pool && !wm_dev))) || wm_count < 0 ||
         cost_count < 0 || (cost_count && !cost_pool))
         return SVTGPU_ERR_INVALID_ARG;
     b->nitems = 0; // a rejected list leaves nothing to search
@@ -419,15 +420,28 @@ extern "C" int svtgpu_obmc_set_items(SvtGpuObmcBatch *b, const SvtGpuObmcItem *i
     HIP_TRY(grow(b->d_wm, b->wm_cap, (size_t)wm_count));
     HIP_TRY(grow(b->d_cost, b->cost_cap, (size_t)cost_count));
     if (nitems) HIP_TRY(hipMemcpyAsync(b->d_items, items, (size_t)nitems * sizeof *items, hipMemcpyHostToDevice, st));
-    if (wm_count)
+    if (wm_count && !wm_dev)
         HIP_TRY(hipMemcpyAsync(b->d_wm, wm_pool, (size_t)wm_count * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (cost_count)
         HIP_TRY(hipMemcpyAsync(b->d_cost, cost_pool, (size_t)cost_count * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    svtgpu_count_xfer(0, (size_t)nitems * sizeof *items + ((size_t)wm_count + cost_count) * sizeof(int32_t));
+    svtgpu_count_xfer(0, (size_t)nitems * sizeof *items + ((size_t)(wm_dev ? 0 : wm_count) + cost_count) * sizeof(int32_t));
     HIP_TRY(hipStreamSynchronize(st));
     b->nitems = nitems;
     std::memcpy(b->nclass, nclass, sizeof nclass);
+    if (wm_dev) *wm_dev = b->d_wm;
     return SVTGPU_OK;
+}
+
+extern "C" int svtgpu_obmc_set_items(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems,
+                                     const int32_t *wm_pool, int32_t wm_count, const int32_t *cost_pool,
+                                     int32_t cost_count, void *stream) {
+    return set_items(b, items, nitems, wm_pool, wm_count, cost_pool, cost_count, nullptr, stream);
+}
+
+extern "C" int svtgpu_obmc_set_items_device_wm(SvtGpuObmcBatch *b, const SvtGpuObmcItem *items, int32_t nitems, int32_t wm_count,
+                                               const int32_t *cost_pool, int32_t cost_count, int32_t **wm_dev, void *stream) {
+    if (!wm_dev) return SVTGPU_ERR_INVALID_ARG;
+    return set_items(b, items, nitems, nullptr, wm_count, cost_pool, cost_count, wm_dev, stream);
 }
 
 extern "C" int svtgpu_obmc_search(SvtGpuObmcBatch *b, const SvtGpuFrame *const *refs, int32_t item_begin,

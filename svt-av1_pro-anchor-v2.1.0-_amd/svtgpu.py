@@ -407,6 +407,38 @@ class WarpBlock(ctypes.Structure):
 
 assert ctypes.sizeof(WarpBlock) == 64 and WarpBlock.wmmat0.offset == 12 and WarpBlock.wmmat1.offset == 36
 
+
+class ObmcNeighbour(ctypes.Structure):
+    """Mirror of SvtGpuObmcNeighbour: one overlappable neighbour span, 8 bytes."""
+    _fields_ = [("rel", ctypes.c_uint8), ("size", ctypes.c_uint8), ("ref", ctypes.c_uint8), ("filters", ctypes.c_uint8),
+                ("mv_x", ctypes.c_int16), ("mv_y", ctypes.c_int16)]
+
+
+class ObmcBlock(ctypes.Structure):
+    """Mirror of SvtGpuObmcBlock: one single-reference block with its above and left neighbour lists, 96 bytes."""
+    _fields_ = [("x", ctypes.c_int16), ("y", ctypes.c_int16), ("w_log2", ctypes.c_uint8), ("h_log2", ctypes.c_uint8),
+                ("ref", ctypes.c_uint8), ("filter_x", ctypes.c_uint8), ("filter_y", ctypes.c_uint8), ("n_above", ctypes.c_uint8),
+                ("n_left", ctypes.c_uint8), ("reserved0", ctypes.c_uint8), ("mv_x", ctypes.c_int16), ("mv_y", ctypes.c_int16),
+                ("wm_offset", ctypes.c_int32), ("reserved", ctypes.c_uint8 * 12), ("nb", ObmcNeighbour * 8)]
+
+    @classmethod
+    def make(cls, x, y, w, h, ref, mv, filter_x, filter_y, above=(), left=()):
+        """w, h: luma size in samples; mv (x, y) in 1/8 luma sample; above / left: up to four spans each, dicts with rel,
+        size (units of 4 luma samples), ref, fx, fy, mv."""
+        b = cls()
+        b.x, b.y, b.w_log2, b.h_log2 = int(x), int(y), int(w).bit_length() - 1, int(h).bit_length() - 1
+        b.ref, b.filter_x, b.filter_y, b.mv_x, b.mv_y = int(ref), int(filter_x), int(filter_y), int(mv[0]), int(mv[1])
+        b.n_above, b.n_left = len(above), len(left)
+        for base, spans in ((0, above), (4, left)):
+            for k, n in enumerate(spans[:4]):
+                q = b.nb[base + k]
+                q.rel, q.size, q.ref, q.filters = int(n["rel"]), int(n["size"]), int(n["ref"]), int(n["fx"]) | int(n["fy"]) << 4
+                q.mv_x, q.mv_y = int(n["mv"][0]), int(n["mv"][1])
+        return b
+
+
+assert ctypes.sizeof(ObmcNeighbour) == 8 and ctypes.sizeof(ObmcBlock) == 96 and ObmcBlock.nb.offset == 32
+
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
     "svtgpu_version": (ctypes.c_char_p, []),
@@ -587,6 +619,16 @@ _SIGS = {
     "svtgpu_av1_highbd_warp_affine": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P] + [_I32] * 11 + [_P] + [_I32] * 5 +
                                       [ctypes.c_int16] * 4),
     "svtgpu_warp_predict_batch": (ctypes.c_int, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P]),
+    "svtgpu_obmc_mask": (ctypes.c_int, [_I32, ctypes.POINTER(_P)]),
+    **{"svtgpu_aom_blend_a64_%smask" % d: (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, _I32, _I32])
+       for d in "vh"},
+    **{"svtgpu_aom_highbd_blend_a64_%smask_%s" % (d, f): (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P,
+                                                                 _I32, _I32, _I32]) for d in "vh" for f in ("16bit", "8bit")},
+    "svtgpu_obmc_weighted_src_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32, _P, _I32,
+                                                      ctypes.POINTER(ObmcBlock), _I32, _P, _I32, _P]),
+    "svtgpu_obmc_set_items_device_wm": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_P), _P]),
+    "svtgpu_obmc_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32, ctypes.POINTER(ObmcBlock), _I32,
+                                                 _I32, _I32, ctypes.POINTER(TfPlanes), _P]),
     "svtgpu_tf_search_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                               ctypes.POINTER(TfFullpel), ctypes.POINTER(TfSearchParams), _P]),
     "svtgpu_tf_search_read": (ctypes.c_int, [_P, _I32, ctypes.POINTER(TfMotion), ctypes.POINTER(TfBlock), _P]),
@@ -1230,6 +1272,20 @@ class ObmcBatch:
                                           cp.size, stream))
         self.nitems = len(items)
 
+    def set_items_device_wm(self, items, wm_count, cost_pool=None, stream=None):
+        """svtgpu_obmc_set_items_device_wm: as set_items without a pool; returns the device address of the batch's pool of
+        wm_count int32 entries, for TfState.obmc_weighted_src_batch to fill."""
+        arr = (ObmcItem * max(len(items), 1))()
+        for i, it in enumerate(items):
+            arr[i] = it if isinstance(it, ObmcItem) else ObmcItem(**{k: int(it[k]) for k in ObmcItem.FIELDS})
+        cp = np.ascontiguousarray(cost_pool if cost_pool is not None else np.zeros(0), dtype=np.int32)
+        self.nitems = 0
+        wm = _P()
+        check(lib().svtgpu_obmc_set_items_device_wm(self.h, arr, len(items), int(wm_count), ptr(cp) if cp.size else None, cp.size,
+                                                    ctypes.byref(wm), stream))
+        self.nitems = len(items)
+        return wm.value
+
     def search(self, refs, item_begin=0, item_end=None, stream=None):
         assert len(refs) == self.nref
         arr = (_P * self.nref)(*[r.h for r in refs])
@@ -1720,6 +1776,21 @@ class TfState:
         ra, ba = (TfPlanes * max(n, 1))(*refs), (WarpBlock * max(nb, 1))(*blocks)
         check(lib().svtgpu_warp_predict_batch(self.h, ra, n, ba, nb, int(bit_depth), int(chroma), ctypes.byref(pred), stream))
 
+    def obmc_predict_batch(self, refs, border_x, border_y, blocks, bit_depth, chroma, pred, stream=None):
+        """svtgpu_obmc_predict_batch: refs a list of TfPlanes at sample (0, 0) of the padded pictures; blocks a list of
+        ObmcBlock; pred one TfPlanes, the predictor picture."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (ObmcBlock * max(nb, 1))(*blocks)
+        check(lib().svtgpu_obmc_predict_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, int(bit_depth), int(chroma),
+                                              ctypes.byref(pred), stream))
+
+    def obmc_weighted_src_batch(self, refs, border_x, border_y, src_luma, src_stride, blocks, wm_dev, wm_count, stream=None):
+        """svtgpu_obmc_weighted_src_batch: src_luma / wm_dev device addresses; blocks a list of ObmcBlock with wm_offset set."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (ObmcBlock * max(nb, 1))(*blocks)
+        check(lib().svtgpu_obmc_weighted_src_batch(self.h, ra, n, int(border_x), int(border_y), src_luma, int(src_stride), ba, nb,
+                                                   wm_dev, int(wm_count), stream))
+
     def search_frame(self, centre, refs, border_x, border_y, fullpel, params, stream=None):
         """centre: TfPlanes (luma read); refs: a list of TfPlanes at sample (0, 0) of the padded pictures; fullpel: a list
         of TfFullpel, [reference][block] flattened; params: TfSearchParams.  The records stay on the device."""
@@ -1829,6 +1900,27 @@ def warp_filter_table():
     t, n = _P(), _I32(0)
     check(lib().svtgpu_warp_filter_table(ctypes.byref(t), ctypes.byref(n)))
     return np.ctypeslib.as_array(ctypes.cast(t, _I16P), (n.value, 8)).copy()
+
+
+def blend_a64_mask(direction, dst, src0, src1, mask, w, h, bd=8, form=None):
+    """One of the six OBMC blend shims on host arrays given as (array, x0, y0): direction "v" or "h"; form None (8-bit
+    samples), "16bit", or "8bit" (16-bit samples behind a uint8_t *).  dst is written in place."""
+    def at(v):
+        a, x0, y0 = v
+        ptr = a.ctypes.data + y0 * a.strides[0] + x0 * a.itemsize
+        return ptr, a.strides[0] // a.itemsize
+    m = (ctypes.c_uint8 * len(mask))(*[int(v) for v in mask])
+    (dp, ds), (p0, s0), (p1, s1) = at(dst), at(src0), at(src1)
+    name = "svtgpu_aom_blend_a64_%smask" % direction if form is None else "svtgpu_aom_highbd_blend_a64_%smask_%s" % (direction, form)
+    args = [dp, ds, p0, s0, p1, s1, m, int(w), int(h)]
+    getattr(lib(), name)(*(args if form is None else args + [int(bd)]))
+
+
+def obmc_mask(length):
+    """svtgpu_obmc_mask: the 1-D OBMC mask of `length` (1, 2, 4, 8, 16 or 32) as a list (host only)."""
+    m = _P()
+    check(lib().svtgpu_obmc_mask(int(length), ctypes.byref(m)))
+    return list(ctypes.cast(m, ctypes.POINTER(ctypes.c_uint8))[:int(length)])
 
 
 def warp_shear_params(wmmat):

@@ -121,7 +121,10 @@ const char *svtgpu_version(void);
  * svtgpu_av1_warp_affine / svtgpu_av1_highbd_warp_affine, svtgpu_warp_shear_params, svtgpu_warp_filter_table, SvtGpuWarpBlock
  * and svtgpu_warp_predict_batch; 19: OBMC prediction: svtgpu_obmc_mask, SvtGpuObmcNeighbour / SvtGpuObmcBlock and
  * svtgpu_obmc_predict_batch, the six svtgpu_aom_(highbd_)blend_a64_{v,h}mask shims,
- * svtgpu_obmc_weighted_src_batch and svtgpu_obmc_set_items_device_wm).
+ * svtgpu_obmc_weighted_src_batch and svtgpu_obmc_set_items_device_wm; 19, additive: inter-intra prediction:
+ * SvtGpuInterIntraBlock, svtgpu_interintra_predict_batch, svtgpu_interintra_mode_sse_batch, svtgpu_interintra_smooth_mask, the
+ * two svtgpu_aom_(highbd_)blend_a64_mask shims and the two svtgpu_aom_(highbd_)intra_predictor shims -- new entries and a new
+ * struct only, so no bump).
  * A caller built against another header checks svtgpu_abi_version() ==
  * SVTGPU_ABI_VERSION once at start-up and refuses to run on a mismatch. */
 #define SVTGPU_ABI_VERSION 19
@@ -1340,7 +1343,7 @@ int svtgpu_tf_compensate_filter_frame(SvtGpuTfState *state, const SvtGpuTfPlanes
  * svt_aom_convolveHbd[][][1] tables hold), the frame-distance weights of COMPOUND_DISTWTD
  * (svt_av1_dist_wtd_comp_weight_assign, :276-318), and svt_aom_inter_prediction (EbEncInterPrediction.c:4070) with
  * is_compound = 1 for a list of blocks in one launch, bit-exact with the reference's C.  The masked compounds
- * (COMPOUND_WEDGE, COMPOUND_DIFFWTD) are the next section's; inter-intra, warped and scaled references (OBMC blending: the OBMC section),
+ * (COMPOUND_WEDGE, COMPOUND_DIFFWTD) are the next section's; scaled references (warped motion, OBMC blending and inter-intra: their own sections),
  * intrabc and 12-bit pictures at frame level (the shims handle 12 bits) stay on the host.
  * ========================================================================================= */
 /* RTCD shims: host pointers, synchronous, staged through a device buffer of the calling thread.  filter_x / filter_y are
@@ -1576,7 +1579,8 @@ int svtgpu_warp_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, 
  * weighted source and mask of svt_aom_precompute_obmc_data (calc_target_weighted_pred, :1767-1827) written on the device into
  * the pool that svtgpu_obmc_search reads.  What stays on the host: the mode-info walk that finds the neighbours
  * (foreach_overlappable_nb_*), the hbd_md weighted sources (10-bit strips unpacked to 8), an
- * svt_av1_calc_target_weighted_pred_* RTCD adapter, OBMC over scaled references, inter-intra and 12-bit pictures at frame level.
+ * svt_av1_calc_target_weighted_pred_* RTCD adapter, OBMC over scaled references, inter-intra over an OBMC prediction (plain
+ * inter-intra: the next section) and 12-bit pictures at frame level.
  * ========================================================================================= */
 /* RTCD shims of svt_aom_blend_a64_vmask / _hmask (EbBlend_a64_mask.c:302, :350), svt_aom_highbd_blend_a64_vmask_16bit / _hmask_16bit
  * (C_DEFAULT/EbBlend_a64_mask_c.c:15, EbInterPrediction.c:2383) and the two _8bit forms (the same arithmetic on 16-bit samples behind
@@ -1661,6 +1665,105 @@ int svtgpu_obmc_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, 
 int svtgpu_obmc_weighted_src_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
                                    int32_t border_y, const void *src_luma, int32_t src_stride, const SvtGpuObmcBlock *blocks,
                                    int32_t n_blocks, int32_t *wm_dev, int32_t wm_count, void *stream);
+
+/* =========================================================================================
+ * AV1 inter-intra prediction: inter_intra_prediction (EbEncInterPrediction.c:2548-2745) behind svt_aom_inter_prediction with
+ * is_interintra_used = 1, for a list of single-reference blocks, bit-exact with the reference's C; 8- and 10-bit, 4:2:0,
+ * translation, unscaled references.  One launch does the block's single-reference prediction, the intra prediction of the
+ * four inter-intra modes (II_DC_PRED, II_V_PRED, II_H_PRED, II_SMOOTH_PRED: build_intra_predictors' edge preparation and the
+ * dc / dc_top / dc_left / dc_128 / v / h / smooth predictors), the smooth or wedge mask and the blend
+ * (svt_aom_combine_interintra(_highbd), EbInterPrediction.c:2190, :2350).  Beside it: the four-mode luma distortion that
+ * inter_intra_search (EbModeDecision.c:275-478) runs per candidate, the smooth masks on the host, and RTCD shims of
+ * svt_aom_(highbd_)blend_a64_mask and of the intra predictors.  What stays on the host: reading the recon neighbour arrays
+ * and the availability from mode info (the caller hands the raw neighbour samples and counts over), the wedge inter-intra
+ * search (pick_interintra_wedge, pick_wedge_fixed_sign, svt_av1_wedge_sse_from_residuals), model_rd_for_sb_with_curvfit,
+ * every other intra mode, inter-intra over warped or OBMC predictions or scaled references, and 12-bit pictures at frame level.
+ * ========================================================================================= */
+#define SVTGPU_II_DC_PRED 0
+#define SVTGPU_II_V_PRED 1
+#define SVTGPU_II_H_PRED 2
+#define SVTGPU_II_SMOOTH_PRED 3
+/* build_smooth_interintra_mask (EbInterPrediction.c:2153-2188): the w * h bytes (stride w) of the smooth inter-intra mask of
+ * `mode` (0 .. 3, InterIntraMode) for one of the ten plane sizes inter-intra reaches: 4x4, 4x8, 8x4, 8x8, 8x16, 16x8, 16x16,
+ * 16x32, 32x16, 32x32.  Host only; the counterpart of svtgpu_wedge_mask and svtgpu_obmc_mask.  SVTGPU_ERR_INVALID_ARG: any
+ * other size, a mode above 3, a null pointer. */
+int svtgpu_interintra_smooth_mask(int32_t w, int32_t h, int32_t mode, uint8_t *mask);
+typedef struct SvtGpuInterIntraBlock {    /* one single-reference inter-intra block; 32 bytes */
+    int16_t x, y;                          /* luma position, multiples of 8 */
+    uint8_t w_log2, h_log2;                /* luma size, one of 8x8, 8x16, 16x8, 16x16, 16x32, 32x16, 32x32 */
+    uint8_t ref, filter_x, filter_y;       /* the reference (index into refs[]) and dual filter, as SvtGpuObmcBlock */
+    uint8_t mode;                          /* InterIntraMode: SVTGPU_II_DC_PRED .. SVTGPU_II_SMOOTH_PRED */
+    uint8_t use_wedge, wedge_index;        /* 0: the smooth mask of `mode`; 1: wedge `wedge_index` (0 .. 15), sign 0 */
+    int16_t mv_x, mv_y;                    /* the MV, 1/8 luma sample */
+    uint8_t n_top[2], n_left[2];           /* n_top_px / n_left_px of build_intra_predictors, [0] luma, [1] chroma: 0 .. the
+                                              plane's width / height */
+    int32_t edge_offset;                   /* where the block's neighbour samples begin in the edge pool */
+    uint8_t reserved[8];                   /* must be zero */
+} SvtGpuInterIntraBlock;
+/* The inter-intra blocks of one picture in one launch: for every block of blocks[n_blocks] (host memory, copied before the
+ * call returns) what svt_aom_inter_prediction writes with is_compound = 0, SIMPLE_TRANSLATION and is_interintra_used = 1, luma
+ * and -- with chroma != 0 -- the two 4:2:0 chroma planes at (x / 2, y / 2): per plane the block's own prediction from
+ * refs[ref] (as svtgpu_obmc_predict_batch with empty lists), blended sample by sample with the intra prediction of
+ * interintra_to_intra_mode[mode] at the plane's block size: pred = (m * intra + (64 - m) * inter + 32) >> 6.  m is the smooth
+ * mask of (mode, the plane's size), or with use_wedge the wedge mask of the luma size, index wedge_index, sign 0, read for
+ * chroma as the rounded mean of its 2x2 luma entries.
+ * edges: the edge pool, host memory of n_edges samples of the picture's sample type (uint8_t at 8 bits, uint16_t at 10), copied
+ * with the metadata before the call returns.  At edge_offset a block holds above[w], left[h] of luma, then above[w / 2],
+ * left[h / 2] of Cb and the same of Cr: the raw neighbour samples, of which above[0 .. n_top) and left[0 .. n_left) are read.
+ * The library prepares the edges as build_intra_predictors does for these modes: the last read sample repeated to the side's
+ * length; with no samples the other side's first one, or 128 << (bd - 8) less one (above) / plus one (left) when there are
+ * none at all; DC takes dc, dc_top, dc_left or dc_128 by which counts are non-zero.  With chroma == 0 the chroma parts need not
+ * exist.  A block lies whole inside the state's picture and its MV is clamped against that picture (a block the encoder lets
+ * hang over the coded picture's edge is given with its shortened counts; its MV must not need the clamp of the shorter
+ * picture).  `state`, refs, pred, the border and the read clamp, stream order, n_blocks == 0 and overlapping blocks are
+ * svtgpu_compound_predict_batch's, word for word.
+ * SVTGPU_ERR_UNSUPPORTED: n_refs > 26.  SVTGPU_ERR_INVALID_ARG before any launch, pred untouched: a null pointer (edges only
+ * when n_blocks > 0), n_refs < 0, n_blocks < 0, n_edges < 0, a bit depth other than 8 or 10, a negative border, a misaligned or
+ * too narrow plane, a block that leaves the picture area or is not at a multiple of 8, a size outside the seven, ref >=
+ * n_refs, a filter kind above 3, mode > 3, use_wedge > 1, wedge_index > 15, a count above the plane's side, an edge_offset that
+ * is negative or whose samples leave n_edges, a non-zero reserved byte. */
+int svtgpu_interintra_predict_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                                    int32_t border_y, const SvtGpuInterIntraBlock *blocks, int32_t n_blocks, const void *edges,
+                                    int32_t n_edges, int32_t bit_depth, int32_t chroma, const SvtGpuTfPlanes *pred, void *stream);
+/* inter_intra_search's distortion: for every block i and each mode m = 0 .. 3, luma only, sse_dev[4 * i + m] = the sum of
+ * squared differences (svt_aom_sse / svt_aom_highbd_sse) between the source block and the smooth blend
+ * (svt_aom_combine_interintra with use_wedge = 0) of the block's inter prediction with mode m's intra prediction.  The blocks'
+ * mode, use_wedge and wedge_index are not looked at, nor the chroma counts and edges.  src_luma: a device plane of the
+ * picture's sample type at sample (0, 0) of the source, src_stride >= width, in samples.  sse_dev: device memory of 4 *
+ * n_blocks int64, 8-byte aligned, written in stream order.  The rest as svtgpu_interintra_predict_batch.
+ * SVTGPU_ERR_INVALID_ARG before any launch: that entry's refusals that do not concern pred, mode, use_wedge, wedge_index or
+ * chroma; a null src_luma or sse_dev, a misaligned one, a src_stride below the width. */
+int svtgpu_interintra_mode_sse_batch(SvtGpuTfState *state, const SvtGpuTfPlanes *refs, int32_t n_refs, int32_t border_x,
+                                     int32_t border_y, const SvtGpuInterIntraBlock *blocks, int32_t n_blocks, const void *edges,
+                                     int32_t n_edges, int32_t bit_depth, const void *src_luma, int32_t src_stride,
+                                     int64_t *sse_dev, void *stream);
+/* RTCD shims of svt_aom_blend_a64_mask and svt_aom_highbd_blend_a64_mask (EbBlend_a64_mask.c:201-299): dst = (m * src0 +
+ * (64 - m) * src1 + 32) >> 6 with m the mask entry (subw = subh = 0), the rounded mean of the 2x2 entries (1, 1), or the
+ * rounded mean of the horizontal (1, 0) or vertical (0, 1) pair.  The high-bit-depth form takes 16-bit samples behind a
+ * uint8_t * that is cast, not shifted, as this encoder's C reads them.  Host pointers, synchronous, staged through the calling
+ * thread's buffer with one reservation.  w, h powers of two from 1 to 128; strides in elements, at least w; mask_stride at
+ * least w << subw; mask entries 0 .. 64; bd 8, 10 or 12 (not otherwise used).  src0 / src1 may alias dst: every read happens
+ * before any write.  Bad arguments are fatal, as for the other void shims. */
+void svtgpu_aom_blend_a64_mask(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1,
+                               uint32_t src1_stride, const uint8_t *mask, uint32_t mask_stride, int w, int h, int subw, int subh);
+void svtgpu_aom_highbd_blend_a64_mask(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride,
+                                      const uint8_t *src1, uint32_t src1_stride, const uint8_t *mask, uint32_t mask_stride, int w,
+                                      int h, int subw, int subh, int bd);
+/* The intra predictors inter-intra uses, as two generic entries: the w x h block into dst (stride in samples) from above[w] and
+ * left[h], by `kind`: svt_aom_(highbd_)dc / dc_top / dc_left / dc_128 / v / h / smooth _predictor_WxH
+ * (EbIntraPrediction.c:1041-1134, :1240+, :1351+).  w, h in {4, 8, 16, 32}; bd 8, 10 or 12.  Host pointers, synchronous; bad
+ * arguments are fatal.  svtgpu_install_interintra_rtcd binds the per-size RTCD names to wrappers of these. */
+#define SVTGPU_INTRA_DC 0
+#define SVTGPU_INTRA_DC_TOP 1
+#define SVTGPU_INTRA_DC_LEFT 2
+#define SVTGPU_INTRA_DC_128 3
+#define SVTGPU_INTRA_V 4
+#define SVTGPU_INTRA_H 5
+#define SVTGPU_INTRA_SMOOTH 6
+void svtgpu_aom_intra_predictor(uint8_t *dst, ptrdiff_t stride, const uint8_t *above, const uint8_t *left, int32_t w, int32_t h,
+                                int32_t kind);
+void svtgpu_aom_highbd_intra_predictor(uint16_t *dst, ptrdiff_t stride, const uint16_t *above, const uint16_t *left, int32_t w,
+                                       int32_t h, int32_t kind, int32_t bd);
 
 /* =========================================================================================
  * Loop restoration

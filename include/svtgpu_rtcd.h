@@ -660,4 +660,62 @@ static inline int svtgpu_warp_rtcd_bound(int i) {
     }
 }
 #endif /* SVTGPU_RTCD_WITH_WARP */
+/* Inter-intra (common_dsp_rtcd.h): the two blends svt_aom_blend_a64_mask / svt_aom_highbd_blend_a64_mask that
+ * svt_aom_combine_interintra(_highbd) calls, and the per-size intra predictors svt_aom_(highbd_){dc, dc_top, dc_left, dc_128, v,
+ * h, smooth}_predictor_WxH of the ten plane sizes inter-intra reaches: 2 + 2 * 7 * 10 = 142 pointers, each predictor a wrapper
+ * of svtgpu_aom_(highbd_)intra_predictor generated from one list.  Opt-in: define SVTGPU_RTCD_WITH_INTERINTRA before including
+ * this header.  Install point: after the RTCD setup and BEFORE svt_aom_init_intra_predictors_internal (EbEncHandle.c:1539),
+ * which copies the predictor pointers into svt_aom_eb_pred / svt_aom_dc_pred and their highbd tables: build_intra_predictors
+ * calls through those tables, so an install after it changes nothing the encoder calls (the interp install's caveat).  The two
+ * blend pointers are called directly and may be bound at any time.  An encoder whose reference pictures are on the device
+ * does not need them: it calls svtgpu_interintra_predict_batch instead. */
+#ifdef SVTGPU_RTCD_WITH_INTERINTRA
+#define SVTGPU_II_SIZES(X, k) X(k, 4, 4) X(k, 4, 8) X(k, 8, 4) X(k, 8, 8) X(k, 8, 16) X(k, 16, 8) X(k, 16, 16) X(k, 16, 32) X(k, 32, 16) X(k, 32, 32)
+#define SVTGPU_II_KINDS(X)                                                                                                     \
+    SVTGPU_II_SIZES(X, dc) SVTGPU_II_SIZES(X, dc_top) SVTGPU_II_SIZES(X, dc_left) SVTGPU_II_SIZES(X, dc_128) SVTGPU_II_SIZES(X, v) \
+    SVTGPU_II_SIZES(X, h) SVTGPU_II_SIZES(X, smooth)
+enum { svtgpu_ii_kind_dc = SVTGPU_INTRA_DC, svtgpu_ii_kind_dc_top = SVTGPU_INTRA_DC_TOP, svtgpu_ii_kind_dc_left = SVTGPU_INTRA_DC_LEFT,
+       svtgpu_ii_kind_dc_128 = SVTGPU_INTRA_DC_128, svtgpu_ii_kind_v = SVTGPU_INTRA_V, svtgpu_ii_kind_h = SVTGPU_INTRA_H,
+       svtgpu_ii_kind_smooth = SVTGPU_INTRA_SMOOTH };
+#define SVTGPU_II_ADAPT(k, w, h)                                                                                               \
+    static void svtgpu_adapt_##k##_predictor_##w##x##h(uint8_t *dst, ptrdiff_t stride, const uint8_t *above, const uint8_t *left) { \
+        svtgpu_aom_intra_predictor(dst, stride, above, left, w, h, svtgpu_ii_kind_##k);                                        \
+    }                                                                                                                          \
+    static void svtgpu_adapt_highbd_##k##_predictor_##w##x##h(uint16_t *dst, ptrdiff_t stride, const uint16_t *above,          \
+                                                              const uint16_t *left, int32_t bd) {                              \
+        svtgpu_aom_highbd_intra_predictor(dst, stride, above, left, w, h, svtgpu_ii_kind_##k, bd);                             \
+    }
+SVTGPU_II_KINDS(SVTGPU_II_ADAPT)
+static void svtgpu_adapt_blend_a64_mask(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride,
+                                        const uint8_t *src1, uint32_t src1_stride, const uint8_t *mask, uint32_t mask_stride, int w,
+                                        int h, int subx, int suby) {
+    svtgpu_aom_blend_a64_mask(dst, dst_stride, src0, src0_stride, src1, src1_stride, mask, mask_stride, w, h, subx, suby);
+}
+static void svtgpu_adapt_highbd_blend_a64_mask(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride,
+                                               const uint8_t *src1, uint32_t src1_stride, const uint8_t *mask, uint32_t mask_stride,
+                                               int w, int h, int subx, int suby, int bd) {
+    svtgpu_aom_highbd_blend_a64_mask(dst, dst_stride, src0, src0_stride, src1, src1_stride, mask, mask_stride, w, h, subx, suby, bd);
+}
+#define SVTGPU_II_BIND(k, w, h)                                                                                                \
+    svt_aom_##k##_predictor_##w##x##h        = svtgpu_adapt_##k##_predictor_##w##x##h;                                         \
+    svt_aom_highbd_##k##_predictor_##w##x##h = svtgpu_adapt_highbd_##k##_predictor_##w##x##h;
+static inline void svtgpu_install_interintra_rtcd(void) {
+    svt_aom_blend_a64_mask        = svtgpu_adapt_blend_a64_mask;
+    svt_aom_highbd_blend_a64_mask = svtgpu_adapt_highbd_blend_a64_mask;
+    SVTGPU_II_KINDS(SVTGPU_II_BIND)
+}
+#define SVTGPU_INTERINTRA_RTCD_COUNT 142
+/* 1 when pointer i (0 .. 141) is the library's: 0 and 1 the blends, then per (kind, size) of the list the 8-bit and the highbd
+ * pointer; the adapters are private to the installing unit */
+#define SVTGPU_II_PROBE(k, w, h)                                                                                               \
+    if (i == n++) return svt_aom_##k##_predictor_##w##x##h == svtgpu_adapt_##k##_predictor_##w##x##h;                          \
+    if (i == n++) return svt_aom_highbd_##k##_predictor_##w##x##h == svtgpu_adapt_highbd_##k##_predictor_##w##x##h;
+static inline int svtgpu_interintra_rtcd_bound(int i) {
+    int n = 2;
+    if (i == 0) return svt_aom_blend_a64_mask == svtgpu_adapt_blend_a64_mask;
+    if (i == 1) return svt_aom_highbd_blend_a64_mask == svtgpu_adapt_highbd_blend_a64_mask;
+    SVTGPU_II_KINDS(SVTGPU_II_PROBE)
+    return 0;
+}
+#endif /* SVTGPU_RTCD_WITH_INTERINTRA */
 #endif /* SVTGPU_RTCD_H */

@@ -439,6 +439,31 @@ class ObmcBlock(ctypes.Structure):
 
 assert ctypes.sizeof(ObmcNeighbour) == 8 and ctypes.sizeof(ObmcBlock) == 96 and ObmcBlock.nb.offset == 32
 
+
+class InterIntraBlock(ctypes.Structure):
+    """Mirror of SvtGpuInterIntraBlock: one single-reference inter-intra block, 32 bytes."""
+    _fields_ = [("x", ctypes.c_int16), ("y", ctypes.c_int16), ("w_log2", ctypes.c_uint8), ("h_log2", ctypes.c_uint8),
+                ("ref", ctypes.c_uint8), ("filter_x", ctypes.c_uint8), ("filter_y", ctypes.c_uint8), ("mode", ctypes.c_uint8),
+                ("use_wedge", ctypes.c_uint8), ("wedge_index", ctypes.c_uint8), ("mv_x", ctypes.c_int16), ("mv_y", ctypes.c_int16),
+                ("n_top", ctypes.c_uint8 * 2), ("n_left", ctypes.c_uint8 * 2), ("edge_offset", ctypes.c_int32),
+                ("reserved", ctypes.c_uint8 * 8)]
+
+    @classmethod
+    def make(cls, x, y, w, h, ref, mv, filter_x, filter_y, mode, use_wedge=0, wedge_index=0, n_top=(0, 0), n_left=(0, 0),
+             edge_offset=0):
+        """w, h: luma size in samples; mv (x, y) in 1/8 luma sample; mode 0 .. 3 (II_DC / V / H / SMOOTH); n_top / n_left:
+        (luma, chroma) counts of neighbour samples; edge_offset: the block's first sample in the edge pool."""
+        b = cls()
+        b.x, b.y, b.w_log2, b.h_log2 = int(x), int(y), int(w).bit_length() - 1, int(h).bit_length() - 1
+        b.ref, b.filter_x, b.filter_y, b.mv_x, b.mv_y = int(ref), int(filter_x), int(filter_y), int(mv[0]), int(mv[1])
+        b.mode, b.use_wedge, b.wedge_index, b.edge_offset = int(mode), int(use_wedge), int(wedge_index), int(edge_offset)
+        b.n_top[0], b.n_top[1], b.n_left[0], b.n_left[1] = int(n_top[0]), int(n_top[1]), int(n_left[0]), int(n_left[1])
+        return b
+
+
+assert ctypes.sizeof(InterIntraBlock) == 32 and InterIntraBlock.mv_x.offset == 12 and InterIntraBlock.edge_offset.offset == 20
+INTRA_KINDS = ("dc", "dc_top", "dc_left", "dc_128", "v", "h", "smooth")
+
 _SIGS = {
     "svtgpu_device_available": (ctypes.c_int, []),
     "svtgpu_version": (ctypes.c_char_p, []),
@@ -629,6 +654,18 @@ _SIGS = {
     "svtgpu_obmc_set_items_device_wm": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_P), _P]),
     "svtgpu_obmc_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32, ctypes.POINTER(ObmcBlock), _I32,
                                                  _I32, _I32, ctypes.POINTER(TfPlanes), _P]),
+    "svtgpu_interintra_smooth_mask": (ctypes.c_int, [_I32, _I32, _I32, _P]),
+    "svtgpu_interintra_predict_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
+                                                       ctypes.POINTER(InterIntraBlock), _I32, _P, _I32, _I32, _I32,
+                                                       ctypes.POINTER(TfPlanes), _P]),
+    "svtgpu_interintra_mode_sse_batch": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
+                                                        ctypes.POINTER(InterIntraBlock), _I32, _P, _I32, _I32, _P, _I32, _P, _P]),
+    "svtgpu_aom_blend_a64_mask": (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "svtgpu_aom_highbd_blend_a64_mask": (None, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, ctypes.c_uint32,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "svtgpu_aom_intra_predictor": (None, [_P, ctypes.c_ssize_t, _P, _P, _I32, _I32, _I32]),
+    "svtgpu_aom_highbd_intra_predictor": (None, [_P, ctypes.c_ssize_t, _P, _P, _I32, _I32, _I32, _I32]),
     "svtgpu_tf_search_frame": (ctypes.c_int, [_P, ctypes.POINTER(TfPlanes), ctypes.POINTER(TfPlanes), _I32, _I32, _I32,
                                               ctypes.POINTER(TfFullpel), ctypes.POINTER(TfSearchParams), _P]),
     "svtgpu_tf_search_read": (ctypes.c_int, [_P, _I32, ctypes.POINTER(TfMotion), ctypes.POINTER(TfBlock), _P]),
@@ -1791,6 +1828,26 @@ class TfState:
         check(lib().svtgpu_obmc_weighted_src_batch(self.h, ra, n, int(border_x), int(border_y), src_luma, int(src_stride), ba, nb,
                                                    wm_dev, int(wm_count), stream))
 
+    def interintra_predict_batch(self, refs, border_x, border_y, blocks, edges, bit_depth, chroma, pred, stream=None):
+        """svtgpu_interintra_predict_batch: refs a list of TfPlanes at sample (0, 0) of the padded pictures; blocks a list of
+        InterIntraBlock; edges the edge pool, a 1-D numpy array of the picture's sample type (uint8 / uint16); pred one
+        TfPlanes, the predictor picture."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (InterIntraBlock * max(nb, 1))(*blocks)
+        assert edges.dtype == (np.uint16 if bit_depth > 8 else np.uint8) and edges.flags.c_contiguous
+        check(lib().svtgpu_interintra_predict_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, edges.ctypes.data,
+                                                    int(edges.size), int(bit_depth), int(chroma), ctypes.byref(pred), stream))
+
+    def interintra_mode_sse_batch(self, refs, border_x, border_y, blocks, edges, bit_depth, src_luma, src_stride, sse_dev,
+                                  stream=None):
+        """svtgpu_interintra_mode_sse_batch: as interintra_predict_batch; src_luma / sse_dev device addresses (the source luma
+        plane of the picture's sample type; 4 * len(blocks) int64)."""
+        n, nb = len(refs), len(blocks)
+        ra, ba = (TfPlanes * max(n, 1))(*refs), (InterIntraBlock * max(nb, 1))(*blocks)
+        assert edges.dtype == (np.uint16 if bit_depth > 8 else np.uint8) and edges.flags.c_contiguous
+        check(lib().svtgpu_interintra_mode_sse_batch(self.h, ra, n, int(border_x), int(border_y), ba, nb, edges.ctypes.data,
+                                                     int(edges.size), int(bit_depth), src_luma, int(src_stride), sse_dev, stream))
+
     def search_frame(self, centre, refs, border_x, border_y, fullpel, params, stream=None):
         """centre: TfPlanes (luma read); refs: a list of TfPlanes at sample (0, 0) of the padded pictures; fullpel: a list
         of TfFullpel, [reference][block] flattened; params: TfSearchParams.  The records stay on the device."""
@@ -1921,6 +1978,44 @@ def obmc_mask(length):
     m = _P()
     check(lib().svtgpu_obmc_mask(int(length), ctypes.byref(m)))
     return list(ctypes.cast(m, ctypes.POINTER(ctypes.c_uint8))[:int(length)])
+
+
+def interintra_smooth_mask(w, h, mode):
+    """svtgpu_interintra_smooth_mask: the smooth inter-intra mask of `mode` for a w x h plane block as a uint8 array [h][w]
+    (host only)."""
+    m = np.zeros((int(h), int(w)), np.uint8)
+    check(lib().svtgpu_interintra_smooth_mask(int(w), int(h), int(mode), m.ctypes.data))
+    return m
+
+
+def blend_a64_mask2d(dst, src0, src1, mask, w, h, subw, subh, bd=None):
+    """svtgpu_aom_blend_a64_mask (bd None, uint8 arrays) or svtgpu_aom_highbd_blend_a64_mask (uint16 arrays) on host arrays
+    given as (array, x0, y0); mask a uint8 array [h << subh][w << subw] (any row stride).  dst is written in place."""
+    def at(v):
+        a, x0, y0 = v
+        return a.ctypes.data + y0 * a.strides[0] + x0 * a.itemsize, a.strides[0] // a.itemsize
+    assert mask.dtype == np.uint8
+    (dp, ds), (p0, s0), (p1, s1) = at(dst), at(src0), at(src1)
+    args = [dp, ds, p0, s0, p1, s1, mask.ctypes.data, mask.strides[0], int(w), int(h), int(subw), int(subh)]
+    if bd is None:
+        lib().svtgpu_aom_blend_a64_mask(*args)
+    else:
+        lib().svtgpu_aom_highbd_blend_a64_mask(*(args + [int(bd)]))
+
+
+def intra_predictor(kind, above, left, bd=None):
+    """svtgpu_aom_intra_predictor (bd None, uint8) or svtgpu_aom_highbd_intra_predictor (uint16): the len(left) x len(above)
+    block of `kind` (a name of INTRA_KINDS) as an array [h][w]."""
+    hbd = bd is not None
+    t = np.uint16 if hbd else np.uint8
+    a, l = np.ascontiguousarray(above, t), np.ascontiguousarray(left, t)
+    out = np.zeros((l.size, a.size), t)
+    args = [out.ctypes.data, a.size, a.ctypes.data, l.ctypes.data, a.size, l.size, INTRA_KINDS.index(kind)]
+    if hbd:
+        lib().svtgpu_aom_highbd_intra_predictor(*(args + [int(bd)]))
+    else:
+        lib().svtgpu_aom_intra_predictor(*args)
+    return out
 
 
 def warp_shear_params(wmmat):
